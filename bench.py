@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Headline benchmark of the Pix2Poly / FFL hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: it sets up, warms up, times exactly K steps, writes the last step's outputs if
+--dump-outputs is given, and prints the JSON line (`ms_per_step` = the milliseconds of one timed step).  Every other leg described
+below runs with --full only.
 
 N > 1 without a launcher (no WORLD_SIZE in the environment): bench.py starts `python -m torch.distributed.run --nnodes=1
 --nproc-per-node N --master-addr 127.0.0.1 bench.py <same arguments>` itself as a CHILD process - before anything here has touched the
@@ -10,20 +14,20 @@ and `setup_ddp`, misc/shared_utils.py:205-230).  Under a launcher (the driver's 
 
 A "step" = one reference train step (train/trainer_pix2poly.py:305-329) on one synthetic batch that is already resident
 in HBM: forward (encoder + fusion + decoder + 2x ScoreNet + Sinkhorn) -> 1.0*CE + 10.0*BCE -> backward -> AdamW.
-Metric (BASELINE.json): training tiles/s, whole job; `fwd_ms_per_tile` is reported in the same line.
+Metric (BASELINE.json): training tiles/s, whole job; with --full, `fwd_ms_per_tile` is reported in the same line.
 Default workload = the configuration the metric is quoted on ("224px img + 3k-pt lidar"): early-fusion Pix2Poly
 (ViT-S/8 + PointPillars stem, mnv = 64), 64 tiles per GPU, in the precision that meets north_star's tolerance at the highest rate:
-`--precision fp32x3` (fp32 storage, every product as bf16 x 3 on the bf16 MFMA; logits within 1e-3 of the oracle and token indices bit-exact - the line carries
-its own measured error as `fp32x3_vs_oracle`).  `bf16_mode` (bf16 storage, its measured error beside it) and `fp32_exact_mode` are sub-objects of the same line.
+`--precision fp32x3` (fp32 storage, every product as bf16 x 3 on the bf16 MFMA; logits within 1e-3 of the oracle and token indices bit-exact - the --full line
+carries its own measured error as `fp32x3_vs_oracle`).  `bf16_mode` (bf16 storage, its measured error beside it) and `fp32_exact_mode` are sub-objects of the --full line.
 `--workload ffl_fusion` = BASELINE configs[4]: FFL early_fusion_vit_cnn, step = forward + FFL criterion + backward + AdamW.
 
-Extra objects in the JSON line (N = 1): `roofline` (dominant kernel, HIP events on the launch stream; step-level traffic from the
+Extra objects in the JSON line (N = 1, --full): `roofline` (dominant kernel, HIP events on the launch stream; step-level traffic from the
 committed PMC passes), `encoder_fwd` (the fused ViT + LiDAR encoder forward alone: the quantity the north star's MFMA fraction is defined on),
 `fp32_exact_mode` (the same step on the exact fp32 MFMA path) and `bf16_mode` (bf16 storage - faster, outside the tolerance),
 `bf16_vs_oracle` / `fp32_vs_oracle` / `fp32x3_vs_oracle` (MEASURED error of each bench model on two tiles of the
 bench batch against the oracle on the host), `dense_lidar` (the LiDAR stem at 3 k and 40 k points per tile), `ffl` (BASELINE configs[4], 5 captured steps), `image_b16` (BASELINE configs[1]: the ViT-B/16 image-only step at bs 64 in bf16 and fp32x3),
 `predict` (BASELINE configs[0]: image-only model, batch 1, 385-step greedy decode of the demo tile), `pcie_inclusive` (host-fed step, never `value`),
-`cpu_baseline` (the oracle on this box's host cores), `rank_ms_per_step` (min / max over the ranks).
+`cpu_baseline` (the oracle on the host's cores).  N > 1 lines carry `rank_ms_per_step` (min / max over the ranks) in every run.
 """
 import argparse
 import json
@@ -76,8 +80,17 @@ def parse():
     ap.add_argument("--pool", type=int, default=4, help="distinct synthetic batches cycled through")
     ap.add_argument("--no-host-feed", action="store_true", help="skip the PCIe-inclusive leg (host uint8 tiles + point lists through the device input pipeline)")
     ap.add_argument("--lean", action="store_true", help="timed loop only (= all --no-* switches; profiling / A-B runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline step (forward latency, encoder, dense LiDAR, roofline, host feed, the other precisions, "
+                         "FFL, ViT-B/16, predict, errors against the oracle, CPU baseline; each can still be switched off by its --no-* option).  "
+                         "Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32; the loss float64): the loss, "
+                         "the forward outputs, and a seeded sample of the updated parameters and of the step's gradients; 64 MB at most")
     a = ap.parse_args()
-    if a.lean:
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.lean or not a.full:
         a.no_cpu_baseline = a.no_kernel_timing = a.no_fwd = a.no_fp32_leg = a.no_predict = a.no_host_feed = a.no_ffl = a.no_b16 = True
     return a
 
@@ -136,6 +149,7 @@ class Stepper:
         # at N = 1 graph and eager steps time the same (48.66 vs 48.70 ms, profiles/r02_graph_vs_eager.txt).
         self.use_graph = use_graph and (not reducer.active or reducer.graph_safe)
         self.out = None
+        self.outputs = None                  # the forward's outputs of the last step (static tensors of the graph once it is captured)
 
     def load(self, b):
         for k, v in b.items():
@@ -164,6 +178,8 @@ class Stepper:
         self.opt.zero_grad()
         self.ops.advance_rng(dev)               # new decoder dropout masks every step (device counter: replays with the graph)
         out = self._forward()
+        # detached: a forward result that still holds its autograd graph would keep that graph (and its AccumulateGrad nodes) alive into the next step
+        self.outputs = {k: v.detach() for k, v in out.items()} if isinstance(out, dict) else tuple(o.detach() for o in out)
         if self.criterion is not None:
             loss = self.criterion(out, {"gt_polygons_image": s["gt_polygons_image"], "gt_crossfield_angle": s["gt_crossfield_angle"]},
                                   normalize=True, epoch=10.0)[0]
@@ -245,6 +261,38 @@ def timed_steps(st, pool, steps, warmup, world, dev):
         spread = (-float(t[1]), float(t[0]))
     timed_steps.rank_spread = spread
     return dt, float(out)
+
+
+DUMP_CAP = 6 << 20              # elements per dumped output: a larger one is written as a seeded sample of this many
+DUMP_PARAM_SAMPLE = 1 << 20     # elements of the parameter and gradient samples
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(st, out_dir):
+    """--dump-outputs: what the last timed step handed back, one DIR/<name>.npy per array (float32; the loss float64): `loss`, the forward's
+    outputs (`logits`, `perm`; FFL: `seg`, `crossfield`), and the parameters after the step's AdamW update and the step's gradients, both
+    concatenated in model.parameters() order.  An array larger than its cap is written flattened as `<name>_sample`: the elements at
+    the same seeded positions (numpy default_rng(0), ascending) in every run, so two builds compare element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    outs = st.outputs
+    named = dict(outs) if isinstance(outs, dict) else dict(zip(("logits", "perm"), outs))
+    params = [p for p in st.model.parameters() if p.requires_grad]
+    named["params"] = torch.cat([p.detach().reshape(-1) for p in params])
+    named["grads"] = torch.cat([p.grad.reshape(-1) for p in params])
+    caps = {"params": DUMP_PARAM_SAMPLE, "grads": DUMP_PARAM_SAMPLE}
+    arrays = {"loss": np.array([float(st.out)], dtype=np.float64)}
+    for name, t in named.items():
+        k = caps.get(name, DUMP_CAP)
+        if t.numel() > k:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), size=k, replace=False))
+            t, name = t.reshape(-1)[torch.from_numpy(idx).to(t.device)], name + "_sample"
+        arrays[name] = t.detach().float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (more than {DUMP_MAX_BYTES})")
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def host_feed_leg(S, args, st, dev, kind, rank):
@@ -720,6 +768,8 @@ def main():
     ops.SYNC_BN[0] = sync_bn
     cfg, model, opt, reducer, pool, st = build(args, dev, local, args.precision, S, rank, world, sync_bn)
     dt, loss_val = timed_steps(st, pool, args.steps, max(args.warmup, 3 if st.use_graph else 0), world, dev)   # 2 eager steps + the capture stay untimed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(st, args.dump_outputs)
 
     # forward-only latency (train-mode forward of the same model state, no grad; hipGraph)
     fwd_ms = fwd_eval_ms = float("nan")

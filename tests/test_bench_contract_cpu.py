@@ -8,9 +8,9 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench():
+def _bench(*args):
     sys.path.insert(0, ROOT)
-    argv, sys.argv = sys.argv, ["bench.py"]
+    argv, sys.argv = sys.argv, ["bench.py", *args]
     try:
         import bench
         return bench, bench.parse()
@@ -27,7 +27,38 @@ def test_defaults_are_one_gpu_and_a_run_of_minutes():
     bench, a = _bench()
     assert a.gpus == 1 and a.steps == 20 and a.warmup == 5 and a.batch == 64 and a.points == 3000
     assert a.workload == "fusion_s8" and a.precision == "fp32x3" and a.graph == 1 and a.sync_bn == 1      # the headline precision meets north_star's tolerance
-    assert not (a.no_cpu_baseline or a.no_fp32_leg or a.no_predict or a.no_host_feed)      # the default run reports every leg
+    legs = ("no_cpu_baseline", "no_kernel_timing", "no_fwd", "no_fp32_leg", "no_ffl", "no_b16", "no_predict", "no_host_feed")
+    assert not a.full and a.dump_outputs is None and all(getattr(a, k) for k in legs)      # a plain run times the headline step only
+    _, f = _bench("--full")
+    assert not any(getattr(f, k) for k in legs)                                           # --full reports every leg
+    _, f = _bench("--full", "--no-ffl")
+    assert f.no_ffl and not any(getattr(f, k) for k in legs if k != "no_ffl")
+
+
+def test_dump_outputs_writes_the_last_steps_arrays(tmp_path):
+    """--dump-outputs: one float32 .npy per array (the loss float64); an array over its cap is written as the elements at fixed seeded positions,
+    the same in every run, so that two builds compare element for element."""
+    import types
+    import numpy as np
+    import torch
+    bench, _ = _bench()
+    m = torch.nn.Linear(3000, 400)                     # 1.2 M parameters: more than the parameter sample
+    for p in m.parameters():
+        p.grad = torch.full_like(p, 0.5)
+    st = types.SimpleNamespace(model=m, out=torch.tensor(1.25), outputs=(torch.arange(12.0).view(3, 4), torch.ones(2, 2, dtype=torch.float64)))
+    for d in ("a", "b"):
+        bench.dump_outputs(st, str(tmp_path / d))
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["grads_sample.npy", "logits.npy", "loss.npy", "params_sample.npy", "perm.npy"]
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == (np.float64 if f == "loss.npy" else np.float32) and np.array_equal(a, b), f
+    assert np.load(tmp_path / "a" / "loss.npy").tolist() == [1.25]
+    assert np.array_equal(np.load(tmp_path / "a" / "logits.npy"), np.arange(12.0, dtype=np.float32).reshape(3, 4))
+    flat = torch.cat([p.detach().reshape(-1) for p in m.parameters()]).numpy()
+    idx = np.sort(np.random.default_rng(0).choice(flat.size, size=bench.DUMP_PARAM_SAMPLE, replace=False))
+    assert np.array_equal(np.load(tmp_path / "a" / "params_sample.npy"), flat[idx])
+    assert (np.load(tmp_path / "a" / "grads_sample.npy") == 0.5).all()
 
 
 def test_committed_bench_line_has_the_contract_keys_and_is_self_consistent():
