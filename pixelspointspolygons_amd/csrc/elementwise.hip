@@ -167,6 +167,8 @@ __global__ void pair_mean_kernel(const T* __restrict__ feats, T* __restrict__ ou
 }
 
 // ---- ScoreNet BN1 batch statistics in closed form: h[b,i,j,c] = U[b,i,c] + V[b,j,c] ----
+// The sums are fp32 and not shift-invariant: the variance bn_finalize derives from them (E[h^2] - E[h]^2, in float64) has a relative error
+// of at most 2^-17 * E[h^2] / Var[h] (pinned by tests/test_glue_kernels_gpu.py::test_pair_stats)
 template <typename T>
 __global__ void pair_stats_kernel(const T* __restrict__ U, const T* __restrict__ V, int N, int C, float* __restrict__ sums, float* __restrict__ slab) {
     const int b = blockIdx.x;
@@ -315,20 +317,28 @@ __global__ void bn_finalize2_kernel(const float* __restrict__ sums, int C, float
     if (save_mean) { save_mean[c] = mean; save_rstd[c] = rstd; }
 }
 
-// ---- argmax over the last dim (greedy decode: softmax -> argmax == argmax of logits; first max wins like torch) ----
+// ---- argmax over the last dim (greedy decode: softmax -> argmax == argmax of logits) ----
+// torch.argmax order: NaN above every number, first index wins among equal keys (NaN ties included), so the result is always in [0, cols)
+__device__ __forceinline__ bool argmax_before(float v, int i, float best, int bi) {
+    const bool vn = v != v, bn = best != best;
+    if (vn != bn) return vn;
+    if (vn || v == best) return i < bi;
+    return v > best;
+}
+
 __global__ void argmax_kernel(const float* __restrict__ x, int64_t* __restrict__ out, int rows, int cols, int ld) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (row >= rows) return;
-    float best = -INFINITY; int bi = 0x7fffffff;
+    float best = -INFINITY; int bi = 0x7fffffff;          // a lane without columns loses every comparison (index above any real one)
     for (int c = lane; c < cols; c += 64) {
         const float v = x[(int64_t)row * ld + c];
-        if (v > best || (v == best && c < bi)) { best = v; bi = c; }
+        if (argmax_before(v, c, best, bi)) { best = v; bi = c; }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
-        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+        if (argmax_before(ov, oi, best, bi)) { best = ov; bi = oi; }
     }
     if (lane == 0) out[row] = bi;
 }
@@ -395,12 +405,14 @@ extern "C" int p3_patchify(const float* img, void* out, int B, int Cin, int H, i
     hipStream_t s = (hipStream_t)stream;
     const int64_t total = (int64_t)B * Cin * H * W;
     if (Cin * P * P <= 1024 && (int64_t)B * (H / P) * (W / P) < (1ll << 31)) {
+        if (p3_tracing()) p3_note_kernel(dtype_out == P3_BF16 ? "patchify_rows_kernel<bf16>" : "patchify_rows_kernel<float>");
         const dim3 gr((unsigned)(B * (H / P) * (W / P))), bl((unsigned)((Cin * P * P + 63) / 64 * 64));
         DISPATCH_T(dtype_out, hipLaunchKernelGGL((patchify_rows_kernel<bf16_t>), gr, bl, 0, s, img, (bf16_t*)out, Cin, H, W, P),
                    hipLaunchKernelGGL((patchify_rows_kernel<float>), gr, bl, 0, s, img, (float*)out, Cin, H, W, P), "p3_patchify");
         P3_LAUNCH_CHECK();
         return P3_OK;
     }
+    if (p3_tracing()) p3_note_kernel(dtype_out == P3_BF16 ? "patchify_kernel<bf16>" : "patchify_kernel<float>");
     DISPATCH_T(dtype_out, hipLaunchKernelGGL((patchify_kernel<bf16_t>), dim3(grid_for(total)), dim3(256), 0, s, img, (bf16_t*)out, B, Cin, H, W, P),
                hipLaunchKernelGGL((patchify_kernel<float>), dim3(grid_for(total)), dim3(256), 0, s, img, (float*)out, B, Cin, H, W, P), "p3_patchify");
     P3_LAUNCH_CHECK();
@@ -413,16 +425,25 @@ extern "C" int p3_tokens_assemble(const void* src, int src_ld, int dtype_src, co
     hipStream_t s = (hipStream_t)stream;
     const int64_t total = (int64_t)B * (np + 1) * D;
     if (D % 4 == 0 && src_ld % 4 == 0 && ((uintptr_t)src % 16) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)pos % 16) == 0) {
+        if (p3_tracing()) p3_note_kernel(dtype_src == P3_BF16 ? "tokens_assemble_rows_kernel<bf16>" : "tokens_assemble_rows_kernel<float>");
         const dim3 gr((unsigned)(B * (np + 1)));
         DISPATCH_T(dtype_src, hipLaunchKernelGGL((tokens_assemble_rows_kernel<bf16_t>), gr, dim3(128), 0, s, (const bf16_t*)src, src_ld, scale, shift, cls, pos, x, np, D),
                    hipLaunchKernelGGL((tokens_assemble_rows_kernel<float>), gr, dim3(128), 0, s, (const float*)src, src_ld, scale, shift, cls, pos, x, np, D), "p3_tokens_assemble");
         P3_LAUNCH_CHECK();
         return P3_OK;
     }
+    if (p3_tracing()) p3_note_kernel(dtype_src == P3_BF16 ? "tokens_assemble_kernel<bf16>" : "tokens_assemble_kernel<float>");
     DISPATCH_T(dtype_src, hipLaunchKernelGGL((tokens_assemble_kernel<bf16_t>), dim3(grid_for(total)), dim3(256), 0, s, (const bf16_t*)src, src_ld, scale, shift, cls, pos, x, B, np, D),
                hipLaunchKernelGGL((tokens_assemble_kernel<float>), dim3(grid_for(total)), dim3(256), 0, s, (const float*)src, src_ld, scale, shift, cls, pos, x, B, np, D), "p3_tokens_assemble");
     P3_LAUNCH_CHECK();
     return P3_OK;
+}
+
+static const char* pool_pos_name(bool rows, int dtype_in, int dtype_out) {
+    static const char* const names[2][4] = {{"pool_pos_kernel<float, float>", "pool_pos_kernel<float, bf16>", "pool_pos_kernel<bf16, float>", "pool_pos_kernel<bf16, bf16>"},
+                                            {"pool_pos_rows_kernel<float, float>", "pool_pos_rows_kernel<float, bf16>", "pool_pos_rows_kernel<bf16, float>",
+                                             "pool_pos_rows_kernel<bf16, bf16>"}};
+    return names[rows ? 1 : 0][(dtype_in == P3_BF16 ? 2 : 0) + (dtype_out == P3_BF16 ? 1 : 0)];
 }
 
 extern "C" int p3_pool_pos(const void* y, int dtype_in, const float* pos, void* out, void* out_nopos, int dtype_out, int B, int np, int Din,
@@ -435,6 +456,7 @@ extern "C" int p3_pool_pos(const void* y, int dtype_in, const float* pos, void* 
         const int rpb = (int)p3_ceil_div(rows, 2048) < 8 ? 8 : (int)p3_ceil_div(rows, 2048);
         dim3 g2((unsigned)p3_ceil_div(rows, rpb)), b2((unsigned)((Dout + 63) / 64 * 64));
 #define P3_POOL_ROWS(TI, TO) hipLaunchKernelGGL((pool_pos_rows_kernel<TI, TO>), g2, b2, 0, s, (const TI*)y, pos, (TO*)out, (TO*)out_nopos, rows, np, Din, Dout, rpb)
+        if (p3_tracing()) p3_note_kernel(pool_pos_name(true, dtype_in, dtype_out));
         if (dtype_in == P3_F32 && dtype_out == P3_F32) P3_POOL_ROWS(float, float);
         else if (dtype_in == P3_F32 && dtype_out == P3_BF16) P3_POOL_ROWS(float, bf16_t);
         else if (dtype_in == P3_BF16 && dtype_out == P3_BF16) P3_POOL_ROWS(bf16_t, bf16_t);
@@ -445,6 +467,7 @@ extern "C" int p3_pool_pos(const void* y, int dtype_in, const float* pos, void* 
         return P3_OK;
     }
     dim3 g(grid_for(total)), b(256);
+    if (p3_tracing()) p3_note_kernel(pool_pos_name(false, dtype_in, dtype_out));
     if (dtype_in == P3_F32 && dtype_out == P3_F32) hipLaunchKernelGGL((pool_pos_kernel<float, float>), g, b, 0, s, (const float*)y, pos, (float*)out, (float*)out_nopos, B, np, Din, Dout);
     else if (dtype_in == P3_F32 && dtype_out == P3_BF16) hipLaunchKernelGGL((pool_pos_kernel<float, bf16_t>), g, b, 0, s, (const float*)y, pos, (bf16_t*)out, (bf16_t*)out_nopos, B, np, Din, Dout);
     else if (dtype_in == P3_BF16 && dtype_out == P3_BF16) hipLaunchKernelGGL((pool_pos_kernel<bf16_t, bf16_t>), g, b, 0, s, (const bf16_t*)y, pos, (bf16_t*)out, (bf16_t*)out_nopos, B, np, Din, Dout);
@@ -504,10 +527,12 @@ extern "C" int p3_score_out(const void* H3, int dtype, const float* scale, const
     hipStream_t s = (hipStream_t)stream;
     const int64_t total = (int64_t)B * N * N;
     if (dtype == P3_BF16 && C == 64 && ((uintptr_t)H3 % 16) == 0) {
+        if (p3_tracing()) p3_note_kernel("score_out64_kernel");
         hipLaunchKernelGGL(score_out64_kernel, dim3(grid_for(total * 8)), dim3(256), 0, s, (const bf16_t*)H3, scale, shift, w4, b4, out, B, N, transpose_accumulate);
         P3_LAUNCH_CHECK();
         return P3_OK;
     }
+    if (p3_tracing()) p3_note_kernel(dtype == P3_BF16 ? "score_out_kernel<bf16>" : "score_out_kernel<float>");
     DISPATCH_T(dtype, hipLaunchKernelGGL((score_out_kernel<bf16_t>), dim3(grid_for(total)), dim3(256), 0, s, (const bf16_t*)H3, scale, shift, w4, b4, out, B, N, C, transpose_accumulate),
                hipLaunchKernelGGL((score_out_kernel<float>), dim3(grid_for(total)), dim3(256), 0, s, (const float*)H3, scale, shift, w4, b4, out, B, N, C, transpose_accumulate), "p3_score_out");
     P3_LAUNCH_CHECK();
@@ -522,8 +547,8 @@ extern "C" int p3_argmax(const float* x, int64_t* out, int rows, int cols, int l
 }
 
 extern "C" int p3_cast(const void* a, int dtype_a, void* b, int dtype_b, int64_t n, void* stream) {
-    P3_CHECK(a && b && n >= 0, P3_EINVAL, "p3_cast: bad arguments");
-    if (n == 0) return P3_OK;
+    if (n == 0) return P3_OK;                                   // an empty tensor may have no storage (NULL data pointer)
+    P3_CHECK(a && b && n > 0, P3_EINVAL, "p3_cast: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     dim3 g(grid_for(n)), blk(256);
     if (dtype_a == P3_F32 && dtype_b == P3_BF16) hipLaunchKernelGGL((cast_kernel<float, bf16_t>), g, blk, 0, s, (const float*)a, (bf16_t*)b, n);

@@ -142,7 +142,8 @@ template <typename T, int NOUT>
 __global__ __launch_bounds__(256) void head1x1_bwd_kernel(const T* __restrict__ H, const float* __restrict__ sc, const float* __restrict__ sh,
                                                           const float* __restrict__ mean, const float* __restrict__ Wt,
                                                           const float* __restrict__ out_nchw, const float* __restrict__ dout_nchw, int act,
-                                                          float post_mul, T* __restrict__ dHd, float* __restrict__ acc, int64_t R, int64_t HW) {
+                                                          float post_mul, T* __restrict__ dHd, float* __restrict__ acc, float* __restrict__ slab,
+                                                          int64_t R, int64_t HW) {
     const int lane = threadIdx.x & 63, c0 = lane * 4, wv = threadIdx.x >> 6;
     float s[4], h[4], mu[4], w[NOUT][4];
 #pragma unroll
@@ -194,7 +195,11 @@ __global__ __launch_bounds__(256) void head1x1_bwd_kernel(const T* __restrict__ 
     }
     __syncthreads();
     constexpr int NV = 512 + NOUT * 256 + NOUT;
-    for (int i = threadIdx.x; i < NV; i += 256) atomicAdd(acc + i, (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]));
+    for (int i = threadIdx.x; i < NV; i += 256) {
+        const float v = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
+        if (slab) slab[(int64_t)blockIdx.x * NV + i] = v;        // deterministic mode: per-workgroup partials, reduced in workgroup order
+        else atomicAdd(acc + i, v);
+    }
 }
 
 // Backward through a BatchNorm + ReLU that sits in front of a consumer (C = 256): dA = gradient w.r.t. relu(bn(H)).
@@ -202,7 +207,7 @@ __global__ __launch_bounds__(256) void head1x1_bwd_kernel(const T* __restrict__ 
 template <typename T>
 __global__ __launch_bounds__(256) void affine_relu_bwd256_kernel(const T* __restrict__ dA, const T* __restrict__ H, int ldh, const float* __restrict__ sc,
                                                                  const float* __restrict__ sh, const float* __restrict__ mean, T* __restrict__ dHd,
-                                                                 float* __restrict__ acc, int64_t R) {
+                                                                 float* __restrict__ acc, float* __restrict__ slab, int64_t R) {
     const int lane = threadIdx.x & 63, c0 = lane * 4, wv = threadIdx.x >> 6;
     float s[4], h[4], mu[4];
 #pragma unroll
@@ -225,7 +230,11 @@ __global__ __launch_bounds__(256) void affine_relu_bwd256_kernel(const T* __rest
 #pragma unroll
     for (int k = 0; k < 4; ++k) { red[wv][c0 + k] = a_sc[k]; red[wv][256 + c0 + k] = a_sh[k]; }
     __syncthreads();
-    for (int i = threadIdx.x; i < 512; i += 256) atomicAdd(acc + i, (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]));
+    for (int i = threadIdx.x; i < 512; i += 256) {
+        const float v = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
+        if (slab) slab[(int64_t)blockIdx.x * 512 + i] = v;       // deterministic mode: per-workgroup partials, reduced in workgroup order
+        else atomicAdd(acc + i, v);
+    }
 }
 
 // [R = B*H*W, ld_src] (first C channels) -> interior of the zero-bordered [B, H+2, W+2, Cp] image the shifted-row weight-gradient
@@ -290,6 +299,14 @@ __global__ __launch_bounds__(256) void pad_nhwc_vec_kernel(const bf16_t* __restr
 
 // Adjoint of upsample_bilinear, separable: pass X folds the W output columns onto the w source columns, pass Y the H rows onto h.
 // Exactly the forward's index / weight rule, gathered per source cell (deterministic, no atomics).
+// Output o reaches source cells floor(f) and floor(f) + 1, f = (o + 0.5) * srcn / outn - 0.5: cell `cell` is reached only by the outputs with
+// f in [cell - 1, cell + 1).  The window below is that range widened by one output on each side against the rounding of f; any ratio
+// outn / srcn >= 1 (integer or not), bilinear_weight decides the exact weights.
+__device__ __forceinline__ void bilinear_window(int cell, int srcn, int outn, int& lo, int& hi) {
+    const float r = (float)outn / (float)srcn;
+    lo = max(0, (int)floorf(((float)cell - 0.5f) * r - 0.5f) - 1);
+    hi = min(outn - 1, (int)ceilf(((float)cell + 1.5f) * r - 0.5f) + 1);
+}
 __device__ __forceinline__ float bilinear_weight(int o, int srcn, int outn, int cell) {
     const float f = fmaxf(((float)o + 0.5f) * ((float)srcn / (float)outn) - 0.5f, 0.f);
     const int i0 = (int)f, i1 = i0 + (i0 < srcn - 1 ? 1 : 0);
@@ -302,14 +319,14 @@ __global__ void upsample_bwd_x_kernel(const T* __restrict__ dUp, float* __restri
     // tmp[b, Y, xs, c] = sum_X wx(X, xs) * dUp[b, Y, X, c]
     const int Cq = C / 4;
     const int64_t total = (int64_t)B * H * w * Cq;
-    const int span = (W + w - 1) / w;               // output columns per source cell
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int c = (int)(i % Cq) * 4;
         const int64_t t = i / Cq;
         const int xs = (int)(t % w);
         const int64_t row = t / w;                  // b*H + Y
         float a[4] = {0.f, 0.f, 0.f, 0.f};
-        const int lo = max(0, xs * span - span), hi = min(W - 1, xs * span + 2 * span - 1);
+        int lo, hi;
+        bilinear_window(xs, w, W, lo, hi);
         for (int X = lo; X <= hi; ++X) {
             const float wt = bilinear_weight(X, w, W, xs);
             if (wt != 0.f) {
@@ -329,14 +346,14 @@ __global__ void upsample_bwd_y_kernel(const float* __restrict__ tmp, T* __restri
     // dtok[b, tok_off + ys*w + xs, c] = sum_Y wy(Y, ys) * tmp[b, Y, xs, c]
     const int Cq = C / 4;
     const int64_t total = (int64_t)B * h * w * Cq;
-    const int span = (H + h - 1) / h;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int c = (int)(i % Cq) * 4;
         const int64_t t = i / Cq;
         const int xs = (int)(t % w), ys = (int)((t / w) % h);
         const int64_t b = t / ((int64_t)w * h);
         float a[4] = {0.f, 0.f, 0.f, 0.f};
-        const int lo = max(0, ys * span - span), hi = min(H - 1, ys * span + 2 * span - 1);
+        int lo, hi;
+        bilinear_window(ys, h, H, lo, hi);
         for (int Y = lo; Y <= hi; ++Y) {
             const float wt = bilinear_weight(Y, h, H, ys);
             if (wt != 0.f) {
@@ -399,11 +416,14 @@ extern "C" int p3_head1x1_bwd(const void* H, int dtype, const float* scale, cons
     hipStream_t s = (hipStream_t)stream;
     int64_t gr = (R + 3) / 4; if (gr > 2048) gr = 2048;
     dim3 g((int)gr), b(256);
-#define HB(T, NO) hipLaunchKernelGGL((head1x1_bwd_kernel<T, NO>), g, b, 0, s, (const T*)H, scale, shift, mean, W, out_nchw, dout_nchw, act, post_mul, (T*)dHd, acc, R, HW)
+    const int nv = 512 + n_out * 256 + n_out;
+    float* slab = p3_det_scratch(gr * nv, dtype);
+#define HB(T, NO) hipLaunchKernelGGL((head1x1_bwd_kernel<T, NO>), g, b, 0, s, (const T*)H, scale, shift, mean, W, out_nchw, dout_nchw, act, post_mul, (T*)dHd, acc, slab, R, HW)
     if (dtype == P3_BF16) { if (n_out == 1) HB(bf16_t, 1); else HB(bf16_t, 4); }
     else { if (n_out == 1) HB(float, 1); else HB(float, 4); }
 #undef HB
     P3_LAUNCH_CHECK();
+    if (slab) return p3_det_reduce(slab, (int)gr, nv, acc, nv, 1, s);
     return P3_OK;
 }
 
@@ -413,9 +433,11 @@ extern "C" int p3_affine_relu_bwd256(const void* dA, const void* H, int ldh, int
     P3_CHECK(dtype == P3_BF16 || dtype == P3_F32, P3_EUNSUP, "p3_affine_relu_bwd256: dtype");
     hipStream_t s = (hipStream_t)stream;
     int64_t gr = (R + 3) / 4; if (gr > 2048) gr = 2048;
-    if (dtype == P3_BF16) hipLaunchKernelGGL((affine_relu_bwd256_kernel<bf16_t>), dim3((int)gr), dim3(256), 0, s, (const bf16_t*)dA, (const bf16_t*)H, ldh, scale, shift, mean, (bf16_t*)dHd, acc, R);
-    else hipLaunchKernelGGL((affine_relu_bwd256_kernel<float>), dim3((int)gr), dim3(256), 0, s, (const float*)dA, (const float*)H, ldh, scale, shift, mean, (float*)dHd, acc, R);
+    float* slab = p3_det_scratch(gr * 512, dtype);
+    if (dtype == P3_BF16) hipLaunchKernelGGL((affine_relu_bwd256_kernel<bf16_t>), dim3((int)gr), dim3(256), 0, s, (const bf16_t*)dA, (const bf16_t*)H, ldh, scale, shift, mean, (bf16_t*)dHd, acc, slab, R);
+    else hipLaunchKernelGGL((affine_relu_bwd256_kernel<float>), dim3((int)gr), dim3(256), 0, s, (const float*)dA, (const float*)H, ldh, scale, shift, mean, (float*)dHd, acc, slab, R);
     P3_LAUNCH_CHECK();
+    if (slab) return p3_det_reduce(slab, (int)gr, 512, acc, 512, 1, s);
     return P3_OK;
 }
 
@@ -429,6 +451,7 @@ extern "C" int p3_pad_nhwc(const void* src, int ld_src, int dtype, const float* 
         (!scale || (((uintptr_t)scale % 16) == 0 && ((uintptr_t)shift % 16) == 0))) {
         const int64_t tot = (int64_t)B * (H + 2) * (W + 2) * (Cp / 8);
         int64_t g = (tot + 255) / 256; if (g > 65536) g = 65536;
+        if (p3_tracing()) p3_note_kernel("pad_nhwc_vec_kernel");
         hipLaunchKernelGGL(pad_nhwc_vec_kernel, dim3((int)g), dim3(256), 0, s, (const bf16_t*)src, ld_src, scale, shift, c_aff, C, Cp, (bf16_t*)dst, B, H, W);
         P3_LAUNCH_CHECK();
         return P3_OK;
@@ -438,6 +461,7 @@ extern "C" int p3_pad_nhwc(const void* src, int ld_src, int dtype, const float* 
     if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
     const int64_t total = (int64_t)B * H * W * (Cp / 4);
     int64_t gr = (total + 255) / 256; if (gr > 16384) gr = 16384;
+    if (p3_tracing()) p3_note_kernel(dtype == P3_BF16 ? "pad_nhwc_kernel<bf16>" : "pad_nhwc_kernel<float>");
     if (dtype == P3_BF16) hipLaunchKernelGGL((pad_nhwc_kernel<bf16_t>), dim3((int)gr), dim3(256), 0, s, (const bf16_t*)src, ld_src, scale, shift, c_aff, C, Cp, (bf16_t*)dst, B, H, W);
     else hipLaunchKernelGGL((pad_nhwc_kernel<float>), dim3((int)gr), dim3(256), 0, s, (const float*)src, ld_src, scale, shift, c_aff, C, Cp, (float*)dst, B, H, W);
     P3_LAUNCH_CHECK();
