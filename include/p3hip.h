@@ -362,6 +362,23 @@ int p3_pillar_stem_bwd_phased(const void* dcanvas, int dcanvas_ld, const float* 
  * ------------------------------------------------------------------------------------------ */
 /* im2col of timm PatchEmbed.proj (Conv2d k=P, s=P): img NCHW f32 -> rows [B*(H/P)*(W/P), Cin*P*P], k = c*P*P + py*P + px */
 int p3_patchify(const float* img, void* out, int B, int Cin, int H, int W, int P, int dtype_out, void* stream);
+/* the same rows with a leading dimension ldk >= Cin*P*P (<= 1024): columns [Cin*P*P, ldk) are written as zeros, so that a K that no GEMM
+ * kernel takes (patch 14: K = 588) runs as K = ldk against a weight zero-padded in the same way */
+int p3_patchify_ld(const float* img, void* out, int B, int Cin, int H, int W, int P, int ldk, int dtype_out, void* stream);
+/* DINOv2 (vit_dinov2.py: the hub model's interpolate_pos_encoding): bicubic (A = -0.75, align_corners = False, no antialias, clamped border)
+ * resampling of the trained position table [1 + n_in*n_in, D] to [1 + n_out*n_out, D]; row 0 (CLS) passes through.  The operator is separable
+ * and linear: out[y, x, :] = sum_i sum_j wy[y, i] wx[x, j] table[i, j, :] with host-built tap tables wy, wx [n_out, n_in] (device fp32).
+ * _bwd is the transposed gather (one workgroup per source cell, fixed order, no atomics): dtable[i, j, :] = sum_y sum_x wy[y, i] wx[x, j] dout[y, x, :].
+ * D % 4 == 0, D <= 4096, 16-byte aligned tensors. */
+int p3_posembed_resample(const float* table, const float* wy, const float* wx, float* out, int n_in, int n_out, int D, void* stream);
+int p3_posembed_resample_bwd(const float* dout, const float* wy, const float* wx, float* dtable, int n_in, int n_out, int D, void* stream);
+/* DINOv2 LayerScale folded into the branch's last Linear: res + gamma * (W a + b) = res + (diag(gamma) W) a + gamma * b.
+ *   fold:  Wf[n, :] = gamma[n] W[n, :],  bf[n] = gamma[n] b[n]                      (W [N, K] fp32, K % 4 == 0; b / bf may be NULL)
+ *   bwd:   dW = gamma[:, None] dWf,  db = gamma dbf,  dgamma[n] = sum_k dWf[n, k] W[n, k] + dbf[n] b[n]   (one wave per row, fixed order;
+ *          dgamma never divides by gamma) */
+int p3_layerscale_fold(const float* gamma, const float* W, const float* b, float* Wf, float* bf, int N, int K, void* stream);
+int p3_layerscale_fold_bwd(const float* gamma, const float* W, const float* b, const float* dWf, const float* dbf, float* dW, float* db,
+                           float* dgamma, int N, int K, void* stream);
 /* timm VisionTransformer._pos_embed (+ fusion BN2d+ReLU, early_fusion_vit.py:75-79,123 when scale/shift given):
  *   x[b,0,:] = cls + pos[0];  x[b,1+p,:] = f(src[b,p,:]) + pos[1+p];  x is the fp32 residual stream [B, np+1, D] */
 int p3_tokens_assemble(const void* src, int src_ld, int dtype_src, const float* scale, const float* shift, const float* cls,

@@ -10,6 +10,8 @@ keys and shapes, so a published `.pth` loads as it is; this module mirrors the r
                                                   files and bare state dicts; return_extras=True also hands back the other entries
   normalize_checkpoint(obj)                       that key normalisation alone
   compare(model, checkpoint_state_dict)           -> Report(matched, missing, unused, shape_mismatch) without touching the model
+  a bare DINOv2 backbone file (keys without the "encoder.vit." prefix) is accepted by all of them for a vit_dinov2 model's encoder (strict=False:
+  it holds no decoder)
   export_state_dict(model)                        reference-keyed CPU fp32 state dict (for torch.save), whatever the compute dtype
 """
 import logging
@@ -20,8 +22,26 @@ import torch
 Report = namedtuple("Report", "matched missing unused shape_mismatch")
 
 
+def _place_bare_backbone(model_keys, ckpt):
+    """A bare DINOv2 backbone file (`dinov2_vits14_pretrain.pth`: cls_token, pos_embed, mask_token, patch_embed.*, blocks.*, norm.* with no prefix)
+    offered to a model whose encoder is ViTDINOv2: the keys get the prefix of the model's `...vit.` subtree, and norm.* also feeds the wrapper's second
+    registration of the same LayerNorm (`encoder.norm.*`).  Anything else passes through unchanged."""
+    if not ("cls_token" in ckpt and "pos_embed" in ckpt and "patch_embed.proj.weight" in ckpt):
+        return ckpt
+    anchor = next((k for k in model_keys if k.endswith("vit.mask_token")), None)
+    if anchor is None:
+        return ckpt
+    pre = anchor[:-len("mask_token")]                     # "encoder.vit." (or "vit." for the bare encoder, "module.encoder.vit." under DDP)
+    out = OrderedDict()
+    for k, v in ckpt.items():
+        out[pre + k] = v
+        if k.startswith("norm.") and pre[:-len("vit.")] + k in model_keys:
+            out[pre[:-len("vit.")] + k] = v
+    return out
+
+
 def _match(model_keys, ckpt):
-    ckpt = OrderedDict(ckpt)
+    ckpt = _place_bare_backbone(model_keys, OrderedDict(ckpt))
     for k in list(ckpt.keys()):                      # the reference adds the renamed twin and keeps the original (shared_utils.py:73-77)
         ckpt[k.replace("encoder.model.", "encoder.vit.")] = ckpt[k]
     mapping = OrderedDict()                          # model key -> checkpoint key

@@ -1,7 +1,7 @@
 """Plain attribute-dict config carrying exactly the keys the reference models read (SURVEY §5, config/**/*.yaml).
 
 Hydra / OmegaConf are not required: `make_config()` restates the shipped defaults of
-config/encoder/{vit,pointpillars_vit,early_fusion_vit,early_fusion_vit_cnn}.yaml + config/model/{pix2poly,ffl}.yaml.
+config/encoder/{vit,vit_dinov2,pointpillars_vit,early_fusion_vit,early_fusion_vit_cnn}.yaml + config/model/{pix2poly,ffl}.yaml.
 An OmegaConf DictConfig produced by the reference's own scripts works as well (same attribute access).
 """
 
@@ -28,6 +28,7 @@ class AttrDict(dict):
 
 _ENCODERS = {
     "vit": dict(use_images=True, use_lidar=False),
+    "vit_dinov2": dict(use_images=True, use_lidar=False),
     "pointpillars_vit": dict(use_images=False, use_lidar=True),
     "early_fusion_vit": dict(use_images=True, use_lidar=True),
     "vit_cnn": dict(use_images=True, use_lidar=False),
@@ -36,7 +37,7 @@ _ENCODERS = {
 }
 
 
-def make_config(encoder="early_fusion_vit", model="pix2poly", *, in_size=224, patch_size=8, patch_feature_dim=384,
+def make_config(encoder="early_fusion_vit", model="pix2poly", *, in_size=224, patch_size=None, patch_feature_dim=384,
                 vit_depth=12, vit_heads=6, vit_mlp=None, max_num_vertices=192, out_feature_dim=256,
                 max_num_points_per_voxel=64, sinkhorn_iterations=100, device="cuda", multi_gpu=False,
                 lidar_dropout=None, precision="bf16", batch_size=16):
@@ -44,6 +45,9 @@ def make_config(encoder="early_fusion_vit", model="pix2poly", *, in_size=224, pa
     the bf16 MFMA: 2^-17 per product - the north star's 1e-3 at a multiple of the exact mode's throughput)."""
     if encoder not in _ENCODERS:
         raise NotImplementedError(f"Encoder {encoder} not implemented")
+    dino = encoder == "vit_dinov2"
+    if patch_size is None:
+        patch_size = 14 if dino else 8           # config/encoder/vit_dinov2.yaml: patch 14 -> a 16 x 16 grid, num_patches 256
     g = in_size // patch_size
     enc = dict(
         name=encoder, **_ENCODERS[encoder], in_size=in_size, in_height=in_size, in_width=in_size,
@@ -57,6 +61,9 @@ def make_config(encoder="early_fusion_vit", model="pix2poly", *, in_size=224, pa
         patch_feature_dim=patch_feature_dim, num_patches=g * g, out_feature_dim=out_feature_dim,
         image_mean=[0.0, 0.0, 0.0], image_std=[1.0, 1.0, 1.0], image_max_pixel_value=255.0,
     )
+    if dino:
+        # "DINO v2 normalization" of vit_dinov2.yaml (its 0.228 is kept as written); interpolate_offset: vision_transformer.DinoVisionTransformer
+        enc.update(image_mean=[0.485, 0.456, 0.406], image_std=[0.228, 0.224, 0.225], interpolate_offset=0.1)
     mdl = dict(
         name=model, decoder=dict(in_feature_dim=out_feature_dim, in_feature_size=g),
         tokenizer=dict(num_bins=in_size, shuffle_tokens=False, max_num_vertices=max_num_vertices, max_len=None,

@@ -664,6 +664,87 @@ def patchify(img, P, dtype):
     return out
 
 
+def patchify_ld(img, P, dtype, ldk):
+    """patchify with rows of leading dimension ldk >= Cin*P*P; the pad columns are zeros"""
+    _dev(img)
+    B, Cin, H, W = img.shape
+    out = torch.empty((B * (H // P) * (W // P), ldk), dtype=dtype, device=img.device)
+    check(lib().p3_patchify_ld(ptr(img), ptr(out), c_int(B), c_int(Cin), c_int(H), c_int(W), c_int(P), c_int(ldk), c_int(dt(out)), stream()),
+          "p3_patchify_ld")
+    return out
+
+
+def bicubic_taps(n_in, n_out, scale=None):
+    """[n_out, n_in] float64 tap table of torch's 1-D bicubic resampling (A = -0.75, align_corners=False, no antialias, border indices clamped):
+    out[o] = sum_i taps[o, i] * in[i].  `scale`: the scale_factor handed to F.interpolate (source coordinate = (o + 0.5) / scale - 0.5);
+    None: the `size=` form (source coordinate = (o + 0.5) * n_in / n_out - 0.5).  Host arithmetic only."""
+    A = -0.75
+    ratio = (1.0 / scale) if scale is not None else n_in / n_out
+    taps = torch.zeros((n_out, n_in), dtype=torch.float64)
+    for o in range(n_out):
+        src = ratio * (o + 0.5) - 0.5
+        i0 = math.floor(src)
+        t = src - i0
+        coef = (((A * (t + 1) - 5 * A) * (t + 1) + 8 * A) * (t + 1) - 4 * A,
+                ((A + 2) * t - (A + 3)) * t * t + 1,
+                ((A + 2) * (1 - t) - (A + 3)) * (1 - t) * (1 - t) + 1,
+                ((A * (2 - t) - 5 * A) * (2 - t) + 8 * A) * (2 - t) - 4 * A)
+        for k, c in enumerate(coef):
+            taps[o, min(max(i0 - 1 + k, 0), n_in - 1)] += c
+    return taps
+
+
+def posembed_resample(table, wy, wx, n_in, n_out):
+    """table [1 + n_in^2, D] fp32 -> [1 + n_out^2, D]; wy / wx: device fp32 [n_out, n_in] tap tables (bicubic_taps)"""
+    _dev(table)
+    D = table.shape[-1]
+    if table.dtype != torch.float32 or table.shape[0] != 1 + n_in * n_in or tuple(wy.shape) != (n_out, n_in) or tuple(wx.shape) != (n_out, n_in):
+        raise P3Error("posembed_resample: fp32 table [1 + n_in^2, D] and tap tables [n_out, n_in] expected")
+    out = torch.empty((1 + n_out * n_out, D), dtype=torch.float32, device=table.device)
+    check(lib().p3_posembed_resample(ptr(table.contiguous()), ptr(wy), ptr(wx), ptr(out), c_int(n_in), c_int(n_out), c_int(D), stream()),
+          "p3_posembed_resample")
+    return out
+
+
+def posembed_resample_bwd(dout, wy, wx, n_in, n_out):
+    _dev(dout)
+    D = dout.shape[-1]
+    if dout.dtype != torch.float32 or dout.shape[0] != 1 + n_out * n_out or tuple(wy.shape) != (n_out, n_in) or tuple(wx.shape) != (n_out, n_in):
+        raise P3Error("posembed_resample_bwd: fp32 gradient [1 + n_out^2, D] and tap tables [n_out, n_in] expected")
+    dtable = torch.empty((1 + n_in * n_in, D), dtype=torch.float32, device=dout.device)
+    check(lib().p3_posembed_resample_bwd(ptr(dout.contiguous()), ptr(wy), ptr(wx), ptr(dtable), c_int(n_in), c_int(n_out), c_int(D), stream()),
+          "p3_posembed_resample_bwd")
+    return dtable
+
+
+def layerscale_fold(gamma, W, b=None):
+    """-> (gamma[:, None] * W, gamma * b) fp32"""
+    _dev(W)
+    N, K = W.shape
+    if W.dtype != torch.float32 or gamma.dtype != torch.float32 or gamma.numel() != N or (b is not None and b.numel() != N):
+        raise P3Error("layerscale_fold: fp32 W [N, K], gamma [N] (and b [N]) expected")
+    Wf = torch.empty((N, K), dtype=torch.float32, device=W.device)
+    bf = torch.empty(N, dtype=torch.float32, device=W.device) if b is not None else None
+    check(lib().p3_layerscale_fold(ptr(gamma.contiguous()), ptr(W.contiguous()), ptr(b), ptr(Wf), ptr(bf), c_int(N), c_int(K), stream()),
+          "p3_layerscale_fold")
+    return Wf, bf
+
+
+def layerscale_fold_bwd(gamma, W, b, dWf, dbf):
+    """-> (dW, db, dgamma) from the gradients of the folded weight / bias"""
+    _dev(W)
+    N, K = W.shape
+    if dWf.dtype != torch.float32 or tuple(dWf.shape) != (N, K) or (b is not None and (dbf is None or dbf.dtype != torch.float32 or dbf.numel() != N)):
+        raise P3Error("layerscale_fold_bwd: fp32 dW' [N, K] (and db' [N]) expected")
+    dW = torch.empty((N, K), dtype=torch.float32, device=W.device)
+    db = torch.empty(N, dtype=torch.float32, device=W.device) if b is not None else None
+    dgamma = torch.empty(N, dtype=torch.float32, device=W.device)
+    check(lib().p3_layerscale_fold_bwd(ptr(gamma.contiguous()), ptr(W.contiguous()), ptr(b), ptr(dWf.contiguous()),
+                                       ptr(dbf.contiguous() if dbf is not None else None), ptr(dW), ptr(db), ptr(dgamma), c_int(N), c_int(K), stream()),
+          "p3_layerscale_fold_bwd")
+    return dW, db, dgamma
+
+
 def tokens_assemble(src, cls, pos, B, np_, D, scale=None, shift=None, src_ld=None):
     x = torch.empty((B, np_ + 1, D), dtype=torch.float32, device=src.device)
     check(lib().p3_tokens_assemble(ptr(src), c_int(src.stride(-2) if src_ld is None else src_ld), c_int(dt(src)), ptr(scale),

@@ -389,6 +389,16 @@ def unregister(params):
         del _shadow_cache[k]
 
 
+def forget_derived(ident):
+    """drop the cached copies (compute-dtype shadow, transposes, planes) derived from the NON-parameter tensor with this id(): a weight that is
+    itself computed per forward (the LayerScale fold) would otherwise leave one set of copies behind per step - the caches hold their source alive"""
+    for cache in (_shadow_cache, _planes_cache):
+        for k in [k for k, ent in cache.items() if k[0] == ident]:
+            src = cache[k].p if cache is _shadow_cache else cache[k][0]
+            if not isinstance(src, torch.nn.Parameter):
+                del cache[k]
+
+
 def reset_process_state():
     """Forget every process-wide registration: optimizer arena views and the copies derived from them, the direct-gradient switch, the
     reducer's report channel, pending gradient twins, SyncBatchNorm.  For a process that builds one model after another (tests, sweeps):
@@ -721,7 +731,7 @@ class _Linear(torch.autograd.Function):
                 dx = hip.gemm(dpre, wt, out_dtype=cd, residual=res_g, w_planes=wtp).view(ctx.xshape)
             if ctx.gout_x is not None:
                 ctx.gout_x.g, dx = dx, None
-        direct = DIRECT_GRAD[0] and weight.grad is not None and dpre.shape[1] == n_true
+        direct = DIRECT_GRAD[0] and weight.is_leaf and weight.grad is not None and dpre.shape[1] == n_true    # a derived weight (LayerScale fold) has no arena slot
         bias_p = ctx.bias_param
         if direct:
             r0, r1 = rows if rows is not None else (0, weight.shape[0])
@@ -762,7 +772,7 @@ def linear(x, weight, bias=None, *, act=hip.ACT_NONE, residual=None, out_dtype=N
 def _weight_grads(dpre, x2, weight, bias, need_w, need_b):
     """(dW, db) of y = x W^T + b from dpre = dL/dy; in DIRECT_GRAD mode both are accumulated into the flat arena (returns None)."""
     dw = db = None
-    if DIRECT_GRAD[0] and weight.grad is not None:
+    if DIRECT_GRAD[0] and weight.is_leaf and weight.grad is not None:
         fuse_b = bias is not None and need_b and bias.grad is not None and need_w
         if need_w:
             _tn_side(dpre, x2, out=weight.grad, colsum_out=bias.grad if fuse_b else None)

@@ -15,7 +15,7 @@ from torch.nn.parallel import DistributedDataParallel as DDP
 from . import hip, ops
 from .fusion_layers import EarlyFusionViT
 from .pointpillars import PointPillarsViT
-from .vision_transformer import ViT, is_split, model_precision
+from .vision_transformer import ViT, ViTDINOv2, is_split, model_precision
 
 
 # ------------------------------------------------------------------------------------------------ Tokenizer
@@ -564,6 +564,8 @@ class Pix2PolyModel(torch.nn.Module):
         elif enc.use_images:
             if enc.name == "vit":
                 encoder = ViT(cfg, bottleneck=True, local_rank=local_rank)
+            elif enc.name == "vit_dinov2":
+                encoder = ViTDINOv2(cfg, bottleneck=True, local_rank=local_rank)
             else:
                 raise NotImplementedError(f"Encoder {enc.name} not implemented for Pix2PolyModel")
         elif enc.use_lidar:
