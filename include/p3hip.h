@@ -648,6 +648,48 @@ int64_t p3_ffl_loss_workspace_bytes(int B, int H, int W);
  * ------------------------------------------------------------------------------------------ */
 int p3_afm(const float* lines, const int32_t* shape_info, int B, int height, int width, float* afmap, int32_t* aflabel, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * HiSup inference after the heads (models/hisup/model_hisup.py:229-293 `EncoderDecoder.forward_val`).  Forward only; every output
+ * repeats bit for bit from run to run.  A logit map is given as base pointer + (batch, channel, pixel) strides in ELEMENTS, element
+ * (b, c, pix) = base[b*sb + c*sc + pix*sp]: NCHW fp32 is (C*H*W, H*W, 1), token-major fp32 rows [B*H*W, ld] are (H*W*ld, 1, ld).
+ * H * W <= 2^22.  workspace: p3_*_workspace_bytes(...) bytes of device scratch, contents irrelevant on entry.
+ *
+ * p3_hisup_junctions - model_hisup.py:251-253,266-268 + models/hisup/polygon.py:8-38 (softmax, max_pool2d NMS, two .item() counts, two
+ *   topk, four gathers per image) for the whole batch without host synchronisation.  jloc: 3 classes, joff: 2 channels.
+ *   p = softmax(jloc); per class a pixel is a candidate when p equals the maximum of its (border-clipped) 3x3 neighbourhood and p > 0.008;
+ *   plateaus survive whole.  The 300 candidates with the highest p are kept in descending order of p; EQUAL p: LOWER FLAT INDEX FIRST
+ *   (torch.topk leaves that order open).  Class 2 first, then class 1 (forward_val's argument order into get_pred_junctions):
+ *   counts[b] = (n_class2, n_class1), class-1 entries start at juncs[b, n_class2].  x = ((idx % W) + (sigmoid(joff0) - 0.5) + 0.5) * scale_x,
+ *   y likewise with idx / W, joff1, scale_y.  juncs fp32 [B,600,2], scores fp32 [B,600] (= p), index int32 [B,600] (flat source pixel),
+ *   counts int32 [B,2]; entries past the count are 0 (index: -1).
+ *
+ * p3_hisup_regions - model_hisup.py:254,265,271 (`remask.softmax(1)[:, 1:]`, skimage `label(mask > 0.5)`, the `regionprops` fields
+ *   forward_val and polygon.py:139-142 read).  remask: 2 classes.  mask fp32 [B,H,W] = class-1 probability; labels int32 [B,H,W]:
+ *   8-connected components of mask > 0.5 numbered 1..n in raster order of each component's first pixel (the numbering of
+ *   skimage.measure.label / scipy.ndimage.label), 0 = background; n_regions int32 [B]; for the first max_regions regions area int32
+ *   [B,max_regions], bbox int32 [B,max_regions,4] = (min_row, min_col, max_row + 1, max_col + 1), score fp32 [B,max_regions] = mean of
+ *   mask over the region (summed as 32.32 fixed point: order independent).  status int32 [B] = 1 where n_regions > max_regions: labels
+ *   and n_regions are still complete, the statistics hold the first max_regions regions, nothing is written past the arrays.
+ *
+ * p3_hisup_val_loss - model_hisup.py:241-245 with sigmoid_l1_loss (:27-37): NCHW fp32 contiguous logits jloc [B,3,H,W], joff / mask / afm /
+ *   remask [B,2,H,W]; targets as AnnotationEncoder (:66-120) makes them: t_jloc int64 [B,1,H,W] in {0,1,2}, t_joff fp32 [B,2,H,W], t_mask fp32
+ *   [B,1,H,W] in {0,1}, t_afm fp32 [B,2,H,W].  losses fp32 [5] = loss_jloc (3-class cross-entropy), loss_joff (mean of |sigmoid(joff) - 0.5 -
+ *   t_joff| * t / w, t = junction pixel, w = the image's share of junction pixels, 1 where there is none), loss_mask, loss_afm (L1),
+ *   loss_remask - un-weighted means.  Workgroup partials are summed in a fixed order in float64.
+ * ------------------------------------------------------------------------------------------ */
+int p3_hisup_junctions(const float* jloc, int64_t jloc_sb, int64_t jloc_sc, int64_t jloc_sp, const float* joff, int64_t joff_sb,
+                       int64_t joff_sc, int64_t joff_sp, int B, int H, int W, float scale_x, float scale_y, float* juncs, float* scores,
+                       int32_t* index, int32_t* counts, void* workspace, void* stream);
+int64_t p3_hisup_junctions_workspace_bytes(int B, int H, int W);
+int p3_hisup_regions(const float* remask, int64_t sb, int64_t sc, int64_t sp, int B, int H, int W, int max_regions, float* mask,
+                     int32_t* labels, int32_t* n_regions, int32_t* area, int32_t* bbox, float* score, int32_t* status, void* workspace,
+                     void* stream);
+int64_t p3_hisup_regions_workspace_bytes(int B, int H, int W, int max_regions);
+int p3_hisup_val_loss(const float* jloc, const float* joff, const float* mask, const float* afm, const float* remask, const int64_t* t_jloc,
+                      const float* t_joff, const float* t_mask, const float* t_afm, int B, int H, int W, float* losses, void* workspace,
+                      void* stream);
+int64_t p3_hisup_val_loss_workspace_bytes(int B, int H, int W);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,7 @@
 """Plain attribute-dict config carrying exactly the keys the reference models read (SURVEY §5, config/**/*.yaml).
 
 Hydra / OmegaConf are not required: `make_config()` restates the shipped defaults of
-config/encoder/{vit,vit_dinov2,pointpillars_vit,early_fusion_vit,early_fusion_vit_cnn}.yaml + config/model/{pix2poly,ffl}.yaml.
+config/encoder/{vit,vit_dinov2,pointpillars_vit,early_fusion_vit,early_fusion_vit_cnn}.yaml + config/model/{pix2poly,ffl,hisup}.yaml.
 An OmegaConf DictConfig produced by the reference's own scripts works as well (same attribute access).
 """
 
@@ -77,6 +77,13 @@ def make_config(encoder="early_fusion_vit", model="pix2poly", *, in_size=224, pa
                                           seg_interior_crossfield=[0, 0, 0.2], seg_edge_crossfield=[0, 0, 0.2], seg_edge_interior=[0, 0, 0.2])),
                   seg=dict(bce_coef=1.0, dice_coef=0.2, use_freq=False, use_dist=False, use_size=False, w0=50, sigma=10, type="bool")),
     )
+    if model == "hisup":
+        # config/model/hisup.yaml as shipped: the heads work on a full-resolution map (decoder.in_feature_size = in_size, which the *_vit_cnn
+        # encoders' out_feature_{size,height,width} interpolate from), its own learning rate and the five loss weights
+        enc.update(out_feature_size=in_size, out_feature_height=in_size, out_feature_width=in_size)
+        mdl["decoder"] = dict(in_feature_size=in_size, in_feature_width=in_size, in_feature_height=in_size, in_feature_dim=out_feature_dim)
+        mdl.update(learning_rate=1e-4, start_epoch=0, milestone=0,
+                   loss_weights=dict(loss_joff=0.25, loss_jloc=8.0, loss_mask=1.0, loss_afm=0.1, loss_remask=1.0))
     return AttrDict.wrap(dict(
         experiment=dict(encoder=enc, model=mdl, lidar_dropout=lidar_dropout),
         host=dict(device=device, multi_gpu=multi_gpu),

@@ -980,6 +980,111 @@ def afm(lines, shape_info, height, width):
     return afmap, lab
 
 
+# ------------------------------------------------------------------------------------------ HiSup inference after the heads
+HISUP_MAX_HW = 1 << 22
+HISUP_TOPK = 300
+
+
+def _logit_map(t, n, shape, what):
+    """a logit map with n channels -> (tensor kept alive, B, H, W, (batch, channel, pixel) strides in elements).  Either NCHW fp32
+    [B, n, H, W] or token-major fp32 rows [B*H*W, ld >= n] (a predictor's output, hisup.HiSupHeads._predictor) with shape = (B, H, W)."""
+    _dev(t)
+    if t.dtype != torch.float32:
+        raise P3Error(f"{what}: fp32 logits expected, got {t.dtype}")
+    if t.dim() == 4:
+        B, C, H, W = t.shape
+        if C != n:
+            raise P3Error(f"{what}: {n} channels expected, got {C}")
+        t = t.contiguous()
+        st = (C * H * W, H * W, 1)
+    elif t.dim() == 2 and shape is not None:
+        B, H, W = shape
+        if t.shape[0] != B * H * W or t.shape[1] < n or t.stride(1) != 1:
+            raise P3Error(f"{what}: token-major rows [{B * H * W}, >= {n}] expected, got {tuple(t.shape)}")
+        st = (H * W * t.stride(0), 1, t.stride(0))
+    else:
+        raise P3Error(f"{what}: NCHW [B, {n}, H, W] or token-major rows with shape=(B, H, W) expected, got {tuple(t.shape)}")
+    if B < 1 or H < 1 or W < 1 or H * W > HISUP_MAX_HW:
+        raise P3Error(f"{what}: H * W = {H * W} is beyond the {HISUP_MAX_HW} pixels per map the kernel supports (or an empty map)")
+    return t, B, H, W, st
+
+
+def hisup_junctions(jloc, joff, scale_x=1.0, scale_y=1.0, shape=None):
+    """p3_hisup_junctions: -> (juncs f32 [B,600,2] (x, y), scores f32 [B,600], index i32 [B,600], counts i32 [B,2] = (n_class2, n_class1)).
+    Class 2 first, then class 1; inside a class descending score, equal scores by ascending flat index.  No host synchronisation."""
+    jl, B, H, W, sl = _logit_map(jloc, 3, shape, "hisup_junctions(jloc)")
+    jo, B2, H2, W2, so = _logit_map(joff, 2, shape, "hisup_junctions(joff)")
+    if (B, H, W) != (B2, H2, W2):
+        raise P3Error(f"hisup_junctions: jloc is {(B, H, W)}, joff is {(B2, H2, W2)}")
+    dev = jl.device
+    juncs = torch.empty((B, 2 * HISUP_TOPK, 2), dtype=torch.float32, device=dev)
+    scores = torch.empty((B, 2 * HISUP_TOPK), dtype=torch.float32, device=dev)
+    index = torch.empty((B, 2 * HISUP_TOPK), dtype=torch.int32, device=dev)
+    counts = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    lib().p3_hisup_junctions_workspace_bytes.restype = c_int64
+    ws = workspace(int(lib().p3_hisup_junctions_workspace_bytes(c_int(B), c_int(H), c_int(W))), dev, "hisup_junctions")
+    check(lib().p3_hisup_junctions(ptr(jl), c_int64(sl[0]), c_int64(sl[1]), c_int64(sl[2]), ptr(jo), c_int64(so[0]), c_int64(so[1]), c_int64(so[2]),
+                                   c_int(B), c_int(H), c_int(W), c_float(scale_x), c_float(scale_y), ptr(juncs), ptr(scores), ptr(index), ptr(counts),
+                                   ptr(ws), stream()), "p3_hisup_junctions")
+    return juncs, scores, index, counts
+
+
+def hisup_regions_device(remask, max_regions=1024, shape=None, _guard=0):
+    """p3_hisup_regions without any synchronisation: -> dict(mask f32 [B,H,W], labels i32 [B,H,W], n_regions i32 [B], area i32 [B,R],
+    bbox i32 [B,R,4] = (min_row, min_col, max_row + 1, max_col + 1), score f32 [B,R], status i32 [B] = 1 where n_regions > R = max_regions)."""
+    rm, B, H, W, st = _logit_map(remask, 2, shape, "hisup_regions(remask)")
+    R = int(max_regions)
+    if R < 1:
+        raise P3Error(f"hisup_regions: max_regions = {max_regions}")
+    dev = rm.device
+    g = int(_guard)                 # test hook: the three statistics arrays are carved out of one buffer with g guard words around each
+    arena = torch.full((B * R * 6 + 4 * g,), -559038737, dtype=torch.int32, device=dev) if g else torch.empty(B * R * 6, dtype=torch.int32, device=dev)
+    area = arena[g:g + B * R].view(B, R)
+    bbox = arena[2 * g + B * R:2 * g + B * R * 5].view(B, R, 4)
+    score = arena[3 * g + B * R * 5:3 * g + B * R * 6].view(torch.float32).view(B, R)
+    out = dict(mask=torch.empty((B, H, W), dtype=torch.float32, device=dev), labels=torch.empty((B, H, W), dtype=torch.int32, device=dev),
+               n_regions=torch.empty(B, dtype=torch.int32, device=dev), area=area, bbox=bbox, score=score,
+               status=torch.empty(B, dtype=torch.int32, device=dev))
+    if g:
+        out["_arena"] = arena
+    lib().p3_hisup_regions_workspace_bytes.restype = c_int64
+    ws = workspace(int(lib().p3_hisup_regions_workspace_bytes(c_int(B), c_int(H), c_int(W), c_int(R))), dev, "hisup_regions")
+    check(lib().p3_hisup_regions(ptr(rm), c_int64(st[0]), c_int64(st[1]), c_int64(st[2]), c_int(B), c_int(H), c_int(W), c_int(R), ptr(out["mask"]),
+                                 ptr(out["labels"]), ptr(out["n_regions"]), ptr(area), ptr(bbox), ptr(score), ptr(out["status"]), ptr(ws), stream()),
+          "p3_hisup_regions")
+    return out
+
+
+def hisup_regions(remask, max_regions=1024, shape=None):
+    """the checking form of hisup_regions_device: reads the status words on the host and raises when an image has more regions than max_regions"""
+    out = hisup_regions_device(remask, max_regions, shape)
+    if bool(out["status"].any()):
+        raise P3Error(f"hisup_regions: an image has more than max_regions = {max_regions} regions (n_regions = {out['n_regions'].tolist()})")
+    return out
+
+
+def hisup_val_loss(jloc, joff, mask, afm_pred, remask, t_jloc, t_joff, t_mask, t_afm):
+    """p3_hisup_val_loss: -> fp32 [5] = loss_jloc, loss_joff, loss_mask, loss_afm, loss_remask (un-weighted, model_hisup.py:241-245)"""
+    _dev(jloc)
+    B, C, H, W = jloc.shape
+    want = ((jloc, 3), (joff, 2), (mask, 2), (afm_pred, 2), (remask, 2), (t_jloc, 1), (t_joff, 2), (t_mask, 1), (t_afm, 2))
+    for i, (t, n) in enumerate(want):
+        _dev(t)
+        if tuple(t.shape) != (B, n, H, W):
+            raise P3Error(f"hisup_val_loss: argument {i} must be {(B, n, H, W)}, got {tuple(t.shape)}")
+    if H * W > HISUP_MAX_HW:
+        raise P3Error(f"hisup_val_loss: H * W = {H * W} is beyond the {HISUP_MAX_HW} pixels per map the kernel supports")
+    f = [t.contiguous().float() for t in (jloc, joff, mask, afm_pred, remask)]
+    tj = t_jloc.contiguous().to(torch.int64)
+    tt = [t.contiguous().float() for t in (t_joff, t_mask, t_afm)]
+    losses = torch.empty(5, dtype=torch.float32, device=jloc.device)
+    lib().p3_hisup_val_loss_workspace_bytes.restype = c_int64
+    ws = workspace(int(lib().p3_hisup_val_loss_workspace_bytes(c_int(B), c_int(H), c_int(W))), jloc.device, "hisup_val_loss")
+    check(lib().p3_hisup_val_loss(ptr(f[0]), ptr(f[1]), ptr(f[2]), ptr(f[3]), ptr(f[4]), ptr(tj), ptr(tt[0]), ptr(tt[1]), ptr(tt[2]), c_int(B),
+                                  c_int(H), c_int(W), ptr(losses), ptr(ws), stream()), "p3_hisup_val_loss")
+    return losses
+
+
 def cast(a, dtype):
     out = torch.empty(a.shape, dtype=dtype, device=a.device)
     check(lib().p3_cast(ptr(a.contiguous()), c_int(dt(a)), ptr(out), c_int(dt(out)), c_int64(a.numel()), stream()), "p3_cast")

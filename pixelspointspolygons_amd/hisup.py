@@ -8,6 +8,9 @@ zero-bordered image (p3_pad_nhwc + p3_gemm P3_A_CONV3X3 / conv_pad) with its Bat
 BatchNorm + ReLU is never applied in a pass of its own: it travels as per-channel (scale, shift) to the kernel that reads the map next
 (the next image builder, the ECA pool, the mixer).  Channel counts are padded to multiples of 32 with zero weights (the GEMM's K slice).
 Forward only (eval and train-mode BatchNorm incl. the running-statistic updates); there is no hand-written backward for this head set.
+
+The whole model for inference (second half of this file): `HiSupModel` (the reference's factory, model_hisup.py:312-360), `EncoderDecoder` (`HiSupHeads` + encoder;
+`forward_val` of :229-293 on the device up to the hand-over to the OpenCV polygonizer: csrc/hisup_predict.hip) and `AnnotationEncoder` (:66-120).
 """
 import math
 
@@ -15,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from . import hip, ops
-from .ffl import _khwc
+from .ffl import EarlyFusionViTCNN, PointPillarsViTCNN, ViTCNN, _khwc
 from .vision_transformer import compute_dtype, is_split
 
 
@@ -158,18 +161,24 @@ class HiSupHeads(nn.Module):
         B, C, H, W = features.shape
         if C != self.dim_in:
             raise hip.P3Error(f"HiSupHeads: expected {self.dim_in} feature channels, got {C}")
+        return self._heads(hip.nchw_to_nhwc(features, self.cd, _up32(C)), None, B, H, W)
+
+    @torch.no_grad()
+    def _heads(self, F_, F_aff, B, H, W):
+        """the head set on a token-major feature map [B*H*W, >= dim_in] in the compute dtype; F_aff = (scale, shift) of a BatchNorm + ReLU that is
+        still pending on it (the `*_vit_cnn` encoders' `features_nhwc`), None for a finished map."""
+        C = self.dim_in
         self._bhw = (B, H, W)
         HW, cd = H * W, self.cd
         with ops.defer_bumps():
-            F_ = hip.nchw_to_nhwc(features, cd, _up32(C))
-            xF = self._image(F_, C)
+            xF = self._image(F_, C, F_aff)
             joff, n_joff = self._predictor(xF, C, self.joff_head.heads[0])
             mask_a, mask_aff = self._tower(xF, C, self.mask_head)
             jloc_a, jloc_aff = self._tower(xF, C, self.jloc_head)
             afm_a, afm_aff = self._tower(xF, C, self.afm_head)
             mz, mz_aff = self._eca(afm_a, afm_aff, mask_a, mask_aff, self.a2m_att)
             jz, jz_aff = self._eca(afm_a, afm_aff, jloc_a, jloc_aff, self.a2j_att)
-            tmp = torch.zeros((B * HW, _up32(C)), dtype=cd, device=features.device)
+            tmp = torch.zeros((B * HW, _up32(C)), dtype=cd, device=F_.device)
             hip.affine_relu_mix(tmp, mask_a, mask_aff, HW, C, b=mz, aff_b=mz_aff)          # mask_feature + mask_att_feature
             mask, n_mask = self._predictor(self._image(tmp, C), C, self.mask_predictor)
             hip.affine_relu_mix(tmp, jloc_a, jloc_aff, HW, C, b=jz, aff_b=jz_aff)
@@ -177,9 +186,175 @@ class HiSupHeads(nn.Module):
             afm, n_afm = self._predictor(self._image(afm_a, C, afm_aff), C, self.afm_predictor)
             afm_cd = afm if cd == torch.float32 else hip.cast(afm, cd)
             ref_a, ref_aff = self._tower(self._image(afm_cd, n_afm), n_afm, self.refuse_conv)
-            cat = torch.zeros((B * HW, 2 * _up32(C)), dtype=cd, device=features.device)     # torch.cat((features, afm_conv), dim=1)
-            hip.affine_relu_mix(cat, F_, None, HW, C)
+            cat = torch.zeros((B * HW, 2 * _up32(C)), dtype=cd, device=F_.device)     # torch.cat((features, afm_conv), dim=1)
+            hip.affine_relu_mix(cat, F_, F_aff, HW, C)
             hip.affine_relu_mix(cat[:, C:], ref_a, ref_aff, HW, C)
             fin_a, fin_aff = self._tower(self._image(cat, 2 * C), 2 * C, self.final_conv)
+            self._rows = {"joff": joff, "jloc": jloc}      # the predictors' own token-major fp32 rows [R, 8] (p3_hisup_junctions reads either layout)
             return {"joff": self._nchw(joff, n_joff), "jloc": self._nchw(jloc, n_jloc), "mask": self._nchw(mask, n_mask),
                     "afm": self._nchw(afm, n_afm), "remask": self._nchw(fin_a, 2, fin_aff)}
+
+
+# ================================================================================================ the whole model (inference)
+LOSS_KEYS = ("loss_jloc", "loss_joff", "loss_mask", "loss_afm", "loss_remask")
+
+
+class AnnotationEncoder:
+    """model_hisup.py:66-120: list of per-image annotation dicts (junctions [n, 2] (x, y), juncs_tag [n] in {1, 2}, edges_positive [e, 2],
+    mask [H, W], height, width, juncs_index, bbox) -> (targets, metas); targets = {jloc [B,1,H,W] int64, joff [B,2,H,W], mask [B,1,H,W],
+    afmap [B,2,H,W]} on the annotations' device.  The attraction field is p3_afm (csrc/afm.hip)."""
+
+    def __init__(self, cfg):
+        self.target_h = cfg.experiment.encoder.in_height
+        self.target_w = cfg.experiment.encoder.in_width
+
+    def __call__(self, annotations):
+        targets, metas = [], []
+        for ann in annotations:
+            t, m = self._process_per_image(ann)
+            targets.append(t)
+            metas.append(m)
+        return {k: torch.stack([t[k] for t in targets]) for k in ("jloc", "joff", "mask", "afmap")}, metas
+
+    def _process_per_image(self, ann):
+        junctions = ann["junctions"]
+        device = junctions.device
+        height, width = int(ann["height"]), int(ann["width"])
+        jmap = torch.zeros((height, width), device=device, dtype=torch.long)
+        joff = torch.zeros((2, height, width), device=device, dtype=torch.float32)
+        edges = ann["edges_positive"]
+        if len(edges) == 0:
+            afmap = torch.zeros((1, 2, height, width), device=device, dtype=torch.float32)
+        else:
+            lines = torch.cat((junctions[edges[:, 0]], junctions[edges[:, 1]]), dim=-1)
+            shape_info = torch.tensor([[0, lines.size(0), height, width]], dtype=torch.int32, device=device)
+            afmap, _ = hip.afm(lines, shape_info, height, width)
+        xint, yint = junctions[:, 0].long(), junctions[:, 1].long()
+        off_x = junctions[:, 0] - xint.float() - 0.5
+        off_y = junctions[:, 1] - yint.float() - 0.5
+        if len(junctions) and (xint.min() < 0 or xint.max() >= width or yint.min() < 0 or yint.max() >= height):
+            raise ValueError('Junctions out of bound')
+        jmap[yint, xint] = ann["juncs_tag"].to(jmap.dtype)
+        joff[0, yint, xint] = off_x
+        joff[1, yint, xint] = off_y
+        meta = {"junc": junctions, "junc_index": ann["juncs_index"], "bbox": ann["bbox"]}
+        return {"jloc": jmap[None], "joff": joff, "mask": ann["mask"].float()[None], "afmap": afmap[0]}, meta
+
+
+class EncoderDecoder(HiSupHeads):
+    """model_hisup.py:122-308, inference: encoder + head set (`HiSupHeads` is the base class, so the state_dict is the reference's: `encoder.*`
+    and the head keys at the top level) + what `forward_val` does after the heads, on the device: validation losses (p3_hisup_val_loss),
+    junctions (p3_hisup_junctions), building regions (p3_hisup_regions).  Polygonization (`generate_polygon`, OpenCV contours) is host code of
+    the reference and starts from `output["regions"]`, see INTEGRATION.md."""
+
+    def __init__(self, cfg, encoder, max_regions=1024):
+        super().__init__(cfg)
+        self.cfg = cfg
+        self.annotation_encoder = AnnotationEncoder(cfg)
+        self.encoder = encoder
+        enc = cfg.experiment.encoder
+        self.pred_height, self.pred_width = int(enc.out_feature_height), int(enc.out_feature_width)
+        self.origin_height, self.origin_width = int(enc.in_height), int(enc.in_width)
+        self.max_regions = int(max_regions)
+
+    def init_loss_dict(self):
+        return {k: 0.0 for k in LOSS_KEYS}
+
+    def forward(self, x_images, x_points, y=None):
+        if self.training:
+            return self.forward_train(x_images, x_points, y=y)
+        return self.forward_val(x_images, x_points, y=y)
+
+    def forward_train(self, x_images, x_lidar, y=None):
+        raise NotImplementedError("HiSup training is not implemented on the HIP path: the head set has no backward yet. "
+                                  "Call model.eval() and use forward_val / forward_val_device.")
+
+    @torch.no_grad()
+    def forward_common(self, x_images, x_lidar, y=None):
+        """-> (targets | None, dict(joff, jloc, mask, afm, remask) NCHW fp32).  A `*_vit_cnn` encoder hands its token-major map with the pending
+        BatchNorm + ReLU straight to the heads; any other encoder module is called for its NCHW map as in the reference (:201-208)."""
+        targets = self.annotation_encoder(y)[0] if y is not None else None
+        enc = self.cfg.experiment.encoder
+        if not (enc.use_images or enc.use_lidar):
+            raise ValueError("At least one of use_images or use_lidar must be True")
+        if hasattr(self.encoder, "features_nhwc"):
+            tokens = self.encoder.tokens(x_images if enc.use_images else None, x_lidar if enc.use_lidar else None)
+            buf, sc, sh = self.encoder.features_nhwc(tokens)
+            B, H = tokens.shape[0], self.encoder.out_size
+            return targets, self._heads(buf, (sc, sh), B, H, H)
+        if enc.use_images and enc.use_lidar:
+            features = self.encoder(x_images, x_lidar)
+        else:
+            features = self.encoder(x_images if enc.use_images else x_lidar)
+        return targets, HiSupHeads.forward(self, features)
+
+    @torch.no_grad()
+    def forward_val_device(self, x_images, x_lidar, y=None):
+        """`forward_val` without any host synchronisation: -> (output, loss_dict) of device tensors.  output: juncs [B,600,2], junc_scores [B,600],
+        junc_index [B,600], junc_counts [B,2] (hip.hisup_junctions), mask [B,H,W], regions = dict(labels, n_regions, area, bbox, score, status)
+        (hip.hisup_regions_device; status[b] = 1: more than max_regions regions in image b) and `heads`, the five NCHW maps."""
+        targets, heads = self.forward_common(x_images, x_lidar, y)
+        B, _, H, W = heads["joff"].shape
+        assert H == self.pred_height and W == self.pred_width
+        if (self.origin_height, self.origin_width) != (H, W):
+            raise NotImplementedError(f"forward_val resizes the {H} x {W} mask to the input size {self.origin_height} x {self.origin_width} with "
+                                      "cv2.resize; every shipped HiSup configuration predicts at the input size (224), so only ratio 1 is supported")
+        loss_dict = self.init_loss_dict()
+        if targets is not None:
+            losses = hip.hisup_val_loss(heads["jloc"], heads["joff"], heads["mask"], heads["afm"], heads["remask"], targets["jloc"], targets["joff"],
+                                        targets["mask"], targets["afmap"])
+            loss_dict = {k: losses[i] for i, k in enumerate(LOSS_KEYS)}
+        rows = self._rows
+        juncs, scores, index, counts = hip.hisup_junctions(rows["jloc"], rows["joff"], self.origin_width / W, self.origin_height / H, shape=(B, H, W))
+        reg = hip.hisup_regions_device(heads["remask"], self.max_regions)
+        output = {"juncs": juncs, "junc_scores": scores, "junc_index": index, "junc_counts": counts, "mask": reg.pop("mask"), "regions": reg,
+                  "heads": heads}
+        return output, loss_dict
+
+    @torch.no_grad()
+    def forward_val(self, x_images, x_lidar, y=None):
+        """model_hisup.py:229-293 up to the hand-over to `generate_polygon`: -> (output, loss_dict).  output["juncs_pred"]: list of [n, 2] fp32 numpy
+        arrays (x, y), class 2 first; output["mask_pred"]: list of [H, W] fp32 numpy arrays; output["regions"]: per image dict(labels int32 [H, W],
+        area int32 [n], bbox int32 [n, 4], score fp32 [n]) in place of the reference's `polys_pred` / `scores`.  One device-to-host copy per kind."""
+        out, loss_dict = self.forward_val_device(x_images, x_lidar, y)
+        reg = out["regions"]
+        status, n_reg = reg["status"].cpu().numpy(), reg["n_regions"].cpu().numpy()
+        if status.any():
+            raise hip.P3Error(f"forward_val: an image has more than max_regions = {self.max_regions} regions (n_regions = {n_reg.tolist()})")
+        juncs, counts = out["juncs"].cpu().numpy(), out["junc_counts"].cpu().numpy()
+        mask, labels = out["mask"].cpu().numpy(), reg["labels"].cpu().numpy()
+        area, bbox, score = reg["area"].cpu().numpy(), reg["bbox"].cpu().numpy(), reg["score"].cpu().numpy()
+        B = mask.shape[0]
+        output = {"juncs_pred": [juncs[b, :counts[b].sum()].copy() for b in range(B)], "mask_pred": [mask[b] for b in range(B)],
+                  "regions": [{"labels": labels[b], "area": area[b, :n_reg[b]].copy(), "bbox": bbox[b, :n_reg[b]].copy(),
+                               "score": score[b, :n_reg[b]].copy()} for b in range(B)]}
+        return output, loss_dict
+
+
+class HiSupModel(torch.nn.Module):
+    """Factory with the reference's signature and encoder dispatch (model_hisup.py:312-360)."""
+
+    def __new__(cls, cfg, local_rank=0):
+        enc = cfg.experiment.encoder
+        if enc.use_images and enc.use_lidar:
+            if enc.name == "early_fusion_vit_cnn":
+                encoder = EarlyFusionViTCNN(cfg, local_rank=local_rank)
+            else:
+                raise NotImplementedError(f"Encoder {enc.name} not implemented for {cls.__name__}")
+        elif enc.use_images:
+            if enc.name == "vit_cnn":
+                encoder = ViTCNN(cfg, local_rank=local_rank)
+            else:
+                raise NotImplementedError(f"Encoder {enc.name} not implemented for {cls.__name__}")
+        elif enc.use_lidar:
+            if enc.name == "pointpillars_vit_cnn":
+                encoder = PointPillarsViTCNN(cfg, local_rank=local_rank)
+            else:
+                raise NotImplementedError(f"Encoder {enc.name} not implemented for {cls.__name__}")
+        else:
+            raise ValueError("Please specify either and image or lidar encoder with encoder=<name>. See help for a list of available encoders.")
+        model = EncoderDecoder(encoder=encoder, cfg=cfg)
+        model.to(cfg.host.device)
+        if cfg.host.multi_gpu:
+            raise NotImplementedError("HiSupModel: multi_gpu wraps the model for training (SyncBatchNorm + DDP); the HIP path has HiSup inference only")
+        return model
