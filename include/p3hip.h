@@ -690,6 +690,32 @@ int p3_hisup_val_loss(const float* jloc, const float* joff, const float* mask, c
                       void* stream);
 int64_t p3_hisup_val_loss_workspace_bytes(int B, int H, int W);
 
+/* ------------------------------------------------------------------------------------------
+ * FFL active-contour (ACM) polygon optimiser: predict/ffl/polygonize_acm.py:77-220 (`PolygonAlignLoss`, `TensorPolyOptimizer`), `steps` plain-SGD
+ * iterations of every contour vertex in one call, with the analytic gradient of the reference's loss instead of an autograd graph.
+ * pos fp32 [N,2] (row, col), updated in place.  poly_slice int32 [P,2] = [first vertex, one past the last) of each polygon, poly_batch int32 [P] its
+ * image, is_endpoint uint8 [N] (a vertex that never moves), indicator fp32 [B,H,W], c0c2 fp32 [B,4,H,W] (c0 re, c0 im, c2 re, c2 im).
+ * A polygon p_0..p_{n-1}, open or closed, has the n edges e_i = p_{(i+1) mod n} - p_i (the reference pads every polygon with its first vertex).
+ *   edge:    mid = round_half_even((p_i + p_{i+1}) / 2) clamped into the map; norm = |e|, mask = norm < 0.1 ? 0 : 1; z = e / (norm + 1e-3) as re + i im;
+ *            align = mask |z^4 + c2(mid) z^2 + c0(mid)|^2, length = (norm mask)^2
+ *   vertex:  level = (bilinear(indicator, p) - data_level)^2, weights from the unclamped floor, the four fetches clamped
+ *   total = (data_coef sum level + length_coef sum length + crossfield_coef sum align) / (data_coef + length_coef + crossfield_coef)
+ *   round, floor, the clamps and the mask are constants of the gradient; d norm / d e = 0 at norm = 0, so a masked edge contributes exactly 0.
+ *   p <- p - lr_i grad for every vertex that is no endpoint, lr_i = poly_lr * (i < warmup_iters ? 1 + (warmup_factor - 1)(warmup_iters - i) / warmup_iters : 1),
+ *   i = first_iter .. first_iter + steps - 1 (evaluated in double, as torch's LambdaLR does).
+ * Polygons of up to 4096 vertices run all steps in ONE launch, one workgroup each, positions in LDS; longer ones (or all, force_fallback != 0) take one
+ * launch per step over `workspace`.  Both paths, any split of the steps into calls, any polygon order and any two runs give the same bits; no atomics, no
+ * host synchronisation.  max_len: an upper bound of the vertices of one polygon that the HOST knows (sizes the LDS and decides whether the fallback is
+ * launched at all; a longer polygon is left as it is), <= 0: unknown, both paths are launched.  poly_losses (NULL or fp32 [P,3]): each polygon's
+ * (align, level, length) sums of the LAST executed step, evaluated before its update.  workspace: p3_acm_workspace_bytes(N) bytes, needed (non-NULL)
+ * only when the fallback can run.  P == 0, N == 0 or steps == 0: returns 0 without a launch.
+ * ------------------------------------------------------------------------------------------ */
+int p3_acm_optimize(float* pos, int64_t N, const int32_t* poly_slice, const int32_t* poly_batch, int P, const uint8_t* is_endpoint,
+                    const float* indicator, const float* c0c2, int B, int H, int W, float data_coef, float length_coef, float crossfield_coef,
+                    float data_level, double poly_lr, int warmup_iters, double warmup_factor, int first_iter, int steps, int max_len,
+                    int force_fallback, float* poly_losses, void* workspace, void* stream);
+int64_t p3_acm_workspace_bytes(int64_t N);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1085,6 +1085,50 @@ def hisup_val_loss(jloc, joff, mask, afm_pred, remask, t_jloc, t_joff, t_mask, t
     return losses
 
 
+# ------------------------------------------------------------------------------------------ FFL active-contour polygon optimiser
+ACM_LDS_CAP = 4096          # csrc/acm.hip: vertices of one polygon that fit the one-launch LDS path
+
+
+def acm_optimize(pos, poly_slice, batch, is_endpoint, indicator, c0c2, data_coef, length_coef, crossfield_coef, data_level=0.5, poly_lr=0.01,
+                 warmup_iters=100, warmup_factor=0.1, first_iter=0, steps=500, losses=False, force_fallback=False, max_len=None):
+    """p3_acm_optimize (predict/ffl/polygonize_acm.py:77-220): `steps` SGD iterations first_iter .. first_iter + steps - 1 on pos fp32 [N,2] (row, col), IN PLACE.
+    poly_slice [P,2]; batch [N] is the tensorpoly's per-node image index (a polygon's image is that of its first vertex); is_endpoint [N].
+    indicator [B,H,W] or seg [B,C,H,W] (channel 0 is taken), c0c2 [B,4,H,W]; bf16 / strided maps are copied to contiguous fp32.
+    max_len: longest polygon if the caller knows it (else read from poly_slice: one host synchronisation).  max_len=0 ("unknown", what the raw C entry
+    takes) is for tests only: it sizes the per-step fallback grid for a polygon of all N vertices, thousands of workgroups that return at once.  -> pos, or (pos, losses fp32 [P,3] = (align,
+    level, length) per polygon at the last step, before its update) with losses=True."""
+    for t in (pos, poly_slice, batch, is_endpoint, indicator, c0c2):
+        _dev(t)
+    if pos.dtype != torch.float32 or pos.dim() != 2 or pos.shape[1] != 2 or not pos.is_contiguous():
+        raise P3Error(f"acm_optimize: pos must be contiguous float32 [N, 2] (it is updated in place), got {pos.dtype} {tuple(pos.shape)}")
+    N, P = pos.shape[0], poly_slice.shape[0]
+    if poly_slice.dim() != 2 or poly_slice.shape[1] != 2 or batch.shape[0] != N or is_endpoint.shape[0] != N:
+        raise P3Error(f"acm_optimize: poly_slice [P, 2], batch [N], is_endpoint [N] expected, got {tuple(poly_slice.shape)}, {tuple(batch.shape)}, {tuple(is_endpoint.shape)}")
+    if indicator.dim() == 4:
+        indicator = indicator[:, 0]
+    if indicator.dim() != 3 or c0c2.dim() != 4 or c0c2.shape[1] != 4 or (c0c2.shape[0],) + tuple(c0c2.shape[2:]) != tuple(indicator.shape):
+        raise P3Error(f"acm_optimize: indicator [B, H, W] and c0c2 [B, 4, H, W] expected, got {tuple(indicator.shape)}, {tuple(c0c2.shape)}")
+    B, H, W = indicator.shape
+    ind, cf = indicator.contiguous().float(), c0c2.contiguous().float()
+    out = torch.zeros((P, 3), dtype=torch.float32, device=pos.device) if losses else None          # zeros: a polygon longer than a wrong max_len is skipped, row and all
+    if P == 0 or N == 0 or steps == 0:
+        return (pos, out) if losses else pos
+    sl = poly_slice.to(torch.int32).contiguous()
+    pb = batch.index_select(0, poly_slice[:, 0].clamp(0, N - 1).long()).to(torch.int32).contiguous()          # image of a polygon = image of its first vertex
+    ep = is_endpoint.to(torch.uint8).contiguous()
+    if max_len is None:
+        max_len = int((poly_slice[:, 1] - poly_slice[:, 0]).max())
+    ws = None
+    if force_fallback or max_len > ACM_LDS_CAP or max_len <= 0:
+        lib().p3_acm_workspace_bytes.restype = c_int64
+        ws = workspace(int(lib().p3_acm_workspace_bytes(c_int64(N))), pos.device, "acm")
+    check(lib().p3_acm_optimize(ptr(pos), c_int64(N), ptr(sl), ptr(pb), c_int(P), ptr(ep), ptr(ind), ptr(cf), c_int(B), c_int(H), c_int(W), c_float(data_coef),
+                                c_float(length_coef), c_float(crossfield_coef), c_float(data_level), ctypes.c_double(poly_lr), c_int(int(warmup_iters)),
+                                ctypes.c_double(warmup_factor), c_int(int(first_iter)), c_int(int(steps)), c_int(int(max_len)), c_int(int(bool(force_fallback))),
+                                ptr(out), ptr(ws), stream()), "p3_acm_optimize")
+    return (pos, out) if losses else pos
+
+
 def cast(a, dtype):
     out = torch.empty(a.shape, dtype=dtype, device=a.device)
     check(lib().p3_cast(ptr(a.contiguous()), c_int(dt(a)), ptr(out), c_int(dt(out)), c_int64(a.numel()), stream()), "p3_cast")
