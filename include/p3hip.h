@@ -716,6 +716,52 @@ int p3_acm_optimize(float* pos, int64_t N, const int32_t* poly_slice, const int3
                     int force_fallback, float* poly_losses, void* workspace, void* stream);
 int64_t p3_acm_workspace_bytes(int64_t N);
 
+/* ------------------------------------------------------------------------------------------
+ * FFL active-skeleton (ASM) optimiser: predict/ffl/polygonize_asm.py:133-421 (`AlignLoss`, `TensorSkeletonOptimizer`) over the containers of
+ * torch_lydorn/torchvision/transforms/tensorskeleton.py, `steps` RMSprop iterations of every skeleton node in one call, with the analytic gradient
+ * of the reference's total_loss instead of an autograd graph.  Line 353 keeps three terms in the loss that is differentiated,
+ *     total_loss = data_coef * level_loss + length_coef * total_length_loss + crossfield_coef * total_align_loss,
+ * so the positions depend on level, length and align alone; the curvature, corner and junction terms (reported, never differentiated) are not built.
+ *
+ * Containers (tensorskeleton.py:44-68): pos [N,2] (row, col) fp32, degrees [N], path_index [M] node ids, path_delim [P+1] delimiting paths inside
+ * path_index, batch [N] each node's image.  A junction node appears in path_index once per incident path end; a closed contour repeats its first
+ * node id as its last entry.  k is a position in path_index; "path start" / "path end" come from path_delim.
+ *
+ * Terms of one step (polygonize_asm.py:177-235):
+ *   level   (:205-216) every node, on a path or not: (bilinear(indicator, pos) - data_level)^2, the interpolation of functionnal.py:4-42 (weights from
+ *           the unclamped floor, fetches clamped).
+ *   align   (:179-202) every edge (k, k+1), k no path end: t = p[k+1] - p[k], mask 0 where |t| < 0.1, z = t / (|t| + 1e-6), c0 and c2 read at the
+ *           rounded (half to even), clamped midpoint; the term is |z^4 + c2 z^2 + c0|^2 * mask and its gradient flows to both end nodes (torch.norm's
+ *           subgradient at 0 is 0).  The maps are read in the image of the node that evaluates the edge: a path lies in one image.
+ *   length  (:219-235) every k that is neither a path start nor a path end: |p[k] - p[k-1]|^2 + |p[k+1] - p[k]|^2 with both neighbours detached, so the
+ *           gradient 2 (p[k] - p[k-1]) - 2 (p[k+1] - p[k]) goes to node path_index[k] only.
+ *   Nothing is divided by a coefficient sum.
+ * Schedules (:151-156, 342-344, 380-381, 411-412), evaluated in double and rounded to float: the three coefficients at integer iteration i are
+ * scipy interp1d's linear form over `knots` (slope = (y_hi - y_lo) / (x_hi - x_lo); y = slope * (i - x_lo) + y_lo on the segment x_lo <= i < x_hi
+ * that numpy.interp, to which scipy hands 1-d tables, picks: a knot gives its own value; beyond the last knot the last segment is extended); lr_i = lr * gamma^i by repeated multiplication, as ExponentialLR chains it.
+ * Update (:380, 404-409): torch.optim.RMSprop(alpha = 0.9, eps = 1e-8, no momentum, not centred): sq = 0.9 sq + 0.1 g^2,
+ * pos -= lr_i * g / (sqrt(sq) + eps).  A node with is_tip (degree 1) keeps its position; its sq is still updated.
+ *
+ * The work unit is a connected component of the skeleton graph, described by a plan the host builds once per skeleton (csrc/asm.hip explains it):
+ * comp_ptr int32 [C+1] delimits components inside cn_node int32 [CN] (node ids; an entry's index inside its component is its local index);
+ * cn_occ int32 [CN+1] delimits each entry's occurrences, ascending in k, inside slot_nb int32 [S,2] = local index of the node at k-1 (-1 at a path
+ * start) and at k+1 (-1 at a path end).  is_tip uint8 [N], node_batch int32 [N].  Every index is clamped on the device.
+ * Components of at most 4096 nodes run all steps in ONE launch (positions in LDS, one barrier per step); larger ones, or all with force_fallback,
+ * take one launch per step over `workspace` (p3_asm_workspace_bytes(N, CN), needed only then).  Both paths, any split of the steps into calls
+ * (first_iter, sq carried) and any two runs give the same bits; no atomics, no host synchronisation.  max_comp: an upper bound of the nodes of one
+ * component that the HOST knows, <= 0: unknown.  knots: HOST double [4, nk] = step_thresholds, data, length, crossfield (2 <= nk <= 8).
+ * pos and sq fp32 [N,2] are updated in place (sq zeros on a first call).  grad_out (NULL or fp32 [N,2]): the gradient of the LAST executed step.
+ * comp_losses (NULL or fp32 [C,3]): each component's (align, level, length) sums of the last executed step before its update, each edge counted
+ * once by its tail.  C == 0, N == 0, CN == 0 or steps == 0: returns 0 without a launch.
+ * p3_asm_schedule (host only): out[4] = (data, length, crossfield, lr) of iteration `iter`, the floats the kernel uses, from the same functions.
+ * ------------------------------------------------------------------------------------------ */
+int p3_asm_optimize(float* pos, float* sq, int64_t N, const int32_t* comp_ptr, int C, const int32_t* cn_node, const int32_t* cn_occ, int64_t CN,
+                    const int32_t* slot_nb, int64_t S, const uint8_t* is_tip, const int32_t* node_batch, const float* indicator, const float* c0c2,
+                    int B, int H, int W, float data_level, const double* knots, int nk, double lr, double gamma, int first_iter, int steps,
+                    int max_comp, int force_fallback, float* grad_out, float* comp_losses, void* workspace, void* stream);
+int64_t p3_asm_workspace_bytes(int64_t N, int64_t CN);
+int p3_asm_schedule(int iter, const double* knots, int nk, double lr, double gamma, double* out);
+
 #ifdef __cplusplus
 }
 #endif

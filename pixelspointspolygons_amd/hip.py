@@ -1129,6 +1129,71 @@ def acm_optimize(pos, poly_slice, batch, is_endpoint, indicator, c0c2, data_coef
     return (pos, out) if losses else pos
 
 
+# ------------------------------------------------------------------------------------------ FFL active-skeleton optimiser
+ASM_LDS_CAP = 4096          # csrc/asm.hip: nodes of one connected component that fit the one-launch LDS path
+ASM_MAX_KNOTS = 8
+
+
+def _asm_knots(knots):
+    """[step_thresholds, data, length, crossfield] -> (ctypes double [4 * nk], nk)"""
+    rows = [[float(v) for v in r] for r in knots]
+    nk = len(rows[0]) if rows else 0
+    if len(rows) != 4 or any(len(r) != nk for r in rows) or not 2 <= nk <= ASM_MAX_KNOTS:
+        raise P3Error(f"asm: knots must be [step_thresholds, data, length, crossfield] with 2 .. {ASM_MAX_KNOTS} entries each")
+    return (ctypes.c_double * (4 * nk))(*[v for r in rows for v in r]), nk
+
+
+def asm_schedule(iter_num, knots, lr=0.1, gamma=0.995):
+    """p3_asm_schedule (host only, needs no device): the (data, length, crossfield, lr) floats the kernel uses at iteration iter_num, as Python floats"""
+    arr, nk = _asm_knots(knots)
+    out = (ctypes.c_double * 4)()
+    check(lib().p3_asm_schedule(c_int(int(iter_num)), arr, c_int(nk), ctypes.c_double(lr), ctypes.c_double(gamma), out), "p3_asm_schedule")
+    return tuple(out)
+
+
+def asm_optimize(pos, sq, plan, is_tip, batch, indicator, c0c2, knots, data_level=0.5, lr=0.1, gamma=0.995, first_iter=0, steps=300, grad_out=None,
+                 losses=False, force_fallback=False):
+    """p3_asm_optimize (predict/ffl/polygonize_asm.py:133-421): `steps` RMSprop iterations first_iter .. first_iter + steps - 1 on pos fp32 [N,2] (row, col),
+    IN PLACE, with the state sq fp32 [N,2] (zeros on a first call) read and written.  plan: polygonize_asm.AsmPlan on the device (components, occurrence
+    lists and neighbour indices derived from path_index / path_delim, built once per skeleton on the host).  is_tip [N] (degrees == 1), batch [N].
+    indicator [B,H,W] or seg [B,C,H,W] (channel 0 is taken), c0c2 [B,4,H,W]; bf16 / strided maps are copied to contiguous fp32.
+    knots: [step_thresholds, data, length, crossfield] of loss_params.coefs.  grad_out: None or contiguous fp32 [N,2], receives the gradient of the last
+    executed step.  Reads nothing back.  -> pos, or (pos, losses fp32 [C,3] = (align, level, length) per component at the last step, before its update)."""
+    for t in (pos, sq, is_tip, batch, indicator, c0c2) + tuple(getattr(plan, k) for k in ("comp_ptr", "cn_node", "cn_occ", "slot_nb")):
+        _dev(t)
+    for name, t in (("pos", pos), ("sq", sq), ("grad_out", grad_out)):
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 2 or not t.is_contiguous() or t.shape[0] != pos.shape[0]):
+            raise P3Error(f"asm_optimize: {name} must be a contiguous float32 [N, 2] device tensor (it is written in place), got {t.dtype} {tuple(t.shape)}")
+    N, C, CN, S = pos.shape[0], plan.comp_ptr.shape[0] - 1, plan.cn_node.shape[0], plan.slot_nb.shape[0]
+    if is_tip.shape[0] != N or batch.shape[0] != N or plan.cn_occ.shape[0] != CN + 1 or plan.slot_nb.dim() != 2 or plan.slot_nb.shape[1] != 2 or C < 0:
+        raise P3Error(f"asm_optimize: is_tip [N], batch [N] and a plan with cn_occ [CN+1], slot_nb [S,2] expected, got {tuple(is_tip.shape)}, {tuple(batch.shape)}, "
+                      f"{tuple(plan.cn_occ.shape)}, {tuple(plan.slot_nb.shape)}")
+    if indicator.dim() == 4:
+        indicator = indicator[:, 0]
+    if indicator.dim() != 3 or c0c2.dim() != 4 or c0c2.shape[1] != 4 or (c0c2.shape[0],) + tuple(c0c2.shape[2:]) != tuple(indicator.shape):
+        raise P3Error(f"asm_optimize: indicator [B, H, W] and c0c2 [B, 4, H, W] expected, got {tuple(indicator.shape)}, {tuple(c0c2.shape)}")
+    B, H, W = indicator.shape
+    arr, nk = _asm_knots(knots)
+    ind, cf = indicator.contiguous().float(), c0c2.contiguous().float()
+    out = torch.zeros((max(C, 0), 3), dtype=torch.float32, device=pos.device) if losses else None
+    if C <= 0 or N == 0 or steps == 0:
+        return (pos, out) if losses else pos
+    i32 = lambda t: t.to(torch.int32).contiguous()
+    # converted copies stay referenced until the launch is queued: a temporary freed while the argument list is built is handed to the next conversion
+    comp_ptr, cn_node, cn_occ, slot_nb = (i32(getattr(plan, k)) for k in ("comp_ptr", "cn_node", "cn_occ", "slot_nb"))
+    tip8, batch32 = is_tip.to(torch.uint8).contiguous(), i32(batch)
+    ws = None
+    if force_fallback or plan.max_comp > ASM_LDS_CAP or plan.max_comp <= 0:
+        lib().p3_asm_workspace_bytes.restype = c_int64
+        ws = workspace(int(lib().p3_asm_workspace_bytes(c_int64(N), c_int64(CN))), pos.device, "asm")
+    check(lib().p3_asm_optimize(ptr(pos), ptr(sq), c_int64(N), ptr(comp_ptr), c_int(C), ptr(cn_node), ptr(cn_occ), c_int64(CN),
+                                ptr(slot_nb), c_int64(S), ptr(tip8), ptr(batch32), ptr(ind), ptr(cf), c_int(B),
+                                c_int(H), c_int(W), c_float(data_level), arr, c_int(nk), ctypes.c_double(lr), ctypes.c_double(gamma), c_int(int(first_iter)),
+                                c_int(int(steps)), c_int(int(plan.max_comp)), c_int(int(bool(force_fallback))), ptr(grad_out), ptr(out), ptr(ws), stream()),
+          "p3_asm_optimize")
+    return (pos, out) if losses else pos
+
+
 def cast(a, dtype):
     out = torch.empty(a.shape, dtype=dtype, device=a.device)
     check(lib().p3_cast(ptr(a.contiguous()), c_int(dt(a)), ptr(out), c_int(dt(out)), c_int64(a.numel()), stream()), "p3_cast")

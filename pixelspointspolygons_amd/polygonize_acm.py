@@ -3,7 +3,7 @@
 
 What stays host code of the caller: the marching-squares initial contours (`polygonize_utils.compute_init_contours_batch`) in front and the shapely
 simplification / polygon assembly (`post_process`) behind; the reference passes both through `polygonize(..., pre_computed={"init_contours_batch": ...})`.
-The ASM method and the optional `dist` term (not in the shipped config) are not built.
+The optional `dist` term (not in the shipped config) is not built; the ASM method is polygonize_asm.py.
 
 `TensorPoly`, `contours_batch_to_tensorpoly` and `tensorpoly_to_contours_batch` keep the reference's fields (torch_lydorn/torchvision/transforms/tensorpoly.py):
 pos [N,2] (row, col), poly_slice [P,2], batch [N], batch_size, is_endpoint [N]."""
