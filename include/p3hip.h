@@ -762,6 +762,31 @@ int p3_asm_optimize(float* pos, float* sq, int64_t N, const int32_t* comp_ptr, i
 int64_t p3_asm_workspace_bytes(int64_t N, int64_t CN);
 int p3_asm_schedule(int iter, const double* knots, int nk, double lr, double gamma, double* out);
 
+/* ------------------------------------------------------------------------------------------
+ * FFL initial contours: predict/ffl/polygonize_utils.py:15-44 (`compute_init_contours_batch`, i.e. skimage.measure.find_contours(indicator, level,
+ * fully_connected='low', positive_orientation='high') per image) on the device, with the contour container of p3_acm_optimize as its output.
+ * indicator fp32 [B,H,W] read through element strides (stride_b, stride_r, stride_c: channel 0 of a [B,C,H,W] map needs no copy); level is a double.
+ *   cell (r, c), 0 <= r < H-1, 0 <= c < W-1, corners ul = I[r,c], ur = I[r,c+1], ll = I[r+1,c], lr = I[r+1,c+1] taken as double; a NaN corner: nothing;
+ *   case = (ul > level) + 2 (ur > level) + 4 (ll > level) + 8 (lr > level); with f(a, b) = (level - a) / (b - a) in double (0 if a == b) the crossing
+ *   points are T = (r, c + f(ul, ur)), B = (r+1, c + f(ll, lr)), L = (r + f(ul, ll), c), R = (r + f(ur, lr), c+1), rounded to fp32 once;
+ *   segments from -> to in slot order: 1 T-L | 2 R-T | 3 R-L | 4 L-B | 5 T-B | 6 R-T, L-B | 7 R-B | 8 B-R | 9 T-L, B-R | 10 B-T | 11 B-L | 12 L-R |
+ *   13 T-R | 14 L-T; key of a segment = 2 (r (W-1) + c) + slot.
+ *   A vertex is a crossed grid edge; linking is by edge identity, never by coordinates; the successor of a segment's `to` vertex is its `from` vertex.
+ *   A contour with a vertex that is the `from` of no segment is open and starts there; any other is closed, starts at the `to` vertex of its
+ *   largest-key segment and does not repeat its first point.  Contours are ordered by image, then by their smallest segment key.
+ * Outputs: pos fp32 [max_vertices,2] (row, col); poly_slice int64 [max_contours,2] = [first vertex, one past the last); poly_batch int32 [max_contours];
+ * batch int64 [max_vertices] the image of each vertex; is_endpoint uint8 [max_vertices] = 1 on both ends of an open contour; counts int32 [3] =
+ * (N vertices, P contours, vertices of the longest contour); n_contours, n_vertices int32 [B]; status int32 [1] = 1 when N > max_vertices or
+ * P > max_contours: counts still hold the true totals and nothing is written past the capacities (B (H (W-1) + (H-1) W) vertices and half as many
+ * contours can never overflow).  H < 2 or W < 2: no contour.
+ * No atomics and one writer per element: two runs give the same bits, an image alone gives the contours it gives inside a batch.  No host
+ * synchronisation; the number of launches depends on B, H, W only.  workspace: p3_init_contours_workspace_bytes(B, H, W) bytes.
+ * ------------------------------------------------------------------------------------------ */
+int p3_init_contours(const float* indicator, int64_t stride_b, int64_t stride_r, int64_t stride_c, int B, int H, int W, double level,
+                     int max_vertices, int max_contours, float* pos, int64_t* poly_slice, int32_t* poly_batch, int64_t* batch, uint8_t* is_endpoint,
+                     int32_t* counts, int32_t* n_contours, int32_t* n_vertices, int32_t* status, void* workspace, void* stream);
+int64_t p3_init_contours_workspace_bytes(int B, int H, int W);
+
 #ifdef __cplusplus
 }
 #endif

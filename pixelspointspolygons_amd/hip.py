@@ -1129,6 +1129,75 @@ def acm_optimize(pos, poly_slice, batch, is_endpoint, indicator, c0c2, data_coef
     return (pos, out) if losses else pos
 
 
+# ------------------------------------------------------------------------------------------ FFL initial contours (marching squares)
+_IC_GUARD_BYTE = 0xA5
+
+
+def _ic_out(shape, dtype, dev, g, arenas):
+    """an output of init_contours_device; with g > 0 it sits between two runs of 16 * g guard bytes inside an arena of its own (kept in `arenas`)"""
+    if not g:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    n = 1
+    for s in shape:
+        n *= s
+    nbytes = n * torch.empty((), dtype=dtype).element_size()
+    arena = torch.full((nbytes + 32 * g,), _IC_GUARD_BYTE, dtype=torch.uint8, device=dev)
+    arenas.append((arena, 16 * g, nbytes))
+    return arena[16 * g:16 * g + nbytes].view(dtype).view(shape)
+
+
+def init_contours_device(indicator, level=0.5, max_vertices=None, max_contours=None, _guard=0):
+    """p3_init_contours (predict/ffl/polygonize_utils.py:15-44: find_contours(indicator, level, fully_connected='low', positive_orientation='high') per image)
+    without any synchronisation.  indicator fp32 [B,H,W] with any strides (seg[:, 0] is not copied), or [B,C,H,W] (channel 0 is taken).
+    -> dict(pos f32 [max_vertices,2] (row, col), poly_slice i64 [max_contours,2], poly_batch i32 [max_contours], batch i64 [max_vertices], is_endpoint u8
+    [max_vertices], counts i32 [3] = (N, P, longest contour), n_contours i32 [B], n_vertices i32 [B], status i32 [1] = 1 when N > max_vertices or P > max_contours;
+    counts are the true totals then, and nothing is written past the capacities).  The default capacities B (H (W-1) + (H-1) W) and half of that cannot overflow.
+    _guard: test hook, guard bytes around every output (out["_arenas"] = [(arena, guard bytes, payload bytes)])."""
+    _dev(indicator)
+    if indicator.dim() == 4:
+        indicator = indicator[:, 0]
+    if indicator.dim() != 3 or indicator.shape[0] < 1 or indicator.shape[1] < 1 or indicator.shape[2] < 1:
+        raise P3Error(f"init_contours: indicator [B, H, W] or seg [B, C, H, W] expected, got {tuple(indicator.shape)}")
+    if indicator.dtype != torch.float32:
+        indicator = indicator.float()
+    B, H, W = indicator.shape
+    bound = B * (H * (W - 1) + (H - 1) * W)
+    nv = max(bound, 1) if max_vertices is None else int(max_vertices)
+    nc = max(bound // 2, 1) if max_contours is None else int(max_contours)
+    if nv < 1 or nc < 1:
+        raise P3Error(f"init_contours: max_vertices = {max_vertices}, max_contours = {max_contours}")
+    dev, arenas, g = indicator.device, [], int(_guard)
+    out = dict(pos=_ic_out((nv, 2), torch.float32, dev, g, arenas), poly_slice=_ic_out((nc, 2), torch.int64, dev, g, arenas),
+               poly_batch=_ic_out((nc,), torch.int32, dev, g, arenas), batch=_ic_out((nv,), torch.int64, dev, g, arenas),
+               is_endpoint=_ic_out((nv,), torch.uint8, dev, g, arenas), counts=_ic_out((3,), torch.int32, dev, g, arenas),
+               n_contours=_ic_out((B,), torch.int32, dev, g, arenas), n_vertices=_ic_out((B,), torch.int32, dev, g, arenas),
+               status=_ic_out((1,), torch.int32, dev, g, arenas))
+    if g:
+        out["_arenas"] = arenas
+    lib().p3_init_contours_workspace_bytes.restype = c_int64
+    ws = workspace(int(lib().p3_init_contours_workspace_bytes(c_int(B), c_int(H), c_int(W))), dev, "init_contours")
+    sb, sr, sc = indicator.stride()
+    check(lib().p3_init_contours(ptr(indicator), c_int64(sb), c_int64(sr), c_int64(sc), c_int(B), c_int(H), c_int(W), ctypes.c_double(float(level)), c_int(nv),
+                                 c_int(nc), ptr(out["pos"]), ptr(out["poly_slice"]), ptr(out["poly_batch"]), ptr(out["batch"]), ptr(out["is_endpoint"]),
+                                 ptr(out["counts"]), ptr(out["n_contours"]), ptr(out["n_vertices"]), ptr(out["status"]), ptr(ws), stream()), "p3_init_contours")
+    return out
+
+
+def init_contours(indicator, level=0.5, max_vertices=None, max_contours=None):
+    """the checking form of init_contours_device: reads counts and status once (the only read-back), raises when a capacity was too small and narrows every
+    array to what was found: pos [N,2], poly_slice [P,2], poly_batch [P], batch [N], is_endpoint [N]; counts = (N, P, longest) as Python ints."""
+    out = init_contours_device(indicator, level, max_vertices, max_contours)
+    N, P, longest, status = torch.cat([out["counts"], out["status"]]).tolist()
+    if status:
+        raise P3Error(f"init_contours: {N} vertices in {P} contours do not fit max_vertices = {out['pos'].shape[0]}, max_contours = {out['poly_slice'].shape[0]}")
+    for k in ("pos", "batch", "is_endpoint"):
+        out[k] = out[k][:N]
+    for k in ("poly_slice", "poly_batch"):
+        out[k] = out[k][:P]
+    out["counts"] = (N, P, longest)
+    return out
+
+
 # ------------------------------------------------------------------------------------------ FFL active-skeleton optimiser
 ASM_LDS_CAP = 4096          # csrc/asm.hip: nodes of one connected component that fit the one-launch LDS path
 ASM_MAX_KNOTS = 8

@@ -1,8 +1,13 @@
 """FFL active-contour (ACM) polygon optimisation: the device part of predict/ffl/polygonize_acm.py of the reference (`PolygonAlignLoss` and
 `TensorPolyOptimizer`, :77-220, and lines 383-398 of `polygonize()`), as one HIP kernel (csrc/acm.hip, p3_acm_optimize) instead of 500 autograd steps.
 
-What stays host code of the caller: the marching-squares initial contours (`polygonize_utils.compute_init_contours_batch`) in front and the shapely
-simplification / polygon assembly (`post_process`) behind; the reference passes both through `polygonize(..., pre_computed={"init_contours_batch": ...})`.
+The marching-squares initial contours in front (`polygonize_utils.compute_init_contours_batch`, polygonize_utils.py:15-44: skimage's find_contours per image
+on the host) are built on the device too: `init_contours` (csrc/contours.hip, p3_init_contours) makes the `TensorPoly` straight from the segmentation map, and
+`polygonize_device` is lines 346-398 of `polygonize()` - seg and crossfield on the device -> optimised contours on the device - with one read-back of three
+counts and no host contour.  The definition init_contours is held to is DESIGN.md section 13 (a pixel that equals the level exactly is linked by grid edge,
+not by coordinate).  `optimize_contours` still takes host contours a caller already has (`pre_computed={"init_contours_batch": ...}` of the reference).
+
+What stays host code of the caller: the shapely simplification / polygon assembly (`post_process`) behind; `tensorpoly_to_contours_batch` hands it the contours.
 The optional `dist` term (not in the shipped config) is not built; the ASM method is polygonize_asm.py.
 
 `TensorPoly`, `contours_batch_to_tensorpoly` and `tensorpoly_to_contours_batch` keep the reference's fields (torch_lydorn/torchvision/transforms/tensorpoly.py):
@@ -161,3 +166,34 @@ def optimize_contours(seg_batch, crossfield_batch, init_contours_batch, config=A
     optimizer = TensorPolyOptimizer(config, tensorpoly, seg_batch[:, 0, :, :], crossfield_batch, config["data_coef"], config["length_coef"],
                                     config["crossfield_coef"])
     return tensorpoly_to_contours_batch(optimizer.optimize())
+
+
+def init_contours(seg_or_indicator, level=0.5):
+    """polygonize_utils.compute_init_contours_batch + contours_batch_to_tensorpoly on the device: seg [B, C, H, W] (channel 0 is the indicator, read in place)
+    or indicator [B, H, W] -> a device TensorPoly whose max_len is filled from the one read-back (vertices, contours, longest), None without any contour."""
+    if not seg_or_indicator.is_cuda:
+        raise hip.P3Error("init_contours: the map must be a device tensor (there is no CPU path)")
+    out = hip.init_contours(seg_or_indicator, level)
+    _, P, longest = out["counts"]
+    if P == 0:
+        return None
+    tensorpoly = TensorPoly(pos=out["pos"], poly_slice=out["poly_slice"], batch=out["batch"], batch_size=seg_or_indicator.shape[0],
+                            is_endpoint=out["is_endpoint"].bool())
+    tensorpoly.max_len = longest
+    return tensorpoly
+
+
+def polygonize_device(seg_batch, crossfield_batch, config=ACM_DEFAULTS):
+    """Lines 346-398 of the reference's polygonize() without a host contour: initial contours at config["data_level"] and the optimiser, both on the device.
+    -> the optimised device TensorPoly (tensorpoly_to_contours_batch hands it to the shapely stage), None without any contour."""
+    assert len(seg_batch.shape) == 4 and seg_batch.shape[1] <= 3, "seg_batch should be (N, C, H, W) with C <= 3, not {}".format(seg_batch.shape)
+    assert len(crossfield_batch.shape) == 4 and crossfield_batch.shape[1] == 4, "crossfield_batch should be (N, 4, H, W)"
+    assert seg_batch.shape[0] == crossfield_batch.shape[0], "Batch size for seg and crossfield should match"
+    if not seg_batch.is_cuda or not crossfield_batch.is_cuda:
+        raise hip.P3Error("polygonize_device: seg_batch and crossfield_batch must be device tensors (there is no CPU path)")
+    tensorpoly = init_contours(seg_batch, config["data_level"])
+    if tensorpoly is None:
+        return None
+    optimizer = TensorPolyOptimizer(config, tensorpoly, seg_batch[:, 0, :, :], crossfield_batch, config["data_coef"], config["length_coef"],
+                                    config["crossfield_coef"])
+    return optimizer.optimize()
