@@ -787,6 +787,42 @@ int p3_init_contours(const float* indicator, int64_t stride_b, int64_t stride_r,
                      int32_t* counts, int32_t* n_contours, int32_t* n_vertices, int32_t* status, void* workspace, void* stream);
 int64_t p3_init_contours_workspace_bytes(int B, int H, int W);
 
+/* ------------------------------------------------------------------------------------------
+ * FFL corner-aware contour simplification: the array half of `post_process` (predict/ffl/polygonize_acm.py:277-284 and polygonize_asm.py:498-504:
+ * skimage.measure.approximate_polygon, frame_field_utils.detect_corners :71-114 over math_utils.compute_crossfield_uv, polygonize_utils.split_polylines_corner
+ * :47-61, LineString.simplify per piece) on the device.  The planar-graph half (unary_union, polygonize_full, the area / probability filters) stays host code.
+ * Polyline i is the EXPLICIT point sequence q_0 .. q_{n-1} = pos[index[slice[i,0] .. slice[i,1])] (pos[slice ...] when index is NULL), the first point
+ * appended once more when closed[i] is set; coordinates are (row, col).  A polyline with fewer than 2 explicit points gives no piece.
+ *   DP(points, tol): Douglas-Peucker.  The first and last point are kept; in a section (s, e) the distance of point k is |cross(q_k - q_s, d)| / |d| with
+ *      d = q_e - q_s when (q_k - q_s).d > 0 and (q_e - q_k).d > 0, else min(|q_k - q_s|, |q_k - q_e|); if any distance is > tol the point with the largest
+ *      one, the lowest index among equal maxima, is kept and both halves are searched, otherwise the interior is dropped.  tol <= 0 keeps every point.
+ *   A  tol_pre > 0: the polyline becomes DP(explicit points, tol_pre)  (ACM: min(1, tolerance); ASM: 0).
+ *   B  corner mask (detect_corners).  Closed (max |q_0 - q_last| < 1e-6): vertex i < last has the left edge predecessor - q_i (the predecessor of vertex 0 is
+ *      the second-to-last point) and the right edge q_{i+1} - q_i, mask[last] = mask[0].  Open: both ends are corners, interior vertices use q_{i-1} - q_i and
+ *      q_{i+1} - q_i.  At the vertex's pixel (round half to even, clipped into the map) c0 = c0c2[0] + i c0c2[1], c2 = c0c2[2] + i c0c2[3],
+ *      s = sqrt(c2^2 - 4 c0), u = sqrt((c2 + s) / 2), v = sqrt((c2 - s) / 2) (principal roots, computed at the vertices only);
+ *      score(e, w) = |e_row Re w + e_col Im w|, is_u(e) = score(e, v) < score(e, u), corner = is_u(left) != is_u(right).
+ *   C  pieces (split_polylines_corner): without a corner the polyline is one piece; else one piece per pair of consecutive corners, both included, and, when
+ *      neither mask[0] nor mask[last] is set, the merged piece polyline[last corner:] + polyline[:first corner + 1] last.
+ *   D  tol > 0: every piece becomes DP(piece, tol).
+ * Distances and the frame field are evaluated in double.  Outputs, polylines in input order and pieces in the order of C: out_pos fp32 [max_vertices,2] (bit
+ * copies of input positions), out_src int32 [max_vertices] (the point's position inside its explicit polyline), piece_slice int64 [max_pieces,2] = [first,
+ * one past the last) inside out_pos, piece_poly / piece_batch int32 [max_pieces]; stage_flags (NULL or uint8 [E], E = (index ? K : N) + P, the polylines'
+ * explicit points one after the other): bit 0 kept by A, bit 1 corner, bit 2 kept by D in some piece; counts int32 [3] = (vertices, pieces, longest piece);
+ * status int32 [1]: bit 0 = more vertices than max_vertices or more pieces than max_pieces (counts still hold the true totals and nothing is written past
+ * the capacities; 2 E' vertices and E' pieces for E' explicit points can never overflow), bit 1 = overlapping slices hold more than E explicit points (the
+ * polylines past E give no piece).  Every index read from index / slice / poly_batch is clamped.
+ * Polylines of up to 4096 explicit points run in one workgroup each with all working arrays in LDS; longer ones (or all, force_fallback != 0) run the same
+ * device functions over `workspace`.  max_len: an upper bound of slice[i,1] - slice[i,0] that the HOST knows (decides whether the second form is launched
+ * at all; a longer polyline gives no piece), <= 0: unknown.  Two runs, either form, a polyline alone or inside a batch give the same bits; no host
+ * synchronisation.  workspace: p3_corner_split_workspace_bytes(E, P) bytes.  P == 0, N == 0 or an empty index: zero counts without a kernel launch.
+ * ------------------------------------------------------------------------------------------ */
+int p3_corner_split(const float* pos, int64_t N, const int64_t* index, int64_t K, const int64_t* slice, const uint8_t* closed, const int32_t* poly_batch,
+                    int P, const float* c0c2, int B, int H, int W, double tol_pre, double tol, int max_len, int force_fallback, int max_vertices,
+                    int max_pieces, float* out_pos, int32_t* out_src, int64_t* piece_slice, int32_t* piece_poly, int32_t* piece_batch,
+                    uint8_t* stage_flags, int32_t* counts, int32_t* status, void* workspace, void* stream);
+int64_t p3_corner_split_workspace_bytes(int64_t E, int P);
+
 #ifdef __cplusplus
 }
 #endif

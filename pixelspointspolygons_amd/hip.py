@@ -1198,8 +1198,80 @@ def init_contours(indicator, level=0.5, max_vertices=None, max_contours=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------ FFL corner-aware contour simplification
+CS_LDS_CAP = 4096          # csrc/corner_split.hip: explicit points of one polyline that run in LDS
+
+
+def corner_split_device(pos, index, poly_slice, closed, poly_batch, c0c2, tol_pre, tol, max_len=None, force_fallback=False, max_vertices=None,
+                        max_pieces=None, stage_flags=False, _guard=0):
+    """p3_corner_split (the array half of FFL's post_process: approximate_polygon, detect_corners, split_polylines_corner, simplify per piece; DESIGN.md
+    section 14) without any synchronisation.  pos fp32 [N,2] (row, col); index int64 [K] or None; poly_slice [P,2] into index (into pos without index);
+    closed [P] (the first point is appended once more); poly_batch [P] the image of each polyline; c0c2 [B,4,H,W].  tol_pre: stage A (ACM: min(1,
+    tolerance); ASM: 0), tol: stage D.  max_len: longest poly_slice row if the caller knows it, None / <= 0: unknown.
+    -> dict(out_pos f32 [max_vertices,2], out_src i32 [max_vertices], piece_slice i64 [max_pieces,2], piece_poly i32 [max_pieces], piece_batch i32
+    [max_pieces], counts i32 [3] = (vertices, pieces, longest piece), status i32 [1] (bit 0: a capacity was too small; counts are the true totals then and
+    nothing is written past the capacities), stage_flags u8 [(K or N) + P] with stage_flags=True).  The default capacities 2 E and E for E = (K or N) + P
+    explicit points cannot overflow.  _guard: test hook, guard bytes around every output (out["_arenas"])."""
+    for t in (pos, poly_slice, closed, poly_batch, c0c2) + (() if index is None else (index,)):
+        _dev(t)
+    if pos.dtype != torch.float32 or pos.dim() != 2 or pos.shape[1] != 2:
+        raise P3Error(f"corner_split: pos must be float32 [N, 2], got {pos.dtype} {tuple(pos.shape)}")
+    N, P = pos.shape[0], poly_slice.shape[0]
+    if poly_slice.dim() != 2 or poly_slice.shape[1] != 2 or closed.shape[0] != P or poly_batch.shape[0] != P or (index is not None and index.dim() != 1):
+        raise P3Error(f"corner_split: poly_slice [P, 2], closed [P], poly_batch [P], index [K] expected, got {tuple(poly_slice.shape)}, {tuple(closed.shape)}, "
+                      f"{tuple(poly_batch.shape)}")
+    if c0c2.dim() != 4 or c0c2.shape[1] != 4 or min(c0c2.shape) < 1:
+        raise P3Error(f"corner_split: c0c2 [B, 4, H, W] expected, got {tuple(c0c2.shape)}")
+    B, _, H, W = c0c2.shape
+    K = 0 if index is None else index.shape[0]
+    E = (N if index is None else K) + P
+    nv = max(2 * E, 1) if max_vertices is None else int(max_vertices)
+    nq = max(E, 1) if max_pieces is None else int(max_pieces)
+    if nv < 1 or nq < 1:
+        raise P3Error(f"corner_split: max_vertices = {max_vertices}, max_pieces = {max_pieces}")
+    dev, arenas, g = pos.device, [], int(_guard)
+    out = dict(out_pos=_ic_out((nv, 2), torch.float32, dev, g, arenas), out_src=_ic_out((nv,), torch.int32, dev, g, arenas),
+               piece_slice=_ic_out((nq, 2), torch.int64, dev, g, arenas), piece_poly=_ic_out((nq,), torch.int32, dev, g, arenas),
+               piece_batch=_ic_out((nq,), torch.int32, dev, g, arenas), counts=_ic_out((3,), torch.int32, dev, g, arenas),
+               status=_ic_out((1,), torch.int32, dev, g, arenas))
+    if stage_flags:
+        out["stage_flags"] = _ic_out((max(E, 1),), torch.uint8, dev, g, arenas)
+    if g:
+        out["_arenas"] = arenas
+    # converted copies stay referenced until the launch is queued
+    p32, cf = pos.contiguous(), c0c2.contiguous().float()
+    idx = None if index is None else index.to(torch.int64).contiguous()
+    sl, cl, pb = poly_slice.to(torch.int64).contiguous(), closed.to(torch.uint8).contiguous(), poly_batch.to(torch.int32).contiguous()
+    lib().p3_corner_split_workspace_bytes.restype = c_int64
+    ws = workspace(int(lib().p3_corner_split_workspace_bytes(c_int64(E), c_int(P))), dev, "corner_split")
+    check(lib().p3_corner_split(ptr(p32), c_int64(N), ptr(idx), c_int64(K), ptr(sl), ptr(cl), ptr(pb), c_int(P), ptr(cf), c_int(B), c_int(H), c_int(W),
+                                ctypes.c_double(float(tol_pre)), ctypes.c_double(float(tol)), c_int(int(max_len or 0)), c_int(int(bool(force_fallback))),
+                                c_int(nv), c_int(nq), ptr(out["out_pos"]), ptr(out["out_src"]), ptr(out["piece_slice"]), ptr(out["piece_poly"]),
+                                ptr(out["piece_batch"]), ptr(out.get("stage_flags")), ptr(out["counts"]), ptr(out["status"]), ptr(ws), stream()),
+          "p3_corner_split")
+    return out
+
+
+def corner_split(pos, index, poly_slice, closed, poly_batch, c0c2, tol_pre, tol, max_len=None, force_fallback=False, max_vertices=None, max_pieces=None,
+                 stage_flags=False):
+    """the checking form of corner_split_device: reads counts and status once (the only read-back), raises when a capacity was too small and narrows the
+    outputs to what was found: out_pos [V,2], out_src [V], piece_slice [Q,2], piece_poly [Q], piece_batch [Q]; counts = (V, Q, longest piece) as ints."""
+    out = corner_split_device(pos, index, poly_slice, closed, poly_batch, c0c2, tol_pre, tol, max_len, force_fallback, max_vertices, max_pieces, stage_flags)
+    V, Q, longest, status = torch.cat([out["counts"], out["status"]]).tolist()
+    if status & 1:
+        raise P3Error(f"corner_split: {V} vertices in {Q} pieces do not fit max_vertices = {out['out_pos'].shape[0]}, max_pieces = {out['piece_slice'].shape[0]}")
+    if status & 2:
+        raise P3Error("corner_split: the rows of poly_slice overlap: they hold more explicit points than index / pos has entries")
+    for k in ("out_pos", "out_src"):
+        out[k] = out[k][:V]
+    for k in ("piece_slice", "piece_poly", "piece_batch"):
+        out[k] = out[k][:Q]
+    out["counts"] = (V, Q, longest)
+    return out
+
+
 # ------------------------------------------------------------------------------------------ FFL active-skeleton optimiser
-ASM_LDS_CAP = 4096          # csrc/asm.hip: nodes of one connected component that fit the one-launch LDS path
+ASM_LDS_CAP = 4096         # csrc/asm.hip: nodes of one connected component that fit the one-launch LDS path
 ASM_MAX_KNOTS = 8
 
 

@@ -5,7 +5,7 @@ The reference differentiates `data_coef * level_loss + length_coef * total_lengt
 and junction terms are computed and reported but never reach the positions.  They are not built here, and `step()` does not report them.
 
 What stays host code of the caller: skeleton initialisation (`skimage` skeletonize plus `skan`, or marching squares; `contours_to_skeleton` below is the
-conversion half of the latter) in front, and `post_process` (corner split, shapely) behind.
+conversion half of the latter) in front, and the shapely half of `post_process` behind (its corner split is polygonize_post.corner_split_skeleton).
 
 `Skeleton`, `Paths`, `TensorSkeleton`, `skeletons_to_tensorskeleton` and `tensorskeleton_to_skeletons` keep the fields of
 torch_lydorn/torchvision/transforms/tensorskeleton.py: pos [N,2] (row, col), degrees [N], path_index [M], path_delim [P+1], batch [N], batch_delim [B+1],

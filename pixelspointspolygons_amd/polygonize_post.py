@@ -1,0 +1,89 @@
+"""FFL corner-aware contour simplification on the device: the array half of the reference's `post_process` (predict/ffl/polygonize_acm.py:260-284 and
+polygonize_asm.py:498-504) - approximate_polygon, detect_corners over compute_crossfield_uv, split_polylines_corner and LineString.simplify per piece -
+as one call of csrc/corner_split.hip (p3_corner_split) on the optimised `TensorPoly` (ACM) or `TensorSkeleton` (ASM) that never left the GPU.  DESIGN.md
+section 14 holds the definition; Douglas-Peucker is held to a float64 restatement and hand-checkable cases, not to skimage or GEOS.
+
+What stays host code of the caller: the planar-graph half - `LineString(piece[:, ::-1])` per piece, the border ring,
+`shapely.ops.unary_union`, `polygonize_full`, the area / probability filters.  `pieces_to_host` hands it the pieces: a few hundred vertices per batch
+instead of every optimised vertex.
+
+A tolerance list gives a dict keyed "tol_{}", as the reference's shapely_postprocess does."""
+import numpy as np
+import torch
+
+from . import hip, polygonize_acm
+
+
+def _is_list(tolerance):
+    return not isinstance(tolerance, (int, float)) and hasattr(tolerance, "__iter__")
+
+
+def _check(container, crossfield_batch, name):
+    if not container.pos.is_cuda or not crossfield_batch.is_cuda:
+        raise hip.P3Error(f"{name}: the container and crossfield_batch must be on the device (there is no CPU path)")
+    if crossfield_batch.dim() != 4 or crossfield_batch.shape[1] != 4:
+        raise hip.P3Error(f"{name}: crossfield_batch should be (N, 4, H, W), got {tuple(crossfield_batch.shape)}")
+
+
+def corner_split_tensorpoly(tensorpoly, crossfield_batch, tolerance, force_fallback=False, stage_flags=False):
+    """The ACM form (polygonize_acm.py:277-284): a contour whose first vertex is no endpoint is closed (its first point is appended again, as
+    tensorpoly_to_contours_batch does), stage A runs at min(1, tolerance).  -> the trimmed dict of hip.corner_split plus batch_size, or a dict of those
+    keyed "tol_{}" for a tolerance list.  One read-back (counts and status) per tolerance."""
+    _check(tensorpoly, crossfield_batch, "corner_split_tensorpoly")
+    if _is_list(tolerance):
+        return {"tol_{}".format(t): corner_split_tensorpoly(tensorpoly, crossfield_batch, t, force_fallback, stage_flags) for t in tolerance}
+    sl, N = tensorpoly.poly_slice, tensorpoly.pos.shape[0]
+    first = sl[:, 0].clamp(0, max(N - 1, 0)).long()
+    closed = ~tensorpoly.is_endpoint.bool().index_select(0, first) if N else torch.zeros(sl.shape[0], dtype=torch.bool, device=sl.device)
+    poly_batch = tensorpoly.batch.index_select(0, first) if N else torch.zeros(sl.shape[0], dtype=torch.long, device=sl.device)
+    out = hip.corner_split(tensorpoly.pos.detach().float(), None, sl, closed, poly_batch, crossfield_batch, min(1, tolerance), tolerance,
+                           max_len=getattr(tensorpoly, "max_len", None), force_fallback=force_fallback, stage_flags=stage_flags)
+    out["batch_size"] = tensorpoly.batch_size
+    return out
+
+
+def corner_split_skeleton(tensorskeleton, crossfield_batch, tolerance, force_fallback=False, stage_flags=False):
+    """The ASM form (polygonize_asm.py:498-504): the paths of path_index / path_delim as they are (a ring already repeats its node), no stage A."""
+    _check(tensorskeleton, crossfield_batch, "corner_split_skeleton")
+    if _is_list(tolerance):
+        return {"tol_{}".format(t): corner_split_skeleton(tensorskeleton, crossfield_batch, t, force_fallback, stage_flags) for t in tolerance}
+    idx, delim, N = tensorskeleton.path_index.long(), tensorskeleton.path_delim.long(), tensorskeleton.pos.shape[0]
+    P = max(delim.shape[0] - 1, 0)
+    sl = torch.stack([delim[:-1], delim[1:]], 1) if P else torch.zeros((0, 2), dtype=torch.long, device=idx.device)
+    closed = torch.zeros(P, dtype=torch.bool, device=idx.device)
+    if P and N and idx.shape[0]:
+        node = idx.index_select(0, sl[:, 0].clamp(0, idx.shape[0] - 1)).clamp(0, N - 1)          # image of a path = image of its first node
+        poly_batch = tensorskeleton.batch.index_select(0, node)
+    else:
+        poly_batch = torch.zeros(P, dtype=torch.long, device=idx.device)
+    out = hip.corner_split(tensorskeleton.pos.detach().float(), idx, sl, closed, poly_batch, crossfield_batch, 0.0, tolerance, force_fallback=force_fallback,
+                           stage_flags=stage_flags)
+    out["batch_size"] = tensorskeleton.batch_size
+    return out
+
+
+def pieces_to_host(result):
+    """-> per image a list of float64 [n, 2] (row, col) arrays, in the device's order; one download per field.  A "tol_{}" dict gives a dict of those."""
+    if "out_pos" not in result:
+        return {k: pieces_to_host(v) for k, v in result.items()}
+    pos = result["out_pos"].cpu().numpy().astype(np.float64)
+    sl = result["piece_slice"].cpu().numpy()
+    pb = result["piece_batch"].cpu().numpy()
+    out = [[] for _ in range(int(result["batch_size"]))]
+    for (s, e), b in zip(sl, pb):
+        out[int(b)].append(pos[s:e])
+    return out
+
+
+def polygonize_acm_pieces(seg_batch, crossfield_batch, config=polygonize_acm.ACM_DEFAULTS, tolerance=None):
+    """polygonize_acm.polygonize_device followed by the ACM form at config["tolerance"] (or `tolerance`): seg and crossfield on the device -> the pieces on the
+    device.  Without any contour: an empty result (None per tolerance is never returned)."""
+    tolerance = config["tolerance"] if tolerance is None else tolerance
+    tensorpoly = polygonize_acm.polygonize_device(seg_batch, crossfield_batch, config)
+    if tensorpoly is None:
+        dev = seg_batch.device
+        empty = lambda: {"out_pos": torch.zeros((0, 2), dtype=torch.float32, device=dev), "out_src": torch.zeros(0, dtype=torch.int32, device=dev),
+                         "piece_slice": torch.zeros((0, 2), dtype=torch.int64, device=dev), "piece_poly": torch.zeros(0, dtype=torch.int32, device=dev),
+                         "piece_batch": torch.zeros(0, dtype=torch.int32, device=dev), "counts": (0, 0, 0), "batch_size": seg_batch.shape[0]}
+        return {"tol_{}".format(t): empty() for t in tolerance} if _is_list(tolerance) else empty()
+    return corner_split_tensorpoly(tensorpoly, crossfield_batch, tolerance)
