@@ -8,14 +8,17 @@
 //              saves the second barrier an edge pass would need.
 //   fallback   acm_global_kernel: polygons over ACM_LDS_CAP vertices (or all, when forced) ping-pong between `pos` and a workspace copy, one launch per step.
 // Both call acm_vertex(), compiled with floating-point contraction off: the two paths give the same bits, and so do two runs, any split of the steps into
-// calls (first_iter) and any order of the polygons.  No atomics, no host synchronisation.
+// calls (first_iter) and any order of the polygons.  No atomics, no host synchronisation.  The sampling of the two maps (pixel clamp, level term, align term
+// of an edge) and the fixed-order sum of the loss terms are shared with asm.hip: ffl_field.h, which turns contraction off for itself.
 #include "p3_common.h"
+#include "ffl_field.h"
 
 #pragma clang fp contract(off)
 
 #ifndef ACM_THREADS
 #define ACM_THREADS 256           // a multiple of 64; -DACM_THREADS=64 / 128 builds the variants DESIGN.md section 11 compares (tools/build_variant.sh)
 #endif
+#define ACM_EPS 1e-3f             // z = e / (|e| + 1e-3) (polygonize_acm.py:117)
 #define ACM_LDS_CAP 4096          // vertices: 2 buffers x 8 B x 4096 = 64 KiB, the most a workgroup gets without opting in to more dynamic LDS (16 vertices per thread)
 static_assert(ACM_THREADS % 64 == 0 && ACM_LDS_CAP <= 64 * ACM_THREADS, "whole waves, and a thread's endpoint flags fit one word");
 #if ACM_LDS_CAP <= 32 * ACM_THREADS
@@ -40,67 +43,26 @@ __host__ __device__ __forceinline__ float acm_lr(const AcmSched& s, int it) {   
     return (float)(s.poly_lr * coef);
 }
 
-// float coordinate -> pixel index in [0, n-1]; the clamp in float first keeps the conversion defined for any input (NaN lands on 0)
-__device__ __forceinline__ int acm_pix(float v, int n) {
-    const int i = (int)fminf(fmaxf(v, -1.f), (float)n);
-    return min(max(i, 0), n - 1);
-}
-
-// edge a -> b of image `img`: gradient of (wc * align + wl * length) with respect to e = b - a, and the two loss terms
-__device__ __forceinline__ void acm_edge(const AcmFields& f, const float* cf, float ar, float ac, float br, float bc, float& gr, float& gc, float& align,
-                                         float& length) {
-    const float e0 = br - ar, e1 = bc - ac;
-    const int pr = acm_pix(rintf((br + ar) / 2.f), f.H), pc = acm_pix(rintf((bc + ac) / 2.f), f.W);          // round half to even, like torch.round
-    const int64_t hw = (int64_t)f.H * f.W;
-    const float* q = cf + (int64_t)pr * f.W + pc;
-    const float c0r = q[0], c0i = q[hw], c2r = q[2 * hw], c2i = q[3 * hw];
-    const float norm = sqrtf(e0 * e0 + e1 * e1);
-    const float mask = norm < 0.1f ? 0.f : 1.f;
-    const float d = norm + 1e-3f;
-    const float z0 = e0 / d, z1 = e1 / d;
-    const float z2r = z0 * z0 - z1 * z1, z2i = z0 * z1 + z1 * z0;
-    const float z4r = z2r * z2r - z2i * z2i, z4i = z2r * z2i + z2i * z2r;
-    const float fr = z4r + (c2r * z2r - c2i * z2i) + c0r, fi = z4i + (c2r * z2i + c2i * z2r) + c0i;          // f(z) = z^4 + c2 z^2 + c0
-    align = (fr * fr + fi * fi) * mask;
-    const float nm = norm * mask;
-    length = nm * nm;
-    // d|f|^2 / d(re z, im z) = 2 conj(f'(z)) f(z),  f'(z) = 4 z^3 + 2 c2 z
-    const float z3r = z2r * z0 - z2i * z1, z3i = z2r * z1 + z2i * z0;
-    const float pr_ = 4.f * z3r + 2.f * (c2r * z0 - c2i * z1), pi_ = 4.f * z3i + 2.f * (c2r * z1 + c2i * z0);
-    const float gz0 = 2.f * (pr_ * fr + pi_ * fi), gz1 = 2.f * (pr_ * fi - pi_ * fr);
-    // z = e / (|e| + 1e-3):  dz_i / de_j = delta_ij / d - e_i e_j / (|e| d^2), the second term 0 at |e| = 0 (torch.norm's subgradient)
-    const float dot = gz0 * e0 + gz1 * e1;
-    const float k = norm > 0.f ? dot / (norm * d * d) : 0.f;
-    const float ge0 = gz0 / d - k * e0, ge1 = gz1 / d - k * e1;
-    gr = mask * (f.wc * ge0 + f.wl * (2.f * e0));
-    gc = mask * (f.wc * ge1 + f.wl * (2.f * e1));
-}
-
-// One SGD step of one vertex from the positions of its predecessor, itself and its successor (cyclic inside the polygon).  The only place the loss is written
-// down: both kernels call it.
+// One SGD step of one vertex from the positions of its predecessor, itself and its successor (cyclic inside the polygon).  The only place the ACM's loss is
+// put together, from the level and align terms of ffl_field.h: both kernels call it.
 __device__ __forceinline__ AcmVertex acm_vertex(const AcmFields& f, int img, float2 prev, float2 cur, float2 next, bool endpoint, float lr) {
     AcmVertex o;
     const int64_t hw = (int64_t)f.H * f.W;
     const float* ind = f.indicator + (int64_t)img * hw;
     const float* cf = f.c0c2 + (int64_t)img * 4 * hw;
-    // level term: bilinear_interpolate (torch_lydorn/torch/nn/functionnal.py:4-42), x = col, y = row; weights from the unclamped floor, fetches clamped
-    const float y = cur.x, x = cur.y;
-    const float x0 = floorf(x), y0 = floorf(y), x1 = x0 + 1.f, y1 = y0 + 1.f;
-    const int x0i = acm_pix(x0, f.W), x1i = acm_pix(x1, f.W), y0i = acm_pix(y0, f.H), y1i = acm_pix(y1, f.H);
-    const float Ia = ind[(int64_t)y0i * f.W + x0i], Ib = ind[(int64_t)y1i * f.W + x0i], Ic = ind[(int64_t)y0i * f.W + x1i], Id = ind[(int64_t)y1i * f.W + x1i];
-    const float ax = x1 - x, bx = x - x0, ay = y1 - y, by = y - y0;
-    const float val = (ax * ay) * Ia + (ax * by) * Ib + (bx * ay) * Ic + (bx * by) * Id;
-    const float dv = val - f.level;
-    o.level = dv * dv;
-    const float gI = f.wd * (2.f * dv);
-    const float dIdy = (ax * Ib - ax * Ia) + (bx * Id - bx * Ic);
-    const float dIdx = (ay * Ic - ay * Ia) + (by * Id - by * Ib);
-    float gin_r, gin_c, gout_r, gout_c, a_in, l_in;
-    acm_edge(f, cf, prev.x, prev.y, cur.x, cur.y, gin_r, gin_c, a_in, l_in);
-    acm_edge(f, cf, cur.x, cur.y, next.x, next.y, gout_r, gout_c, o.align, o.length);
+    const FflLevel lv = ffl_level(ind, f.H, f.W, f.level, cur);
+    o.level = lv.dv * lv.dv;
+    const float gI = f.wd * (2.f * lv.dv);
+    // per edge: gradient of (wc * align + wl * length) with respect to e = head - tail, length = (|e| mask)^2
+    const FflEdge in = ffl_edge(cf, f.H, f.W, ACM_EPS, prev, cur), out = ffl_edge(cf, f.H, f.W, ACM_EPS, cur, next);
+    const float gin_r = in.mask * (f.wc * in.ge0 + f.wl * (2.f * in.e0)), gin_c = in.mask * (f.wc * in.ge1 + f.wl * (2.f * in.e1));
+    const float gout_r = out.mask * (f.wc * out.ge0 + f.wl * (2.f * out.e0)), gout_c = out.mask * (f.wc * out.ge1 + f.wl * (2.f * out.e1));
+    const float nm = out.norm * out.mask;
+    o.align = out.align;
+    o.length = nm * nm;
     // d/dp_v: the vertex's level term, + the incoming edge's gradient (p_v is its head), - the outgoing edge's (p_v is its tail): always in this order
-    const float g_r = (gI * dIdy + gin_r) - gout_r;
-    const float g_c = (gI * dIdx + gin_c) - gout_c;
+    const float g_r = (gI * lv.dIdy + gin_r) - gout_r;
+    const float g_c = (gI * lv.dIdx + gin_c) - gout_c;
     o.r = endpoint ? cur.x : fmaf(-lr, g_r, cur.x);
     o.c = endpoint ? cur.y : fmaf(-lr, g_c, cur.y);
     return o;
@@ -112,19 +74,6 @@ __device__ __forceinline__ void acm_poly(const int32_t* poly_slice, const int32_
     start = (int)s;
     n = (int)(e - s);
     img = min(max(poly_batch[p], 0), B - 1);
-}
-
-// sums of (align, level, length) over a workgroup in a fixed order: xor butterfly inside a wave, then the waves in index order.  red: 3 * (ACM_THREADS / 64) floats of LDS
-__device__ __forceinline__ void acm_reduce3(float a, float l, float g, float* red, float* out3) {
-    a = wave_sum(a); l = wave_sum(l); g = wave_sum(g);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { red[3 * w] = a; red[3 * w + 1] = l; red[3 * w + 2] = g; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-        for (int i = 0; i < ACM_THREADS / 64; ++i) { s0 += red[3 * i]; s1 += red[3 * i + 1]; s2 += red[3 * i + 2]; }
-        out3[0] = s0; out3[1] = s1; out3[2] = s2;
-    }
 }
 
 // fast path.  Dynamic LDS: 2 * lds_len float2 (>= 64 B).  Polygons longer than lds_len are left to the fallback.
@@ -158,7 +107,7 @@ __global__ __launch_bounds__(ACM_THREADS) void acm_lds_kernel(float2* pos, int64
     for (int v = tid; v < n; v += ACM_THREADS) pos[start + v] = fin[v];
     if (poly_losses) {
         __syncthreads();          // the position buffers are free now: their head holds the wave partials
-        acm_reduce3(s_al, s_lv, s_ln, (float*)acm_sm, poly_losses + 3 * (int64_t)p);
+        ffl_reduce3<ACM_THREADS>(s_al, s_lv, s_ln, (float*)acm_sm, poly_losses + 3 * (int64_t)p);
     }
 }
 
@@ -198,7 +147,7 @@ __global__ __launch_bounds__(ACM_THREADS) void acm_global_finish_kernel(const fl
             s_al += w[0]; s_lv += w[1]; s_ln += w[2];
         }
     }
-    if (poly_losses) acm_reduce3(s_al, s_lv, s_ln, red, poly_losses + 3 * (int64_t)blockIdx.x);
+    if (poly_losses) ffl_reduce3<ACM_THREADS>(s_al, s_lv, s_ln, red, poly_losses + 3 * (int64_t)blockIdx.x);
 }
 
 extern "C" int64_t p3_acm_workspace_bytes(int64_t N) { return N > 0 ? N * (int64_t)(sizeof(float2) + 3 * sizeof(float)) : 0; }

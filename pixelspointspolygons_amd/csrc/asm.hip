@@ -11,7 +11,8 @@
 //              The RMSprop state `sq` is touched by the owning thread alone.
 //   fallback   asm_global_kernel: components over ASM_LDS_CAP nodes (or all, when forced) ping-pong between `pos` and a workspace copy, one launch per step.
 // Both call asm_node(), compiled with floating-point contraction off: the two paths give the same bits, and so do two runs and any split of the steps into
-// calls (first_iter, sq).  No atomics, no host synchronisation.
+// calls (first_iter, sq).  No atomics, no host synchronisation.  The sampling of the two maps (pixel clamp, level term, align term of an edge) and the
+// fixed-order sum of the loss terms are shared with acm.hip: ffl_field.h, which turns contraction off for itself.
 //
 // The plan (built once per skeleton by the host wrapper from path_index / path_delim) lists the nodes component by component ("cn order"):
 //   comp_ptr [C+1]   component c holds cn entries comp_ptr[c] .. comp_ptr[c+1]
@@ -20,10 +21,12 @@
 //   slot_nb  [S,2]   per slot: local index of the node at k - 1 (-1 at a path start) and at k + 1 (-1 at a path end)
 // Every index read from it is clamped, so no malformed plan can address outside pos, sq, the maps or the LDS buffers.
 #include "p3_common.h"
+#include "ffl_field.h"
 
 #pragma clang fp contract(off)
 
 #define ASM_THREADS 256
+#define ASM_EPS 1e-6f             // z = e / (|e| + 1e-6) (polygonize_asm.py:182-201)
 #define ASM_LDS_CAP 4096          // nodes: 2 buffers x 8 B x 4096 = 64 KiB, the most a workgroup gets without opting in to more dynamic LDS
 #define ASM_MAX_KNOTS 8
 static_assert(ASM_THREADS % 64 == 0, "whole waves");
@@ -72,41 +75,10 @@ __host__ __device__ __forceinline__ AsmCoefs asm_coefs(const AsmSched& s, int it
     return c;
 }
 
-// float coordinate -> pixel index in [0, n-1]; the clamp in float first keeps the conversion defined for any input (NaN lands on 0)
-__device__ __forceinline__ int asm_pix(float v, int n) {
-    const int i = (int)fminf(fmaxf(v, -1.f), (float)n);
-    return min(max(i, 0), n - 1);
-}
-
-// edge a -> b: gradient of the masked align term with respect to e = b - a, and the term itself (polygonize_asm.py:182-201)
-__device__ __forceinline__ void asm_edge(const AsmFields& f, const float* cf, float2 a, float2 b, float& ge0, float& ge1, float& align) {
-    const float e0 = b.x - a.x, e1 = b.y - a.y;
-    const int pr = asm_pix(rintf((b.x + a.x) / 2.f), f.H), pc = asm_pix(rintf((b.y + a.y) / 2.f), f.W);          // round half to even, like torch.round
-    const int64_t hw = (int64_t)f.H * f.W;
-    const float* q = cf + (int64_t)pr * f.W + pc;
-    const float c0r = q[0], c0i = q[hw], c2r = q[2 * hw], c2i = q[3 * hw];
-    const float norm = sqrtf(e0 * e0 + e1 * e1);
-    const float mask = norm < 0.1f ? 0.f : 1.f;
-    const float d = norm + 1e-6f;
-    const float z0 = e0 / d, z1 = e1 / d;
-    const float z2r = z0 * z0 - z1 * z1, z2i = z0 * z1 + z1 * z0;
-    const float z4r = z2r * z2r - z2i * z2i, z4i = z2r * z2i + z2i * z2r;
-    const float fr = z4r + (c2r * z2r - c2i * z2i) + c0r, fi = z4i + (c2r * z2i + c2i * z2r) + c0i;          // f(z) = z^4 + c2 z^2 + c0
-    align = (fr * fr + fi * fi) * mask;
-    // d|f|^2 / d(re z, im z) = 2 conj(f'(z)) f(z),  f'(z) = 4 z^3 + 2 c2 z
-    const float z3r = z2r * z0 - z2i * z1, z3i = z2r * z1 + z2i * z0;
-    const float pr_ = 4.f * z3r + 2.f * (c2r * z0 - c2i * z1), pi_ = 4.f * z3i + 2.f * (c2r * z1 + c2i * z0);
-    const float gz0 = 2.f * (pr_ * fr + pi_ * fi), gz1 = 2.f * (pr_ * fi - pi_ * fr);
-    // z = e / (|e| + 1e-6):  dz_i / de_j = delta_ij / d - e_i e_j / (|e| d^2), the second term 0 at |e| = 0 (torch.norm's subgradient)
-    const float dot = gz0 * e0 + gz1 * e1;
-    const float k = norm > 0.f ? dot / (norm * d * d) : 0.f;
-    ge0 = mask * (gz0 / d - k * e0);
-    ge1 = mask * (gz1 / d - k * e1);
-}
-
-// One RMSprop step of one node.  The only place the loss is written down: both kernels call it.  `at(local)` is the position of the component's node
-// `local` before the step; the node's occurrences are the slots s0 .. s1 (already clamped to the slot array), nb0 = asm_first_slot() the neighbours of
-// the first of them (most nodes have one occurrence: the one-launch kernel keeps it in registers across the steps), n the nodes of its component.
+// One RMSprop step of one node.  The only place the ASM's loss is put together, from the level and align terms of ffl_field.h: both kernels call it.
+// `at(local)` is the position of the component's node `local` before the step; the node's occurrences are the slots s0 .. s1 (already clamped to the slot
+// array), nb0 = asm_first_slot() the neighbours of the first of them (most nodes have one occurrence: the one-launch kernel keeps it in registers across
+// the steps), n the nodes of its component.
 template <class At>
 __device__ __forceinline__ AsmNode asm_node(const AsmFields& f, const AsmCoefs& co, int img, bool tip, float2 cur, float2 sq, const int32_t* slot_nb, int64_t s0,
                                             int64_t s1, int2 nb0, int n, At at) {
@@ -114,19 +86,10 @@ __device__ __forceinline__ AsmNode asm_node(const AsmFields& f, const AsmCoefs& 
     const int64_t hw = (int64_t)f.H * f.W;
     const float* ind = f.indicator + (int64_t)img * hw;
     const float* cf = f.c0c2 + (int64_t)img * 4 * hw;
-    // level term: bilinear_interpolate (torch_lydorn/torch/nn/functionnal.py:4-42), x = col, y = row; weights from the unclamped floor, fetches clamped
-    const float y = cur.x, x = cur.y;
-    const float x0 = floorf(x), y0 = floorf(y), x1 = x0 + 1.f, y1 = y0 + 1.f;
-    const int x0i = asm_pix(x0, f.W), x1i = asm_pix(x1, f.W), y0i = asm_pix(y0, f.H), y1i = asm_pix(y1, f.H);
-    const float Ia = ind[(int64_t)y0i * f.W + x0i], Ib = ind[(int64_t)y1i * f.W + x0i], Ic = ind[(int64_t)y0i * f.W + x1i], Id = ind[(int64_t)y1i * f.W + x1i];
-    const float ax = x1 - x, bx = x - x0, ay = y1 - y, by = y - y0;
-    const float val = (ax * ay) * Ia + (ax * by) * Ib + (bx * ay) * Ic + (bx * by) * Id;
-    const float dv = val - f.level;
-    o.level = dv * dv;
-    const float gI = co.wd * (2.f * dv);
-    const float dIdy = (ax * Ib - ax * Ia) + (bx * Id - bx * Ic);
-    const float dIdx = (ay * Ic - ay * Ia) + (by * Id - by * Ib);
-    float g_r = gI * dIdy, g_c = gI * dIdx;
+    const FflLevel lv = ffl_level(ind, f.H, f.W, f.level, cur);
+    o.level = lv.dv * lv.dv;
+    const float gI = co.wd * (2.f * lv.dv);
+    float g_r = gI * lv.dIdy, g_c = gI * lv.dIdx;
     o.align = 0.f; o.length = 0.f;
     // the node's occurrences k in path_index, ascending: + the incoming edge's gradient (the node is its head), - the outgoing edge's (its tail), + the
     // length term's (both neighbours detached, :219-235), always in this order
@@ -134,17 +97,16 @@ __device__ __forceinline__ AsmNode asm_node(const AsmFields& f, const AsmCoefs& 
         const int lp = s == s0 ? nb0.x : slot_nb[2 * s], ln = s == s0 ? nb0.y : slot_nb[2 * s + 1];
         const bool has_p = lp >= 0, has_n = ln >= 0;
         float2 prev = cur, next = cur;
-        float ge0, ge1, al;
         if (has_p) {
             prev = at(min(lp, n - 1));
-            asm_edge(f, cf, prev, cur, ge0, ge1, al);
-            g_r += co.wc * ge0; g_c += co.wc * ge1;
+            const FflEdge e = ffl_edge(cf, f.H, f.W, ASM_EPS, prev, cur);
+            g_r += co.wc * (e.mask * e.ge0); g_c += co.wc * (e.mask * e.ge1);
         }
         if (has_n) {
             next = at(min(ln, n - 1));
-            asm_edge(f, cf, cur, next, ge0, ge1, al);
-            g_r -= co.wc * ge0; g_c -= co.wc * ge1;
-            o.align += al;                                     // an edge is counted once, by its tail
+            const FflEdge e = ffl_edge(cf, f.H, f.W, ASM_EPS, cur, next);
+            g_r -= co.wc * (e.mask * e.ge0); g_c -= co.wc * (e.mask * e.ge1);
+            o.align += e.align;                                // an edge is counted once, by its tail
         }
         if (has_p && has_n) {
             const float p0 = cur.x - prev.x, p1 = cur.y - prev.y, n0 = next.x - cur.x, n1 = next.y - cur.y;
@@ -178,19 +140,6 @@ __device__ __forceinline__ void asm_entry(const AsmPlan& pl, int64_t i, int64_t 
 
 __device__ __forceinline__ int2 asm_first_slot(const AsmPlan& pl, int64_t s0, int64_t s1) {
     return s1 > s0 ? make_int2(pl.slot_nb[2 * s0], pl.slot_nb[2 * s0 + 1]) : make_int2(-1, -1);
-}
-
-// sums of (align, level, length) over a workgroup in a fixed order: xor butterfly inside a wave, then the waves in index order.  red: 3 * (ASM_THREADS / 64) floats of LDS
-__device__ __forceinline__ void asm_reduce3(float a, float l, float g, float* red, float* out3) {
-    a = wave_sum(a); l = wave_sum(l); g = wave_sum(g);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { red[3 * w] = a; red[3 * w + 1] = l; red[3 * w + 2] = g; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-        for (int i = 0; i < ASM_THREADS / 64; ++i) { s0 += red[3 * i]; s1 += red[3 * i + 1]; s2 += red[3 * i + 2]; }
-        out3[0] = s0; out3[1] = s1; out3[2] = s2;
-    }
 }
 
 // fast path.  Dynamic LDS: 2 * lds_len float2 (>= 64 B).  Components larger than lds_len are left to the fallback.
@@ -244,7 +193,7 @@ __global__ __launch_bounds__(ASM_THREADS) void asm_lds_kernel(float2* pos, float
     for (int v = tid; v < n; v += ASM_THREADS) pos[min(max((int64_t)pl.cn_node[start + v], (int64_t)0), N - 1)] = asm_sm[fin + v];
     if (comp_losses) {
         __syncthreads();          // the position buffers are free now: their head holds the wave partials
-        asm_reduce3(s_al, s_lv, s_ln, (float*)asm_sm, comp_losses + 3 * (int64_t)c);
+        ffl_reduce3<ASM_THREADS>(s_al, s_lv, s_ln, (float*)asm_sm, comp_losses + 3 * (int64_t)c);
     }
 }
 
@@ -292,7 +241,7 @@ __global__ __launch_bounds__(ASM_THREADS) void asm_global_finish_kernel(const fl
             s_al += w[0]; s_lv += w[1]; s_ln += w[2];
         }
     }
-    if (comp_losses) asm_reduce3(s_al, s_lv, s_ln, red, comp_losses + 3 * (int64_t)blockIdx.x);
+    if (comp_losses) ffl_reduce3<ASM_THREADS>(s_al, s_lv, s_ln, red, comp_losses + 3 * (int64_t)blockIdx.x);
 }
 
 static bool asm_fill_sched(AsmSched& sc, const double* knots, int nk, double lr, double gamma) {

@@ -119,29 +119,6 @@ __device__ __forceinline__ bool ic_edge(const IcMap& m, int b, const IcEnds& n, 
     return true;
 }
 
-// exclusive scan over the workgroup (whole waves); total = the workgroup's sum.  lds: one T per wave
-template <typename T>
-__device__ __forceinline__ T ic_block_scan(T v, T* lds, T& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    T incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const T t = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) lds[w] = incl;
-    __syncthreads();
-    T base = 0, tot = 0;
-    for (int i = 0; i < nw; ++i) {
-        const T s = lds[i];
-        if (i < w) base += s;
-        tot += s;
-    }
-    __syncthreads();          // lds is free again
-    total = tot;
-    return base + incl - v;
-}
-
 // 1: grid (tiles per image, B).  A thread takes IC_ITEMS consecutive edges: their pixels are loaded before any is looked at
 __global__ __launch_bounds__(IC_THREADS) void ic_count_kernel(IcMap m, int* tile_sums) {
     __shared__ int lds[IC_THREADS / 64];
@@ -156,7 +133,7 @@ __global__ __launch_bounds__(IC_THREADS) void ic_count_kernel(IcMap m, int* tile
         if (first + j < m.E && ic_differ(m, n[j]) && ic_edge(m, b, n[j], e)) ++cnt;
     }
     int total;
-    ic_block_scan<int>(cnt, lds, total);
+    wg_scan<false, int>(cnt, lds, total);
     if (threadIdx.x == 0) tile_sums[b * m.tpe + blockIdx.x] = total;
 }
 
@@ -168,7 +145,7 @@ __global__ __launch_bounds__(IC_SCAN_THREADS) void ic_scan_tiles_kernel(int* sum
         const int i = at + threadIdx.x;
         const int v = i < n ? sums[i] : 0;
         int total;
-        const int ex = ic_block_scan<int>(v, lds, total);
+        const int ex = wg_scan<false, int>(v, lds, total) - v;
         if (i < n) sums[i] = carry + ex;
         carry += total;
     }
@@ -192,7 +169,7 @@ __global__ __launch_bounds__(IC_THREADS) void ic_compact_kernel(IcMap m, const i
         cnt += on[j] ? 1 : 0;
     }
     int total;
-    int v = tile_offs[b * m.tpe + blockIdx.x] + ic_block_scan<int>(cnt, lds, total);
+    int v = tile_offs[b * m.tpe + blockIdx.x] + wg_scan<false, int>(cnt, lds, total) - cnt;
 #pragma unroll
     for (int j = 0; j < IC_ITEMS; ++j) {
         if (first + j < m.E) vertex_of[(int64_t)b * m.E + first + j] = on[j] ? v : -1;
@@ -322,7 +299,7 @@ __global__ __launch_bounds__(IC_THREADS) void ic_key_reduce_kernel(int K, int tp
     for (int o = 32; o > 0; o >>= 1) longest = max(longest, __shfl_xor(longest, o, 64));
     if ((threadIdx.x & 63) == 0) lmax[threadIdx.x >> 6] = longest;
     unsigned long long total;
-    ic_block_scan<unsigned long long>(acc, lds, total);          // its barriers publish lmax too
+    wg_scan<false, unsigned long long>(acc, lds, total);          // its barriers publish lmax too
     if (threadIdx.x == 0) {
         int mx = 0;
         for (int i = 0; i < IC_THREADS / 64; ++i) mx = max(mx, lmax[i]);
@@ -345,7 +322,7 @@ __global__ __launch_bounds__(IC_SCAN_THREADS) void ic_key_scan_tiles_kernel(unsi
         const unsigned long long v = i < n ? sums[i] : 0ull;
         if (i < n) longest = max(longest, tile_max[i]);
         unsigned long long total;
-        const unsigned long long ex = ic_block_scan<unsigned long long>(v, lds, total);
+        const unsigned long long ex = wg_scan<false, unsigned long long>(v, lds, total) - v;
         if (i < n) sums[i] = carry + ex;
         carry += total;
     }
@@ -381,7 +358,7 @@ __global__ __launch_bounds__(IC_THREADS) void ic_key_place_kernel(int K, int tpk
         if (len[j] > 0) mine += ((unsigned long long)len[j] << 32) | 1ull;
     }
     unsigned long long total;
-    unsigned long long at = tile_offs[b * tpk + blockIdx.x] + ic_block_scan<unsigned long long>(mine, lds, total);
+    unsigned long long at = tile_offs[b * tpk + blockIdx.x] + wg_scan<false, unsigned long long>(mine, lds, total) - mine;
 #pragma unroll
     for (int j = 0; j < IC_ITEMS; ++j) {
         if (len[j] <= 0) continue;
@@ -421,7 +398,6 @@ struct IcLayout {
     int64_t o_vertex_of, o_vpos, o_vsucc, o_vpred, o_vkey, o_vimg, o_st_a, o_st_b, o_klen, o_koff, o_kidx, o_esums, o_ksums, o_kmax, bytes;
     int rounds;
 };
-static inline int64_t ic_up(int64_t v) { return (v + 255) & ~(int64_t)255; }
 static IcLayout ic_layout(int B, int H, int W) {
     IcLayout l;
     memset(&l, 0, sizeof l);
@@ -435,20 +411,20 @@ static IcLayout ic_layout(int B, int H, int W) {
     l.rounds = 1;
     while (((int64_t)1 << l.rounds) < l.E) ++l.rounds;
     int64_t at = 0;
-    l.o_vertex_of = at; at += ic_up(l.BE * 4);
-    l.o_vpos = at; at += ic_up(l.BE * 8);
-    l.o_vsucc = at; at += ic_up(l.BE * 4);
-    l.o_vpred = at; at += ic_up(l.BE * 4);
-    l.o_vkey = at; at += ic_up(l.BE * 4);
-    l.o_vimg = at; at += ic_up(l.BE * 4);
-    l.o_st_a = at; at += ic_up(l.BE * 16);          // pass 1 ping-pongs between a and b; pass 2 lives in the one pass 1 did not finish in
-    l.o_st_b = at; at += ic_up(l.BE * 16);
-    l.o_klen = at; at += ic_up(l.BK * 4);
-    l.o_koff = at; at += ic_up(l.BK * 4);
-    l.o_kidx = at; at += ic_up(l.BK * 4);
-    l.o_esums = at; at += ic_up((B * l.tpe + 1) * 4);
-    l.o_ksums = at; at += ic_up((B * l.tpk + 1) * 8);
-    l.o_kmax = at; at += ic_up(B * l.tpk * 4);
+    l.o_vertex_of = at; at += p3_up256(l.BE * 4);
+    l.o_vpos = at; at += p3_up256(l.BE * 8);
+    l.o_vsucc = at; at += p3_up256(l.BE * 4);
+    l.o_vpred = at; at += p3_up256(l.BE * 4);
+    l.o_vkey = at; at += p3_up256(l.BE * 4);
+    l.o_vimg = at; at += p3_up256(l.BE * 4);
+    l.o_st_a = at; at += p3_up256(l.BE * 16);          // pass 1 ping-pongs between a and b; pass 2 lives in the one pass 1 did not finish in
+    l.o_st_b = at; at += p3_up256(l.BE * 16);
+    l.o_klen = at; at += p3_up256(l.BK * 4);
+    l.o_koff = at; at += p3_up256(l.BK * 4);
+    l.o_kidx = at; at += p3_up256(l.BK * 4);
+    l.o_esums = at; at += p3_up256((B * l.tpe + 1) * 4);
+    l.o_ksums = at; at += p3_up256((B * l.tpk + 1) * 8);
+    l.o_kmax = at; at += p3_up256(B * l.tpk * 4);
     l.bytes = at;
     return l;
 }

@@ -98,29 +98,6 @@ __device__ __forceinline__ bool cs_corner(const CsIn& in, const float* cf, float
     return left_is_u != right_is_u;
 }
 
-// inclusive scan over the workgroup (whole waves), sum or maximum; total = over all threads.  red: one T per wave
-template <bool MAX, typename T>
-__device__ __forceinline__ T cs_scan(T v, T* red, T& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const T t = __shfl_up(v, o, 64);
-        if (lane >= o) v = MAX ? (t > v ? t : v) : v + t;
-    }
-    if (lane == 63) red[w] = v;
-    __syncthreads();
-    T tot = red[0], base = red[0];
-    for (int i = 1; i < nw; ++i) {
-        const T s = red[i];
-        tot = MAX ? (s > tot ? s : tot) : tot + s;
-        if (i < w) base = MAX ? (s > base ? s : base) : base + s;
-    }
-    __syncthreads();          // red is free again
-    total = tot;
-    if (w == 0) return v;
-    return MAX ? (base > v ? base : v) : base + v;
-}
-
 // Douglas-Peucker over the sequence entry v -> pt[idx[(v + rot) mod m]], v < V.  The caller set state[] (kept, dead or live) and the section of every live entry.
 __device__ __forceinline__ void cs_dp(const CsWork& w, int V, int m, int rot, double tol) {
 #define CS_PT(v) w.pt[w.idx[(v) + rot >= m ? (v) + rot - m : (v) + rot]]
@@ -180,7 +157,7 @@ __device__ __forceinline__ void cs_polyline(const CsIn& in, const CsWork& w, int
         const int k = at + tid;
         const int f = (k < n && (w.state[k] & CS_KEPT)) ? 1 : 0;
         int total;
-        const int incl = cs_scan<false, int>(f, red, total);
+        const int incl = wg_scan<false, int>(f, red, total);
         if (k < n) w.fl[k] = f;
         if (f) w.idx[m + incl - 1] = k;          // slot <= k, and nothing reads idx here
         m += total;
@@ -225,7 +202,7 @@ __device__ __forceinline__ void cs_polyline(const CsIn& in, const CsWork& w, int
     for (int at = 0; at < V; at += CS_THREADS) {          // s: the last boundary at or before v
         const int v = at + tid;
         int total;
-        const int s = max(carry, cs_scan<true, int>((v < V && w.state[v]) ? v : -1, red, total));
+        const int s = max(carry, wg_scan<true, int>((v < V && w.state[v]) ? v : -1, red, total));
         if (v < V && !w.state[v]) w.se[2 * v] = (uint32_t)s;
         carry = max(carry, total);
     }
@@ -233,7 +210,7 @@ __device__ __forceinline__ void cs_polyline(const CsIn& in, const CsWork& w, int
     for (int at = 0; at < V; at += CS_THREADS) {          // e: the first boundary at or after v, from the far end (V - e, 0 = none)
         const int v = V - 1 - (at + tid);
         int total;
-        const int e = max(carry, cs_scan<true, int>((v >= 0 && w.state[v]) ? V - v : 0, red, total));
+        const int e = max(carry, wg_scan<true, int>((v >= 0 && w.state[v]) ? V - v : 0, red, total));
         if (v >= 0 && !w.state[v]) {
             if (e == 0 || w.se[2 * v] == CS_NONE) w.state[v] = CS_DEAD;          // outside every piece
             else { w.se[2 * v + 1] = (uint32_t)(V - e); if (!(in.tol > 0.0)) w.state[v] = CS_KEPT; }
@@ -253,7 +230,7 @@ __device__ __forceinline__ void cs_polyline(const CsIn& in, const CsWork& w, int
         const int st = v < V ? w.state[v] : 0;
         const int fk = (st & CS_KEPT) ? 1 : 0, fb = (st & CS_BND) ? 1 : 0;
         int tk, tb;
-        const int ik = cs_scan<false, int>(fk, red, tk), ib = cs_scan<false, int>(fb, red, tb);
+        const int ik = wg_scan<false, int>(fk, red, tk), ib = wg_scan<false, int>(fb, red, tb);
         if (fk) {
             const int kb = kept_before + ik - 1, b = bnd_before + ib - 1;          // kept entries before v; index of the last boundary at or before v
             const int j = v + rot >= m ? v + rot - m : v + rot;
@@ -283,7 +260,7 @@ __global__ __launch_bounds__(CS_SCAN_THREADS) void cs_offsets_kernel(CsIn in, in
         int64_t s0; int len = 0, n = 0;
         if (i < in.P) cs_range(in, i, s0, len, n);
         int64_t total;
-        const int64_t incl = cs_scan<false, int64_t>((int64_t)n, red, total);
+        const int64_t incl = wg_scan<false, int64_t>((int64_t)n, red, total);
         if (i < in.P) {
             const bool fits = carry + incl <= in.E;
             exoff[i] = fits ? carry + incl - n : -1;
@@ -342,7 +319,7 @@ __global__ __launch_bounds__(CS_SCAN_THREADS) void cs_scan_kernel(int P, const i
         unsigned long long v = 0;
         if (i < P) { v = ((unsigned long long)(uint32_t)pcount[4 * (int64_t)i] << 32) | (uint32_t)pcount[4 * (int64_t)i + 1]; longest = max(longest, pcount[4 * (int64_t)i + 2]); }
         unsigned long long total;
-        const unsigned long long incl = cs_scan<false, unsigned long long>(v, red, total);
+        const unsigned long long incl = wg_scan<false, unsigned long long>(v, red, total);
         if (i < P) ooff[i] = carry + incl - v;
         carry += total;
     }
@@ -388,26 +365,25 @@ __global__ __launch_bounds__(CS_THREADS) void cs_emit_kernel(CsIn in, CsStage st
 
 // ---------------------------------------------------------------------------------------------------------------- workspace
 struct CsLayout { int64_t o_exoff, o_flag, o_pcount, o_ooff, o_src, o_piece, o_flags, o_pt, o_idx, o_se, o_key, o_state, o_mask, bytes; };
-static inline int64_t cs_up(int64_t v) { return (v + 255) & ~(int64_t)255; }
 static CsLayout cs_layout(int64_t E, int P) {
     CsLayout l;
     memset(&l, 0, sizeof l);
     if (E < 1 || P < 1) return l;
     const int64_t E1 = E + (int64_t)CS_PAD * P;
     int64_t at = 0;
-    l.o_exoff = at; at += cs_up(((int64_t)P + 1) * 8);
-    l.o_flag = at; at += cs_up(4);
-    l.o_pcount = at; at += cs_up((int64_t)P * 16);
-    l.o_ooff = at; at += cs_up((int64_t)P * 8);
-    l.o_src = at; at += cs_up(2 * E * 4);
-    l.o_piece = at; at += cs_up(E * 8);
-    l.o_flags = at; at += cs_up(E);
-    l.o_pt = at; at += cs_up(E * 8);
-    l.o_idx = at; at += cs_up(E * 4);
-    l.o_se = at; at += cs_up(E1 * 8);
-    l.o_key = at; at += cs_up(E1 * 8);
-    l.o_state = at; at += cs_up(E1);
-    l.o_mask = at; at += cs_up(E);
+    l.o_exoff = at; at += p3_up256(((int64_t)P + 1) * 8);
+    l.o_flag = at; at += p3_up256(4);
+    l.o_pcount = at; at += p3_up256((int64_t)P * 16);
+    l.o_ooff = at; at += p3_up256((int64_t)P * 8);
+    l.o_src = at; at += p3_up256(2 * E * 4);
+    l.o_piece = at; at += p3_up256(E * 8);
+    l.o_flags = at; at += p3_up256(E);
+    l.o_pt = at; at += p3_up256(E * 8);
+    l.o_idx = at; at += p3_up256(E * 4);
+    l.o_se = at; at += p3_up256(E1 * 8);
+    l.o_key = at; at += p3_up256(E1 * 8);
+    l.o_state = at; at += p3_up256(E1);
+    l.o_mask = at; at += p3_up256(E);
     l.bytes = at;
     return l;
 }

@@ -45,6 +45,29 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// inclusive scan over the workgroup (whole waves), sum or maximum; total = over all threads.  red: one T per wave.  The exclusive sum is the result - v.
+template <bool MAX, typename T>
+__device__ __forceinline__ T wg_scan(T v, T* red, T& total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T t = __shfl_up(v, o, 64);
+        if (lane >= o) v = MAX ? (t > v ? t : v) : v + t;
+    }
+    if (lane == 63) red[w] = v;
+    __syncthreads();
+    T tot = red[0], base = red[0];
+    for (int i = 1; i < nw; ++i) {
+        const T s = red[i];
+        tot = MAX ? (s > tot ? s : tot) : tot + s;
+        if (i < w) base = MAX ? (s > base ? s : base) : base + s;
+    }
+    __syncthreads();          // red is free again
+    total = tot;
+    if (w == 0) return v;
+    return MAX ? (base > v ? base : v) : base + v;
+}
+
 // ---- counter-based dropout (p3_dropout) ---------------------------------------------------------------------------------
 // Element (row, col) of a site: bits = hash32(rowkey(row) ^ colkey(col >> 1)), 16 bits per element (low half: even col, high half:
 // odd col); kept iff bits16 >= p * 65536.  A lane that owns one row (attention fwd / dQ, GEMM epilogue) pays one 2-multiply hash
@@ -129,6 +152,7 @@ __device__ __forceinline__ void p3_commit(float* out, float* slab, int n, int id
 }
 
 static inline int p3_ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+static inline int64_t p3_up256(int64_t v) { return (v + 255) & ~(int64_t)255; }          // workspace sections start on 256-byte boundaries
 
 void p3_set_error(const char* msg);
 int p3_tracing(void);                     // p3_trace_kernels(1): launch sites record the kernel they picked (p3_last_kernel)

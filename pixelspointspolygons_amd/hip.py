@@ -1089,6 +1089,15 @@ def hisup_val_loss(jloc, joff, mask, afm_pred, remask, t_jloc, t_joff, t_mask, t
 ACM_LDS_CAP = 4096          # csrc/acm.hip: vertices of one polygon that fit the one-launch LDS path
 
 
+def _ffl_maps(who, indicator, c0c2):
+    """indicator [B,H,W] or seg [B,C,H,W] (channel 0 is taken) and c0c2 [B,4,H,W] -> contiguous fp32 copies and (B, H, W)"""
+    if indicator.dim() == 4:
+        indicator = indicator[:, 0]
+    if indicator.dim() != 3 or c0c2.dim() != 4 or c0c2.shape[1] != 4 or (c0c2.shape[0],) + tuple(c0c2.shape[2:]) != tuple(indicator.shape):
+        raise P3Error(f"{who}: indicator [B, H, W] and c0c2 [B, 4, H, W] expected, got {tuple(indicator.shape)}, {tuple(c0c2.shape)}")
+    return indicator.contiguous().float(), c0c2.contiguous().float(), tuple(indicator.shape)
+
+
 def acm_optimize(pos, poly_slice, batch, is_endpoint, indicator, c0c2, data_coef, length_coef, crossfield_coef, data_level=0.5, poly_lr=0.01,
                  warmup_iters=100, warmup_factor=0.1, first_iter=0, steps=500, losses=False, force_fallback=False, max_len=None):
     """p3_acm_optimize (predict/ffl/polygonize_acm.py:77-220): `steps` SGD iterations first_iter .. first_iter + steps - 1 on pos fp32 [N,2] (row, col), IN PLACE.
@@ -1104,12 +1113,7 @@ def acm_optimize(pos, poly_slice, batch, is_endpoint, indicator, c0c2, data_coef
     N, P = pos.shape[0], poly_slice.shape[0]
     if poly_slice.dim() != 2 or poly_slice.shape[1] != 2 or batch.shape[0] != N or is_endpoint.shape[0] != N:
         raise P3Error(f"acm_optimize: poly_slice [P, 2], batch [N], is_endpoint [N] expected, got {tuple(poly_slice.shape)}, {tuple(batch.shape)}, {tuple(is_endpoint.shape)}")
-    if indicator.dim() == 4:
-        indicator = indicator[:, 0]
-    if indicator.dim() != 3 or c0c2.dim() != 4 or c0c2.shape[1] != 4 or (c0c2.shape[0],) + tuple(c0c2.shape[2:]) != tuple(indicator.shape):
-        raise P3Error(f"acm_optimize: indicator [B, H, W] and c0c2 [B, 4, H, W] expected, got {tuple(indicator.shape)}, {tuple(c0c2.shape)}")
-    B, H, W = indicator.shape
-    ind, cf = indicator.contiguous().float(), c0c2.contiguous().float()
+    ind, cf, (B, H, W) = _ffl_maps("acm_optimize", indicator, c0c2)
     out = torch.zeros((P, 3), dtype=torch.float32, device=pos.device) if losses else None          # zeros: a polygon longer than a wrong max_len is skipped, row and all
     if P == 0 or N == 0 or steps == 0:
         return (pos, out) if losses else pos
@@ -1309,13 +1313,8 @@ def asm_optimize(pos, sq, plan, is_tip, batch, indicator, c0c2, knots, data_leve
     if is_tip.shape[0] != N or batch.shape[0] != N or plan.cn_occ.shape[0] != CN + 1 or plan.slot_nb.dim() != 2 or plan.slot_nb.shape[1] != 2 or C < 0:
         raise P3Error(f"asm_optimize: is_tip [N], batch [N] and a plan with cn_occ [CN+1], slot_nb [S,2] expected, got {tuple(is_tip.shape)}, {tuple(batch.shape)}, "
                       f"{tuple(plan.cn_occ.shape)}, {tuple(plan.slot_nb.shape)}")
-    if indicator.dim() == 4:
-        indicator = indicator[:, 0]
-    if indicator.dim() != 3 or c0c2.dim() != 4 or c0c2.shape[1] != 4 or (c0c2.shape[0],) + tuple(c0c2.shape[2:]) != tuple(indicator.shape):
-        raise P3Error(f"asm_optimize: indicator [B, H, W] and c0c2 [B, 4, H, W] expected, got {tuple(indicator.shape)}, {tuple(c0c2.shape)}")
-    B, H, W = indicator.shape
+    ind, cf, (B, H, W) = _ffl_maps("asm_optimize", indicator, c0c2)
     arr, nk = _asm_knots(knots)
-    ind, cf = indicator.contiguous().float(), c0c2.contiguous().float()
     out = torch.zeros((max(C, 0), 3), dtype=torch.float32, device=pos.device) if losses else None
     if C <= 0 or N == 0 or steps == 0:
         return (pos, out) if losses else pos

@@ -152,14 +152,19 @@ class TensorPolyOptimizer:
         return self.tensorpoly
 
 
-def optimize_contours(seg_batch, crossfield_batch, init_contours_batch, config=ACM_DEFAULTS):
-    """Lines 383-398 of the reference's polygonize(): initial contours per image -> optimised contours per image (same structure, closed ones closed again).
-    seg_batch [B, C, H, W] (channel 0 is the indicator) and crossfield_batch [B, 4, H, W] on the device."""
+def _check_maps(who, seg_batch, crossfield_batch):
+    """the reference's assertions on the two maps (polygonize_acm.py:339-343, polygonize_asm.py:718-722), and: both on the device"""
     assert len(seg_batch.shape) == 4 and seg_batch.shape[1] <= 3, "seg_batch should be (N, C, H, W) with C <= 3, not {}".format(seg_batch.shape)
     assert len(crossfield_batch.shape) == 4 and crossfield_batch.shape[1] == 4, "crossfield_batch should be (N, 4, H, W)"
     assert seg_batch.shape[0] == crossfield_batch.shape[0], "Batch size for seg and crossfield should match"
     if not seg_batch.is_cuda or not crossfield_batch.is_cuda:
-        raise hip.P3Error("optimize_contours: seg_batch and crossfield_batch must be device tensors (there is no CPU path)")
+        raise hip.P3Error(f"{who}: seg_batch and crossfield_batch must be device tensors (there is no CPU path)")
+
+
+def optimize_contours(seg_batch, crossfield_batch, init_contours_batch, config=ACM_DEFAULTS):
+    """Lines 383-398 of the reference's polygonize(): initial contours per image -> optimised contours per image (same structure, closed ones closed again).
+    seg_batch [B, C, H, W] (channel 0 is the indicator) and crossfield_batch [B, 4, H, W] on the device."""
+    _check_maps("optimize_contours", seg_batch, crossfield_batch)
     tensorpoly = contours_batch_to_tensorpoly(init_contours_batch)
     if tensorpoly is None:
         return [[] for _ in init_contours_batch]
@@ -187,11 +192,7 @@ def init_contours(seg_or_indicator, level=0.5):
 def polygonize_device(seg_batch, crossfield_batch, config=ACM_DEFAULTS):
     """Lines 346-398 of the reference's polygonize() without a host contour: initial contours at config["data_level"] and the optimiser, both on the device.
     -> the optimised device TensorPoly (tensorpoly_to_contours_batch hands it to the shapely stage), None without any contour."""
-    assert len(seg_batch.shape) == 4 and seg_batch.shape[1] <= 3, "seg_batch should be (N, C, H, W) with C <= 3, not {}".format(seg_batch.shape)
-    assert len(crossfield_batch.shape) == 4 and crossfield_batch.shape[1] == 4, "crossfield_batch should be (N, 4, H, W)"
-    assert seg_batch.shape[0] == crossfield_batch.shape[0], "Batch size for seg and crossfield should match"
-    if not seg_batch.is_cuda or not crossfield_batch.is_cuda:
-        raise hip.P3Error("polygonize_device: seg_batch and crossfield_batch must be device tensors (there is no CPU path)")
+    _check_maps("polygonize_device", seg_batch, crossfield_batch)
     tensorpoly = init_contours(seg_batch, config["data_level"])
     if tensorpoly is None:
         return None

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import hip
+from .polygonize_acm import _check_maps
 
 # config/polygonization/asm_acm.yaml, asm_method
 ASM_DEFAULTS = {
@@ -297,11 +298,7 @@ class TensorSkeletonOptimizer:
 def optimize_skeletons(seg_batch, crossfield_batch, skeletons_batch, config=ASM_DEFAULTS):
     """Lines 731-752 of PolygonizerASM.__call__: initial skeletons per image -> optimised polylines per image ([n, 2] float32 arrays, one per path); empty
     lists when no image has a path.  seg_batch [B, C, H, W] (channel 0 is the indicator) and crossfield_batch [B, 4, H, W] on the device."""
-    assert len(seg_batch.shape) == 4 and seg_batch.shape[1] <= 3, "seg_batch should be (N, C, H, W) with C <= 3, not {}".format(seg_batch.shape)
-    assert len(crossfield_batch.shape) == 4 and crossfield_batch.shape[1] == 4, "crossfield_batch should be (N, 4, H, W)"
-    assert seg_batch.shape[0] == crossfield_batch.shape[0], "Batch size for seg and crossfield should match"
-    if not seg_batch.is_cuda or not crossfield_batch.is_cuda:
-        raise hip.P3Error("optimize_skeletons: seg_batch and crossfield_batch must be device tensors (there is no CPU path)")
+    _check_maps("optimize_skeletons", seg_batch, crossfield_batch)
     tensorskeleton = skeletons_to_tensorskeleton(skeletons_batch)
     if tensorskeleton.num_paths == 0:
         return [[] for _ in range(seg_batch.shape[0])]
