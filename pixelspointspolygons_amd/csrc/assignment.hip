@@ -134,23 +134,6 @@ extern "C" int p3_assignment(const float* scores, int B, int N, int maximize, in
     const size_t lds_max = 160 * 1024;
     P3_CHECK(aux <= lds_max, P3_ESHAPE, "p3_assignment: N too large (dual variables must fit 160 KB of LDS)");
     hipStream_t s = (hipStream_t)stream;
-    if (full <= lds_max) {
-        static bool attr_set = false;
-        if (!attr_set) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lsap_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
-            if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
-            attr_set = true;
-        }
-        hipLaunchKernelGGL((lsap_kernel<true>), dim3(B), dim3(64), full, s, scores, N, maximize, col4row, perm, status);
-    } else {
-        static bool attr_set = false;
-        if (!attr_set && aux > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lsap_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
-            if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
-            attr_set = true;
-        }
-        hipLaunchKernelGGL((lsap_kernel<false>), dim3(B), dim3(64), aux, s, scores, N, maximize, col4row, perm, status);
-    }
-    P3_LAUNCH_CHECK();
-    return P3_OK;
+    if (full <= lds_max) return p3_launch<lsap_kernel<true>>(nullptr, dim3(B), dim3(64), full, s, scores, N, maximize, col4row, perm, status);
+    return p3_launch<lsap_kernel<false>>(nullptr, dim3(B), dim3(64), aux, s, scores, N, maximize, col4row, perm, status);
 }

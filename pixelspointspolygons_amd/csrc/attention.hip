@@ -543,32 +543,16 @@ extern "C" int p3_attention(const void* Q, const void* K, const void* V, void* O
         P3_LAUNCH_CHECK();
         return P3_OK;
     }
-    // fp32x3 at head dim 32: raw fp32 images of the K and V tile in dynamic LDS (2 x 8 KB; the attribute below also covers the diagnostic padding)
+    // fp32x3 at head dim 32: raw fp32 images of the K and V tile in dynamic LDS (2 x 8 KB, plus the diagnostic padding)
     size_t dyn = d->dtype == P3_F32X3 && d->head_dim == 32 ? (size_t)2 * ATr<f32s, 32>::KT * 32 * 4 : 0;
     static int pad_lds = -1;              // P3_ATTN_PAD_LDS=<bytes> (diagnostic): extra dynamic LDS per workgroup of the fp32x3 kernels - 40000 leaves ONE workgroup per CU
     if (pad_lds < 0) { const char* e = getenv("P3_ATTN_PAD_LDS"); pad_lds = e ? atoi(e) : 0; }
     if (d->dtype == P3_F32X3) dyn += (size_t)pad_lds;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<f32s, 64, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 64 * 64 * 4 + pad_lds);
-        (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<f32s, 64, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 64 * 64 * 4 + pad_lds);
-        (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<f32s, 32, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 64 * 64 * 4 + pad_lds);
-        (void)hipFuncSetAttribute((const void*)attn_fwd_kernel<f32s, 32, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 64 * 64 * 4 + pad_lds);
-        attr_set = true;
-    }
-#define P3_ATTN_FWD(T, D)                                                                                   \
-    do {                                                                                                    \
-        if (drop) hipLaunchKernelGGL((attn_fwd_kernel<T, D, true>), grid, block, dyn, s, a);                \
-        else hipLaunchKernelGGL((attn_fwd_kernel<T, D, false>), grid, block, dyn, s, a);                    \
-    } while (0)
-    if (d->dtype == P3_BF16) {
-        if (d->head_dim == 64) P3_ATTN_FWD(bf16_t, 64); else P3_ATTN_FWD(bf16_t, 32);
-    } else if (d->dtype == P3_F32X3) {                   // fp32x3 mode: bf16 x 3 products on split images (attn_tile.h)
-        if (d->head_dim == 64) P3_ATTN_FWD(f32s, 64); else P3_ATTN_FWD(f32s, 32);
-    } else {
-        if (d->head_dim == 64) P3_ATTN_FWD(float, 64); else P3_ATTN_FWD(float, 32);
-    }
+#define P3_ATTN_FWD(T, D)                                                                  \
+    (drop ? p3_launch<attn_fwd_kernel<T, D, true>>(nullptr, grid, block, dyn, s, a)        \
+          : p3_launch<attn_fwd_kernel<T, D, false>>(nullptr, grid, block, dyn, s, a))
+    if (d->dtype == P3_F32X3) return d->head_dim == 64 ? P3_ATTN_FWD(f32s, 64) : P3_ATTN_FWD(f32s, 32);      // fp32x3 mode: bf16 x 3 products on split images (attn_tile.h)
+    if (d->dtype == P3_BF16) return d->head_dim == 64 ? P3_ATTN_FWD(bf16_t, 64) : P3_ATTN_FWD(bf16_t, 32);
+    return d->head_dim == 64 ? P3_ATTN_FWD(float, 64) : P3_ATTN_FWD(float, 32);
 #undef P3_ATTN_FWD
-    P3_LAUNCH_CHECK();
-    return P3_OK;
 }

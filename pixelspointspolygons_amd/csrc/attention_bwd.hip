@@ -593,32 +593,13 @@ int launch_bwd(const BwdArgs& a, hipStream_t s) {
     const dim3 gq(p3_ceil_div(d.Lq, 128) * d.H * d.B), gk(p3_ceil_div(d.Lk, 128) * d.H * d.B), blk(256);
     // fp32x3: the raw fp32 images of the two staged operands in dynamic LDS (with the 32 KB of bf16 images above the 64 KB a kernel gets without asking for D = 64)
     const size_t dyn = Kind<T>::X3 ? (size_t)2 * 64 * D * 4 : 0;
-    if constexpr (Kind<T>::X3 && D == 64) {
-        static bool attr_set = false;
-        if (!attr_set) {
-            (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<T, D, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-            (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<T, D, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-            (void)hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<T, D, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-            (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<T, D, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-            (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<T, D, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-            (void)hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<T, D, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
-            attr_set = true;
-        }
-    }
-    if (d.drop.seed != nullptr && d.drop.p > 0.f) {
-        if (d.drop_rows) {
-            hipLaunchKernelGGL((attn_bwd_dq_kernel<T, D, 2>), gq, blk, dyn, s, a);
-            hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, D, 2>), gk, blk, dyn, s, a);
-        } else {
-            hipLaunchKernelGGL((attn_bwd_dq_kernel<T, D, 1>), gq, blk, dyn, s, a);
-            hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, D, 1>), gk, blk, dyn, s, a);
-        }
-    } else {
-        hipLaunchKernelGGL((attn_bwd_dq_kernel<T, D, 0>), gq, blk, dyn, s, a);
-        hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, D, 0>), gk, blk, dyn, s, a);
-    }
-    P3_LAUNCH_CHECK();
-    return P3_OK;
+    auto both = [&](auto mode) {                       // mode: 0 no dropout, 1 dropout, 2 dropout with the kept rows recorded
+        constexpr int MODE = decltype(mode)::value;
+        const int rc = p3_launch<attn_bwd_dq_kernel<T, D, MODE>>(nullptr, gq, blk, dyn, s, a);
+        return rc != P3_OK ? rc : p3_launch<attn_bwd_dkv_kernel<T, D, MODE>>(nullptr, gk, blk, dyn, s, a);
+    };
+    if (d.drop.seed != nullptr && d.drop.p > 0.f) return d.drop_rows ? both(std::integral_constant<int, 2>{}) : both(std::integral_constant<int, 1>{});
+    return both(std::integral_constant<int, 0>{});
 }
 
 }  // namespace

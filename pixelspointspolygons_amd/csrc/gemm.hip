@@ -788,12 +788,6 @@ int launch_mode(const GemmArgs& g, hipStream_t s) {
 
 // gemm_dma.hip: LDS-DMA kernels for the plain bf16 products (variant 4: 128 x 128 tile, 64-deep slices, two in LDS; 6: 32-deep, two = 4 workgroups / CU;
 // 9: 128 x 384 tile, 8 waves)
-int p3_rows_gemm_try(const void* A, const void* W, void* C, const p3_gemm_desc* d, hipStream_t s);   // rows_gemm.hip: 0x7fffffff = not one of its shapes
-int p3_pair_fwd_try(const void* U, const void* W, void* C, const p3_gemm_desc* d, hipStream_t s);    // pair_fwd_mma.hip: same convention
-int p3_pair_fwd_x3_try(const void* U, const void* W, void* C, const p3_gemm_desc* d, hipStream_t s); // pair_fwd_x3.hip: the P3_F32X3 form
-int p3_rows_x3_try(const void* A, const void* W, void* C, const p3_gemm_desc* d, hipStream_t s);     // rows_x3.hip: conv3 forward, P3_F32X3
-int p3_gemm_dma_eligible(const p3_gemm_desc* d, const void* A, const void* W, const void* C);
-int p3_gemm_dma_launch(const void* A, const void* W, void* C, const p3_gemm_desc* d, int variant, hipStream_t s);
 static int gemm_dma_mode() { static int m = -1; if (m < 0) { const char* e = getenv("P3_GEMM_DMA"); m = (e && e[0] == '0') ? 0 : 1; } return m; }
 
 extern "C" int p3_gemm_dma(const void* A, const void* W, void* C, const p3_gemm_desc* d, int variant, void* stream) {
@@ -850,18 +844,13 @@ extern "C" int p3_gemm(const void* A, const void* W, void* C, const p3_gemm_desc
         g.vec_epi = ok ? 1 : 0;
     }
     hipStream_t s = (hipStream_t)stream;
-    {   // the ScoreNet's thin 1x1 convolutions over millions of rows: weight-stationary streaming kernels (rows_gemm.hip); its conv2 over the pair
-        // grid: pair_fwd_mma.hip
-        int rc = d->w_lo ? 0x7fffffff : p3_rows_gemm_try(A, W, C, d, s);
-        if (rc != 0x7fffffff) return rc;
-        rc = d->w_lo ? 0x7fffffff : p3_pair_fwd_try(A, W, C, d, s);
-        if (rc != 0x7fffffff) return rc;
-        if (split && !d->w_lo) {
-            rc = p3_pair_fwd_x3_try(A, W, C, d, s);
-            if (rc != 0x7fffffff) return rc;
-            rc = p3_rows_x3_try(A, W, C, d, s);
-            if (rc != 0x7fffffff) return rc;
-        }
+    if (!d->w_lo) {   // the ScoreNet's thin 1x1 convolutions over millions of rows: weight-stationary streaming kernels (rows_gemm.hip); its conv2 over the pair
+        // grid: pair_fwd_mma.hip.  P3_SKIP = not the hook's shape: ask the next one, then go on with the tile kernels below
+        int rc = p3_rows_gemm_try(A, W, C, d, s);
+        if (rc == P3_SKIP) rc = p3_pair_fwd_try(A, W, C, d, s);
+        if (rc == P3_SKIP && split) rc = p3_pair_fwd_x3_try(A, W, C, d, s);
+        if (rc == P3_SKIP && split) rc = p3_rows_x3_try(A, W, C, d, s);
+        if (rc != P3_SKIP) return rc;
     }
     if (gemm_dma_mode() > 0 && d->M >= 2048 && p3_gemm_dma_eligible(d, A, W, C)) {
         // P3_GEMM_DMA=0 switches the rule off (everything on the register-staged kernel).  The rule (r03, tools/mb_gemm_shapes.py + same-box A/B of the

@@ -31,7 +31,6 @@ struct GDArgs {
     int ablate;                 // diagnostic (-DP3_GD_DIAG build, P3_GD_ABLATE): 1 no C / aux stores, 2 no MFMAs, 4 only the first slices are loaded
 };
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ float gd_act_grad(float x, int act) {
     if (act == P3_ACT_MUL) return x;

@@ -561,18 +561,6 @@ extern "C" int p3_tn_flush(void* stream) {
     P3_LAUNCH_CHECK();
     return P3_OK;
 }
-int p3_gemm_tn_dma_try(const void* A, const void* B, float* C, int M, int N, int K, int lda, int ldb, int ldc, float* colsum, float* slabs, int max_slabs,
-                       hipStream_t s);      // gemm_tn_dma.hip
-
-int p3_pair_dw_try(const void* A, const void* U, float* C, int M, int N, int K, int lda, int ldb, int ldc, const float* scale, const float* shift,
-                   const void* pair_V, int pair_n, float* slabs, int max_slabs, hipStream_t s);      // pair_dw_mma.hip
-
-int p3_mask2_dw_try(const void* A, const void* B, float* C, int M, int N, int Kb, int lda, int ldb, int ldc, const float* scale, const float* shift,
-                    float* slabs, int max_slabs, hipStream_t s);      // mask2_dw_mma.hip
-int p3_mask2_dw_x3_try(const void* A, const void* B, float* C, int M, int N, int Kb, int lda, int ldb, int ldc, const float* scale, const float* shift,
-                       float* slabs, int max_slabs, hipStream_t s);      // mask2_dw_x3.hip: the P3_F32X3 form
-int p3_pair_dw_x3_try(const void* A, const void* U, float* C, int M, int N, int K, int lda, int ldb, int ldc, const float* scale, const float* shift,
-                      const void* pair_V, int pair_n, float* slabs, int max_slabs, hipStream_t s);   // pair_dw_x3.hip: the P3_F32X3 form
 
 extern "C" int p3_gemm_tn_ex(const void* A, const void* B, float* C, int M, int N, int K, int lda, int ldb, int ldc, int dtype_in, int b_mode,
                              const float* b_scale, const float* b_shift, const void* pair_V, int pair_n, float* colsum, float* slabs, int max_slabs, void* stream) {
@@ -588,25 +576,17 @@ extern "C" int p3_gemm_tn_ex(const void* A, const void* B, float* C, int M, int 
     const int vec = dtype == P3_BF16 ? 8 : 4;
     P3_CHECK(N % vec == 0 && K % vec == 0 && lda % vec == 0 && ldb % vec == 0, P3_EALIGN, "p3_gemm_tn: N, K, lda, ldb must be multiples of 8 (bf16) / 4 (f32)");
     P3_CHECK(((uintptr_t)A % 16) == 0 && ((uintptr_t)B % 16) == 0, P3_EALIGN, "p3_gemm_tn: 16-byte base alignment");
-    if (dtype == P3_BF16 && b_mode == 0) {          // the plain bf16 weight gradients at 64 / 128-aligned shapes: LDS-DMA kernel (gemm_tn_dma.hip)
-        const int rc = p3_gemm_tn_dma_try(A, B, C, M, N, K, lda, ldb, ldc, colsum, slabs, max_slabs, (hipStream_t)stream);
-        if (rc != 1) return rc;
-    }
-    if (dtype == P3_BF16 && b_mode == P3_A_PAIR_AFFINE_RELU && !colsum) {      // the ScoreNet's conv2 weight gradient: pair_dw_mma.hip
-        const int rc = p3_pair_dw_try(A, B, C, M, N, K, lda, ldb, ldc, b_scale, b_shift, pair_V, pair_n, slabs, max_slabs, (hipStream_t)stream);
-        if (rc != 1) return rc;
-    }
-    if (split && b_mode == P3_A_PAIR_AFFINE_RELU && !colsum) {                     // the same launch with fp32 operands, products as bf16 x 3: pair_dw_x3.hip
-        const int rc = p3_pair_dw_x3_try(A, B, C, M, N, K, lda, ldb, ldc, b_scale, b_shift, pair_V, pair_n, slabs, max_slabs, (hipStream_t)stream);
-        if (rc != 1) return rc;
-    }
-    if (dtype == P3_BF16 && b_mode == P3_A_AFFINE_MASK2 && !colsum) {             // conv3's dual-operand weight gradient: mask2_dw_mma.hip
-        const int rc = p3_mask2_dw_try(A, B, C, M, N, K, lda, ldb, ldc, b_scale, b_shift, slabs, max_slabs, (hipStream_t)stream);
-        if (rc != 1) return rc;
-    }
-    if (split && b_mode == P3_A_AFFINE_MASK2 && !colsum) {                        // fp32 operands, products as bf16 x 3: mask2_dw_x3.hip
-        const int rc = p3_mask2_dw_x3_try(A, B, C, M, N, K, lda, ldb, ldc, b_scale, b_shift, slabs, max_slabs, (hipStream_t)stream);
-        if (rc != 1) return rc;
+    {   // the dedicated kernels: P3_SKIP = not the hook's shape, go on with the tile kernel below
+        const bool bf = dtype == P3_BF16, gen = (bf || split) && !colsum;       // gen: the generated-operand hooks, bf16 or fp32 operands as bf16 x 3; none sums columns
+        hipStream_t hs = (hipStream_t)stream;
+        int rc = P3_SKIP;
+        if (bf && b_mode == 0)                                  // the plain bf16 weight gradients at 64 / 128-aligned shapes: LDS-DMA kernel (gemm_tn_dma.hip)
+            rc = p3_gemm_tn_dma_try(A, B, C, M, N, K, lda, ldb, ldc, colsum, slabs, max_slabs, hs);
+        else if (gen && b_mode == P3_A_PAIR_AFFINE_RELU)        // the ScoreNet's conv2 weight gradient: pair_dw_mma.hip / pair_dw_x3.hip
+            rc = (bf ? p3_pair_dw_try : p3_pair_dw_x3_try)(A, B, C, M, N, K, lda, ldb, ldc, b_scale, b_shift, pair_V, pair_n, slabs, max_slabs, hs);
+        else if (gen && b_mode == P3_A_AFFINE_MASK2)            // conv3's dual-operand weight gradient: mask2_dw_mma.hip / mask2_dw_x3.hip
+            rc = (bf ? p3_mask2_dw_try : p3_mask2_dw_x3_try)(A, B, C, M, N, K, lda, ldb, ldc, b_scale, b_shift, slabs, max_slabs, hs);
+        if (rc != P3_SKIP) return rc;
     }
     TnArgs g; g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
     g.Kb = K;

@@ -34,10 +34,6 @@ struct TdArgs {
     float* cs_slab;     // deterministic mode: [splits][N]
 };
 
-typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-
 template <int N> __device__ __forceinline__ void td_wait_vm() {
     if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
@@ -221,24 +217,20 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_dma_kernel(TdArgs g) {
 
 }  // namespace
 
-// C[n,k] += sum_s slabs[s][n][k] (float64, split order) - gemm_tn.hip
-void p3_tn_reduce_launch(const float* slabs, float* C, int N, int K, int ldc, int splits, hipStream_t s);
-float* p3_tn_park(float* C, int N, int K, int ldc, int splits);      // gemm_tn.hip: deferred reduce slot or NULL
-
-// returns P3_OK when the launch was taken, 1 when the shape / mode is not this kernel's (the caller then runs gemm_tn.hip's kernel)
+// returns P3_OK when the launch was taken, P3_SKIP when the shape / mode is not this kernel's (the caller then runs gemm_tn.hip's kernel)
 int p3_gemm_tn_dma_try(const void* A, const void* B, float* C, int M, int N, int K, int lda, int ldb, int ldc, float* colsum, float* slabs, int max_slabs,
                        hipStream_t s) {
     static int on = -1;                              // P3_TN_DMA=0: every weight gradient on gemm_tn.hip's register-staged kernel (A/B: profiles/r04_mb_tn.txt)
     if (on < 0) { const char* e = getenv("P3_TN_DMA"); on = (e && e[0] == '0') ? 0 : 1; }
-    if (!on || M % TD_BM != 0 || N % 128 != 0 || K % 128 != 0 || lda % 8 != 0 || ldb % 8 != 0) return 1;
-    if (((uintptr_t)A % 16) != 0 || ((uintptr_t)B % 16) != 0) return 1;
-    if ((int64_t)TD_BM * lda * 2 + 256 >= (1ll << 31) || (int64_t)TD_BM * ldb * 2 + 256 >= (1ll << 31)) return 1;     // 32-bit DMA offsets inside a step
+    if (!on || M % TD_BM != 0 || N % 128 != 0 || K % 128 != 0 || lda % 8 != 0 || ldb % 8 != 0) return P3_SKIP;
+    if (((uintptr_t)A % 16) != 0 || ((uintptr_t)B % 16) != 0) return P3_SKIP;
+    if ((int64_t)TD_BM * lda * 2 + 256 >= (1ll << 31) || (int64_t)TD_BM * ldb * 2 + 256 >= (1ll << 31)) return P3_SKIP;     // 32-bit DMA offsets inside a step
     TdArgs g;
     g.A = (const bf16_t*)A; g.B = (const bf16_t*)B; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.colsum = colsum;
     const int tiles_n = N / 128;
     g.tiles_k = K / 128;
     const int tiles = tiles_n * g.tiles_k;
-    if (tiles > 256) return 1;
+    if (tiles > 256) return P3_SKIP;
     // one workgroup per CU: splits = 256 / tiles (the r03 finding for the register-staged kernel - the best grids fill ONE resident round -
     // holds here by construction); never fewer than 2 steps per split
     int splits = 256 / tiles;
@@ -256,15 +248,8 @@ int p3_gemm_tn_dma_try(const void* A, const void* B, float* C, int M, int N, int
     g.cs_slab = colsum ? p3_colsum_parts(splits, N, colsum, P3_BF16, &cs_parked) : nullptr;
     constexpr int NBUF = 4;                          // three steps in flight (NBUF = 3 measured 2 % slower, profiles/r04_mb_tn.txt)
     const size_t lds = (size_t)NBUF * TD_STEP_BYTES;       // >= the 64 KB the fold needs
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_tn_dma_kernel<NBUF>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
-        attr_set = true;
-    }
-    dim3 grid(tiles * splits), block(512);
-    hipLaunchKernelGGL(gemm_tn_dma_kernel<NBUF>, grid, block, lds, s, g);
-    if (p3_tracing()) p3_note_kernel("gemm_tn_dma_kernel<4>");
+    const int rc = p3_launch<gemm_tn_dma_kernel<NBUF>>("gemm_tn_dma_kernel<4>", dim3(tiles * splits), dim3(512), lds, s, g);
+    if (rc != P3_OK) return rc;
     if (g.slabs && !parked) p3_tn_reduce_launch(g.slabs, C, N, K, ldc, splits, s);
     P3_LAUNCH_CHECK();
     if (g.cs_slab && !cs_parked) return p3_det_reduce(g.cs_slab, splits, N, colsum, N, 1, s);

@@ -27,10 +27,6 @@ struct TdArgs {
     float* cs_slab;     // deterministic mode: [splits][N]
 };
 
-typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-
 template <int N> __device__ __forceinline__ void td_wait_vm() {
     if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
@@ -399,10 +395,6 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_x3_wide_kernel(TdArgs g) {
 
 }  // namespace
 
-// C[n,k] += sum_s slabs[s][n][k] (float64, split order) - gemm_tn.hip
-void p3_tn_reduce_launch(const float* slabs, float* C, int N, int K, int ldc, int splits, hipStream_t s);
-float* p3_tn_park(float* C, int N, int K, int ldc, int splits);      // gemm_tn.hip: deferred reduce slot or NULL
-
 static int g_tn_wide = 1;
 extern "C" int p3_gemm_tn_x3_wide(int on) { const int was = g_tn_wide; g_tn_wide = on; return was; }
 
@@ -442,17 +434,10 @@ extern "C" int p3_gemm_tn_x3(const void* a_hi, const void* a_lo, int lda, const 
     g.cs_slab = colsum ? p3_colsum_parts(splits, N, colsum, P3_F32, &cs_parked) : nullptr;
     constexpr int NBUF = 4;
     const size_t lds = (size_t)NBUF * TD_STEP_BYTES;       // 4 x 32 KB (>= the 64 KB the fold needs); the wide kernel's steps are 32 KB too
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_tn_x3_kernel<NBUF>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_tn_x3_wide_kernel<NBUF>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
-        attr_set = true;
-    }
     dim3 grid(tiles * splits), block(512);
-    if (wide) hipLaunchKernelGGL(gemm_tn_x3_wide_kernel<NBUF>, grid, block, lds, s, g);
-    else hipLaunchKernelGGL(gemm_tn_x3_kernel<NBUF>, grid, block, lds, s, g);
-    if (p3_tracing()) p3_note_kernel(wide ? "gemm_tn_x3_wide_kernel<4>" : "gemm_tn_x3_kernel<4>");
+    const int rc = !wide ? p3_launch<gemm_tn_x3_kernel<NBUF>>("gemm_tn_x3_kernel<4>", grid, block, lds, s, g)
+                         : p3_launch<gemm_tn_x3_wide_kernel<NBUF>>("gemm_tn_x3_wide_kernel<4>", grid, block, lds, s, g);
+    if (rc != P3_OK) return rc;
     if (g.slabs && !parked) p3_tn_reduce_launch(g.slabs, C, N, K, ldc, splits, s);
     P3_LAUNCH_CHECK();
     if (g.cs_slab && !cs_parked) return p3_det_reduce(g.cs_slab, splits, N, colsum, N, 1, s);

@@ -27,8 +27,6 @@ struct X3Args {
     int tiles_m, tiles_n;
 };
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-
 __device__ __forceinline__ void x3_wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // two 1 KB LDS-DMA pieces (consecutive in LDS) from one base pointer
@@ -486,11 +484,6 @@ __global__ __launch_bounds__(256) void from_planes_kernel(const bf16_t* __restri
 
 }  // namespace
 
-// gemm_x3_as.hip: the A-stationary persistent kernel for K = 256 / 384
-bool p3_gemm_x3_as_ok(const p3_gemm_x3_desc* d);
-bool p3_gemm_x3_as_default(const p3_gemm_x3_desc* d);
-int p3_gemm_x3_as(const p3_gemm_x3_desc* d, hipStream_t s);
-
 static int g_x3_tile = 0;
 extern "C" int p3_gemm_x3_tile(int mode) { const int was = g_x3_tile; g_x3_tile = mode; return was; }
 // the 128 x 384 tile (one workgroup per CU, 147 MFMA-flop per staged byte) pays where its quantisation over the CUs is not worse than the small tile's and
@@ -540,18 +533,9 @@ extern "C" int p3_gemm_x3(const p3_gemm_x3_desc* d, void* stream) {
     if (ln || big) {
         g.tiles_n = p3_ceil_div(d->N, 384);
         constexpr size_t LDS = 2 * (2 * 128 * 4 + 2 * 384 * 4) * 16;          // 2 slices x 64 KB
-        static bool attr_set = false;
-        if (!attr_set) {
-            hipError_t e = hipFuncSetAttribute((const void*)gemm_x3_n384_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_x3_n384_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
-            attr_set = true;
-        }
-        if (p3_tracing()) p3_note_kernel(ln ? "gemm_x3_n384_kernel<true>" : "gemm_x3_n384_kernel<false>");
-        if (ln) hipLaunchKernelGGL(gemm_x3_n384_kernel<true>, dim3(g.tiles_m * g.tiles_n), dim3(512), LDS, s, g);
-        else hipLaunchKernelGGL(gemm_x3_n384_kernel<false>, dim3(g.tiles_m * g.tiles_n), dim3(512), LDS, s, g);
-        P3_LAUNCH_CHECK();
-        return P3_OK;
+        const dim3 grid(g.tiles_m * g.tiles_n), block(512);
+        return !ln ? p3_launch<gemm_x3_n384_kernel<false>>("gemm_x3_n384_kernel<false>", grid, block, LDS, s, g)
+                   : p3_launch<gemm_x3_n384_kernel<true>>("gemm_x3_n384_kernel<true>", grid, block, LDS, s, g);
     }
     P3_CHECK(!ln, P3_EUNSUP, "p3_gemm_x3: fused LayerNorm needs N == 384");
     g.tiles_n = p3_ceil_div(d->N, 128);

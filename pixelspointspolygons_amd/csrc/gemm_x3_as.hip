@@ -41,7 +41,6 @@ struct AsArgs {
     unsigned long long* dbg;   // DBG: [workgroup][wave][8] cycle sums (barrier wait, epilogue, DMA issue, A reload, half 0, half 1, total, ticks)
 };
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef uint32_t as_u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ void as_dma1(const bf16_t* base, uint32_t dst, uint32_t v0) {
@@ -455,15 +454,7 @@ __global__ __launch_bounds__(512, 2) void gemm_x3_as_kernel(AsArgs g) {
 template <int KS, int EPI, bool DBG>
 int as_launch1(const AsArgs& g, int nwg, hipStream_t s) {
     const size_t LDS = AS_SLOTS * ((KS / 8) * 2 * 4096) + (size_t)g.d.N * 4 + 8 * 256 + 8 * 16 * 36 * 4;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_x3_as_kernel<KS, EPI, DBG>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((gemm_x3_as_kernel<KS, EPI, DBG>), dim3(nwg), dim3(512), LDS, s, g);
-    P3_LAUNCH_CHECK();
-    return P3_OK;
+    return p3_launch<gemm_x3_as_kernel<KS, EPI, DBG>>(nullptr, dim3(nwg), dim3(512), LDS, s, g);      // p3_gemm_x3_as records the name
 }
 
 // var: 0 the kernel, 1 its instrumented twin (s_memtime sums), 2 without epilogue, 3 without epilogue and weight stream (measurement)

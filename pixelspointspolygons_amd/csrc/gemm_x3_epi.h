@@ -4,6 +4,7 @@
 
 namespace {
 
+// split8 (p3_common.h) in the uint4 form of the 16-byte stores; kept as its own scalar loop: going through split8 and converting changes gemm_x3.hip's schedule
 __device__ __forceinline__ void x3_split8(const float (&v)[8], uint4& h, uint4& l) {
     uint32_t hw[4], lw[4];
 #pragma unroll

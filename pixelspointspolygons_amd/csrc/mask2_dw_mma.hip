@@ -23,10 +23,6 @@ struct MdArgs {
     float* C; int ldc; float* slabs; int64_t steps;
 };
 
-typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-
 __global__ __launch_bounds__(512, 1) void mask2_dw_mma_kernel(MdArgs g) {
     extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31;
@@ -117,27 +113,17 @@ __global__ __launch_bounds__(512, 1) void mask2_dw_mma_kernel(MdArgs g) {
 
 }  // namespace
 
-void p3_tn_reduce_launch(const float* slabs, float* C, int N, int K, int ldc, int splits, hipStream_t s);      // gemm_tn.hip
-
-// p3_gemm_tn_ex's hook for P3_A_AFFINE_MASK2: 1 when the shape is not this kernel's (the caller goes on with gemm_tn.hip), else the launch status
+// p3_gemm_tn_ex's hook for P3_A_AFFINE_MASK2: P3_SKIP when the shape is not this kernel's (the caller goes on with gemm_tn.hip), else the launch status
 int p3_mask2_dw_try(const void* A, const void* B, float* C, int M, int N, int Kb, int lda, int ldb, int ldc, const float* scale, const float* shift,
                     float* slabs, int max_slabs, hipStream_t s) {
-    if (N != 64 || Kb != 128 || lda != 64 || ldb != 128 || M % 128 != 0 || M < 128 * 256) return 1;
-    if ((((uintptr_t)A | (uintptr_t)B) % 16) != 0) return 1;
+    if (N != 64 || Kb != 128 || lda != 64 || ldb != 128 || M % 128 != 0 || M < 128 * 256) return P3_SKIP;
+    if ((((uintptr_t)A | (uintptr_t)B) % 16) != 0) return P3_SKIP;
     MdArgs g;
     g.dH = (const bf16_t*)A; g.H2 = (const bf16_t*)B; g.sc = scale; g.sh = shift; g.C = C; g.ldc = ldc; g.steps = M / 128;
     const int grid = 256;
     g.slabs = (slabs && grid <= max_slabs) ? slabs : nullptr;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)mask2_dw_mma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MD_LDS);
-        if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
-        attr_set = true;
-    }
-    if (p3_tracing()) p3_note_kernel("mask2_dw_mma_kernel");
-    hipLaunchKernelGGL(mask2_dw_mma_kernel, dim3(grid), dim3(512), MD_LDS, s, g);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
+    const int rc = p3_launch<mask2_dw_mma_kernel>("mask2_dw_mma_kernel", dim3(grid), dim3(512), MD_LDS, s, g);
+    if (rc != P3_OK) return rc;
     if (g.slabs) p3_tn_reduce_launch(g.slabs, C, 64, 256, ldc, grid, s);
     return P3_OK;
 }

@@ -26,19 +26,6 @@ struct MxArgs {
     float* C; int ldc; float* slabs; int64_t steps;
 };
 
-typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void mx_split8(const float (&v)[8], u32x4_t& h, u32x4_t& l) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const uint32_t hw = pack_bf2(v[2 * k], v[2 * k + 1]);
-        h[k] = hw;
-        l[k] = pack_bf2(v[2 * k] - __uint_as_float(hw << 16), v[2 * k + 1] - __uint_as_float(hw & 0xffff0000u));
-    }
-}
-
 __global__ __launch_bounds__(512, 2) void mask2_dw_x3_kernel(MxArgs g) {
     extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31;
@@ -66,7 +53,7 @@ __global__ __launch_bounds__(512, 2) void mask2_dw_x3_kernel(MxArgs g) {
         {
             const float x[8] = {pa[0].x, pa[0].y, pa[0].z, pa[0].w, pa[1].x, pa[1].y, pa[1].z, pa[1].w};
             u32x4_t h, l;
-            mx_split8(x, h, l);
+            split8(x, h, l);
             const uint32_t off = (uint32_t)(ar * 128 + ((ack ^ (((ar >> 1) & 1) << 2)) * 16));
             *reinterpret_cast<u32x4_t*>(base + off) = h;
             *reinterpret_cast<u32x4_t*>(base + MX_OFF_AL + off) = l;
@@ -84,7 +71,7 @@ __global__ __launch_bounds__(512, 2) void mask2_dw_x3_kernel(MxArgs g) {
                 m[2 * e] = on0 ? x[2 * e] : 0.f; m[2 * e + 1] = on1 ? x[2 * e + 1] : 0.f;
             }
             u32x4_t h, l;
-            mx_split8(m, h, l);
+            split8(m, h, l);
             const uint32_t off = (uint32_t)(r * 256 + ((bck ^ ((r & 3) << 2)) * 16));
             *reinterpret_cast<u32x4_t*>(base + MX_OFF_M1 + off) = m1;
             *reinterpret_cast<u32x4_t*>(base + MX_OFF_M2H + off) = h;
@@ -153,27 +140,17 @@ __global__ __launch_bounds__(512, 2) void mask2_dw_x3_kernel(MxArgs g) {
 
 }  // namespace
 
-void p3_tn_reduce_launch(const float* slabs, float* C, int N, int K, int ldc, int splits, hipStream_t s);      // gemm_tn.hip
-
-// p3_gemm_tn_ex's hook for P3_A_AFFINE_MASK2 with P3_F32X3 operands: 1 when the shape is not this kernel's (the caller goes on with gemm_tn.hip), else the launch status
+// p3_gemm_tn_ex's hook for P3_A_AFFINE_MASK2 with P3_F32X3 operands: P3_SKIP when the shape is not this kernel's (the caller goes on with gemm_tn.hip), else the launch status
 int p3_mask2_dw_x3_try(const void* A, const void* B, float* C, int M, int N, int Kb, int lda, int ldb, int ldc, const float* scale, const float* shift,
                        float* slabs, int max_slabs, hipStream_t s) {
-    if (N != 64 || Kb != 128 || lda != 64 || ldb != 128 || M % MX_ROWS != 0 || M < MX_ROWS * 256) return 1;
-    if ((((uintptr_t)A | (uintptr_t)B) % 16) != 0) return 1;
+    if (N != 64 || Kb != 128 || lda != 64 || ldb != 128 || M % MX_ROWS != 0 || M < MX_ROWS * 256) return P3_SKIP;
+    if ((((uintptr_t)A | (uintptr_t)B) % 16) != 0) return P3_SKIP;
     MxArgs g;
     g.dH = (const float*)A; g.H2 = (const float*)B; g.sc = scale; g.sh = shift; g.C = C; g.ldc = ldc; g.steps = M / MX_ROWS;
     const int grid = 256;
     g.slabs = (slabs && grid <= max_slabs) ? slabs : nullptr;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)mask2_dw_x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MX_LDS);
-        if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
-        attr_set = true;
-    }
-    if (p3_tracing()) p3_note_kernel("mask2_dw_x3_kernel");
-    hipLaunchKernelGGL(mask2_dw_x3_kernel, dim3(grid), dim3(512), MX_LDS, s, g);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
+    const int rc = p3_launch<mask2_dw_x3_kernel>("mask2_dw_x3_kernel", dim3(grid), dim3(512), MX_LDS, s, g);
+    if (rc != P3_OK) return rc;
     if (g.slabs) p3_tn_reduce_launch(g.slabs, C, 64, 256, ldc, grid, s);
     return P3_OK;
 }

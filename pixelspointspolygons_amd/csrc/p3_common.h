@@ -24,6 +24,24 @@ __device__ __forceinline__ uint32_t pack_bf2(float lo, float hi) {
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, p3_bf16x2));
 }
 
+// 16-byte register views: four dwords as loaded / stored, the same bits as one bf16 MFMA operand
+typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+
+// eight fp32 values -> bf16 hi plane (round to nearest even) and bf16 lo plane (the rounded remainder): the operand split of every fp32x3 kernel
+__device__ __forceinline__ void split8(const float (&v)[8], u32x4_t& h, u32x4_t& l) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t hw = pack_bf2(v[2 * k], v[2 * k + 1]);
+        h[k] = hw;
+        l[k] = pack_bf2(v[2 * k] - __uint_as_float(hw << 16), v[2 * k + 1] - __uint_as_float(hw & 0xffff0000u));
+    }
+}
+
+// workgroup barrier that waits for this wave's LDS traffic only: global loads (LDS-DMA included) stay in flight across it, unlike __syncthreads()
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
 template <typename T> struct Cvt;
 template <> struct Cvt<float> {
     static __device__ __forceinline__ float to_f(float v) { return v; }
@@ -180,3 +198,60 @@ int p3_det_reduce2(const float* parts, int nparts, int64_t stride, float* tmp, f
             return (int)e_;                            \
         }                                              \
     } while (0)
+
+// ---- one launch path for the kernels with more than the default dynamic LDS ---------------------------------------------------------------------
+// p3_launch<kernel>(name, grid, block, lds, stream, args...): raises the kernel's dynamic-LDS limit when the launch asks for more than the 64 KB every kernel
+// may have and more than this helper already set for THIS kernel on the CURRENT device, records `name` while tracing (NULL: a site that records none),
+// launches, and returns P3_OK or the hipError_t (message in p3_set_error).  Each kernel - every template instantiation - has its own table through the
+// template argument.  The table is a plain int array: two threads that race on an entry at worst both set the attribute, which is harmless; a device index
+// past the table sets it on every launch.
+constexpr int P3_LAUNCH_DEVICES = 16;
+template <auto Kernel, typename... Args>
+static inline int p3_launch(const char* name, dim3 grid, dim3 block, size_t lds, hipStream_t s, Args... args) {
+    hipError_t e = hipSuccess;
+    if (lds > 64 * 1024) {
+        static int raised[P3_LAUNCH_DEVICES];          // largest limit set, per device
+        int dev = -1;
+        e = hipGetDevice(&dev);
+        const bool known = e == hipSuccess && dev >= 0 && dev < P3_LAUNCH_DEVICES;
+        if (e == hipSuccess && !(known && raised[dev] >= (int)lds)) {
+            e = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e == hipSuccess && known) raised[dev] = (int)lds;
+        }
+    }
+    if (e == hipSuccess) {
+        if (name && p3_tracing()) p3_note_kernel(name);
+        hipLaunchKernelGGL(Kernel, grid, block, lds, s, args...);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
+    return P3_OK;
+}
+
+// ---- internal functions that cross source files (everything here has C++ linkage and is not exported) ------------------------------------------
+// The dedicated-kernel hooks of p3_gemm (gemm.hip) and p3_gemm_tn_ex (gemm_tn.hip): P3_SKIP when the problem is not one of the hook's shapes - the dispatcher
+// goes on with the next hook, then its tile kernel - else the launch status (P3_OK, a P3_E* code or a hipError_t).
+#define P3_SKIP 0x7fffffff
+static_assert(P3_SKIP > 0xffff && P3_EUNSUP < 0, "P3_SKIP lies outside the P3_E* codes (negative) and the hipError_t values (small positive)");
+int p3_rows_gemm_try(const void* A, const void* W, void* C, const p3_gemm_desc* d, hipStream_t s);        // rows_gemm.hip
+int p3_pair_fwd_try(const void* U, const void* W, void* C, const p3_gemm_desc* d, hipStream_t s);         // pair_fwd_mma.hip
+int p3_pair_fwd_x3_try(const void* U, const void* W, void* C, const p3_gemm_desc* d, hipStream_t s);      // pair_fwd_x3.hip: the P3_F32X3 form
+int p3_rows_x3_try(const void* A, const void* W, void* C, const p3_gemm_desc* d, hipStream_t s);          // rows_x3.hip: conv3 forward, P3_F32X3
+int p3_gemm_tn_dma_try(const void* A, const void* B, float* C, int M, int N, int K, int lda, int ldb, int ldc, float* colsum, float* slabs, int max_slabs,
+                       hipStream_t s);                                                                     // gemm_tn_dma.hip
+int p3_pair_dw_try(const void* A, const void* U, float* C, int M, int N, int K, int lda, int ldb, int ldc, const float* scale, const float* shift,
+                   const void* pair_V, int pair_n, float* slabs, int max_slabs, hipStream_t s);            // pair_dw_mma.hip
+int p3_pair_dw_x3_try(const void* A, const void* U, float* C, int M, int N, int K, int lda, int ldb, int ldc, const float* scale, const float* shift,
+                      const void* pair_V, int pair_n, float* slabs, int max_slabs, hipStream_t s);         // pair_dw_x3.hip: the P3_F32X3 form
+int p3_mask2_dw_try(const void* A, const void* B, float* C, int M, int N, int Kb, int lda, int ldb, int ldc, const float* scale, const float* shift,
+                    float* slabs, int max_slabs, hipStream_t s);                                           // mask2_dw_mma.hip
+int p3_mask2_dw_x3_try(const void* A, const void* B, float* C, int M, int N, int Kb, int lda, int ldb, int ldc, const float* scale, const float* shift,
+                       float* slabs, int max_slabs, hipStream_t s);                                        // mask2_dw_x3.hip: the P3_F32X3 form
+void p3_tn_reduce_launch(const float* slabs, float* C, int N, int K, int ldc, int splits, hipStream_t s);  // gemm_tn.hip: float64 sum of the split-M partial tiles
+float* p3_tn_park(float* C, int N, int K, int ldc, int splits);                                            // gemm_tn.hip: deferred reduce slot or NULL
+void p3_pair_dv_reduce_launch(const float* slab, float* dV, int nblk, int B, int N, int C, hipStream_t s); // scorenet_bwd.hip
+int p3_gemm_dma_eligible(const p3_gemm_desc* d, const void* A, const void* W, const void* C);              // gemm_dma.hip
+int p3_gemm_dma_launch(const void* A, const void* W, void* C, const p3_gemm_desc* d, int variant, hipStream_t s);
+bool p3_gemm_x3_as_ok(const p3_gemm_x3_desc* d);                                                           // gemm_x3_as.hip
+bool p3_gemm_x3_as_default(const p3_gemm_x3_desc* d);
+int p3_gemm_x3_as(const p3_gemm_x3_desc* d, hipStream_t s);

@@ -32,9 +32,6 @@ struct PfArgs {
     int B, N, nblk;
 };
 
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-
 __global__ __launch_bounds__(512, 2) void pair_bwd_mma_kernel(PfArgs g) {
     extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
     const int N = g.N;
@@ -201,8 +198,6 @@ __global__ __launch_bounds__(512, 2) void pair_bwd_mma_kernel(PfArgs g) {
 
 }  // namespace
 
-void p3_pair_dv_reduce_launch(const float* slab, float* dV, int nblk, int B, int N, int C, hipStream_t s);      // scorenet_bwd.hip
-
 extern "C" int64_t p3_pair_bwd_fused_workspace_bytes(int B, int N) { return (int64_t)B * ((N + PF_IB - 1) / PF_IB) * N * 256 * 4; }
 
 extern "C" int p3_pair_bwd_fused(const void* dH2, const void* W2t, const void* U, const void* V, const float* scale, const float* shift, const float* mean,
@@ -216,14 +211,8 @@ extern "C" int p3_pair_bwd_fused(const void* dH2, const void* W2t, const void* U
     g.sc = scale; g.sh = shift; g.mean = mean; g.dU = dU; g.dv_slab = (float*)workspace; g.acc = acc;
     g.B = B; g.N = N; g.nblk = (N + PF_IB - 1) / PF_IB;
     g.acc_slab = p3_det_scratch((int64_t)B * g.nblk * 512, P3_BF16);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)pair_bwd_mma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(pair_bwd_mma_kernel, dim3(g.nblk, B), dim3(512), PF_LDS, s, g);
-    P3_LAUNCH_CHECK();
+    const int rc = p3_launch<pair_bwd_mma_kernel>(nullptr, dim3(g.nblk, B), dim3(512), PF_LDS, s, g);
+    if (rc != P3_OK) return rc;
     p3_pair_dv_reduce_launch(g.dv_slab, dV, g.nblk, B, N, 256, s);
     P3_LAUNCH_CHECK();
     if (g.acc_slab) return p3_det_reduce(g.acc_slab, B * g.nblk, 512, acc, 512, 1, s);

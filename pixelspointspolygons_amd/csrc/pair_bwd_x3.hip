@@ -36,17 +36,9 @@ struct PxArgs {
     int B, N, nblk;
 };
 
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-
 __device__ __forceinline__ void px_split8(const float4& a, const float4& b, u32x4_t& h, u32x4_t& l) {
     const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const uint32_t hw = pack_bf2(v[2 * k], v[2 * k + 1]);
-        h[k] = hw;
-        l[k] = pack_bf2(v[2 * k] - __uint_as_float(hw << 16), v[2 * k + 1] - __uint_as_float(hw & 0xffff0000u));
-    }
+    split8(v, h, l);
 }
 
 struct PxFrag { u32x4_t ah[2], al[2]; };
@@ -233,8 +225,6 @@ __global__ __launch_bounds__(512, 2) void pair_bwd_x3_kernel(PxArgs g) {
 
 }  // namespace
 
-void p3_pair_dv_reduce_launch(const float* slab, float* dV, int nblk, int B, int N, int C, hipStream_t s);      // scorenet_bwd.hip
-
 extern "C" int p3_pair_bwd_fused_x3(const float* dH2, const float* W2t, const float* U, const float* V, const float* scale, const float* shift,
                                     const float* mean, float* dU, float* dV, float* acc, int B, int N, void* workspace, void* stream) {
     P3_CHECK(dH2 && W2t && U && V && scale && shift && mean && dU && dV && acc && workspace && B > 0 && N > 0, P3_EINVAL, "p3_pair_bwd_fused_x3: bad arguments");
@@ -245,15 +235,8 @@ extern "C" int p3_pair_bwd_fused_x3(const float* dH2, const float* W2t, const fl
     g.sc = scale; g.sh = shift; g.mean = mean; g.dU = dU; g.dv_slab = (float*)workspace; g.acc = acc;
     g.B = B; g.N = N; g.nblk = (N + PX_IB - 1) / PX_IB;
     g.acc_slab = p3_det_scratch((int64_t)B * g.nblk * 512, P3_F32);      // the fp32 family reduces in fixed order
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)pair_bwd_x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
-        attr_set = true;
-    }
-    if (p3_tracing()) p3_note_kernel("pair_bwd_x3_kernel");
-    hipLaunchKernelGGL(pair_bwd_x3_kernel, dim3(g.nblk, B), dim3(512), PX_LDS, s, g);
-    P3_LAUNCH_CHECK();
+    const int rc = p3_launch<pair_bwd_x3_kernel>("pair_bwd_x3_kernel", dim3(g.nblk, B), dim3(512), PX_LDS, s, g);
+    if (rc != P3_OK) return rc;
     p3_pair_dv_reduce_launch(g.dv_slab, dV, g.nblk, B, N, 256, s);
     P3_LAUNCH_CHECK();
     if (g.acc_slab) return p3_det_reduce(g.acc_slab, B * g.nblk, 512, acc, 512, 1, s);

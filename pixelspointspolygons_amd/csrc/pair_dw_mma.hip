@@ -34,10 +34,6 @@ struct PdArgs {
     int B, N, nblk, units;
 };
 
-typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-
 __global__ __launch_bounds__(512, 1) void pair_dw_mma_kernel(PdArgs g) {
     extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
     const int N = g.N;
@@ -149,32 +145,22 @@ __global__ __launch_bounds__(512, 1) void pair_dw_mma_kernel(PdArgs g) {
 
 }  // namespace
 
-void p3_tn_reduce_launch(const float* slabs, float* C, int N, int K, int ldc, int splits, hipStream_t s);      // gemm_tn.hip
-
-// p3_gemm_tn_ex's hook for the pair mode: 1 when the shape is not this kernel's (the caller goes on with gemm_tn.hip), else the launch status
+// p3_gemm_tn_ex's hook for the pair mode: P3_SKIP when the shape is not this kernel's (the caller goes on with gemm_tn.hip), else the launch status
 int p3_pair_dw_try(const void* A, const void* U, float* C, int M, int N, int K, int lda, int ldb, int ldc, const float* scale, const float* shift,
                    const void* pair_V, int pair_n, float* slabs, int max_slabs, hipStream_t s) {
-    if (N != 128 || K != 256 || lda != 128 || ldb != 256 || pair_n < PD_JT || pair_n % PD_JT != 0) return 1;
-    if ((((uintptr_t)A | (uintptr_t)U | (uintptr_t)pair_V) % 16) != 0) return 1;
+    if (N != 128 || K != 256 || lda != 128 || ldb != 256 || pair_n < PD_JT || pair_n % PD_JT != 0) return P3_SKIP;
+    if ((((uintptr_t)A | (uintptr_t)U | (uintptr_t)pair_V) % 16) != 0) return P3_SKIP;
     const int n = pair_n;
     const int64_t B = (int64_t)M / ((int64_t)n * n);
-    if (B * n * n != M || B < 1) return 1;
-    if ((int64_t)PD_IB * n * 256 >= (1ll << 31) || (int64_t)n * 512 >= (1ll << 31)) return 1;       // 32-bit DMA offsets inside a unit
+    if (B * n * n != M || B < 1) return P3_SKIP;
+    if ((int64_t)PD_IB * n * 256 >= (1ll << 31) || (int64_t)n * 512 >= (1ll << 31)) return P3_SKIP;       // 32-bit DMA offsets inside a unit
     PdArgs g;
     g.dH = (const bf16_t*)A; g.U = (const bf16_t*)U; g.V = (const bf16_t*)pair_V; g.sc = scale; g.sh = shift; g.C = C; g.ldc = ldc;
     g.B = (int)B; g.N = n; g.nblk = n / PD_IB; g.units = (int)B * g.nblk;
     int grid = g.units < 256 ? g.units : 256;                // one workgroup per CU, ~6 units each at the bench size
     g.slabs = (slabs && grid <= max_slabs) ? slabs : nullptr;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)pair_dw_mma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PD_LDS);
-        if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
-        attr_set = true;
-    }
-    if (p3_tracing()) p3_note_kernel("pair_dw_mma_kernel");
-    hipLaunchKernelGGL(pair_dw_mma_kernel, dim3(grid), dim3(512), PD_LDS, s, g);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
+    const int rc = p3_launch<pair_dw_mma_kernel>("pair_dw_mma_kernel", dim3(grid), dim3(512), PD_LDS, s, g);
+    if (rc != P3_OK) return rc;
     if (g.slabs) p3_tn_reduce_launch(g.slabs, C, 128, 256, ldc, grid, s);
     return P3_OK;
 }

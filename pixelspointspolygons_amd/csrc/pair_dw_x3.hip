@@ -34,20 +34,9 @@ struct DxArgs {
     int B, N, nblk, units;
 };
 
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 typedef short s16x4_t __attribute__((ext_vector_type(4)));
 typedef short s16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) s16x4_t* lds_s16x4_ptr;
-
-__device__ __forceinline__ void dx_split8(const float (&v)[8], u32x4_t& h, u32x4_t& l) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const uint32_t hw = pack_bf2(v[2 * k], v[2 * k + 1]);
-        h[k] = hw;
-        l[k] = pack_bf2(v[2 * k] - __uint_as_float(hw << 16), v[2 * k + 1] - __uint_as_float(hw & 0xffff0000u));
-    }
-}
 
 struct DxSet { s16x4_t h[4][2], l[4][2]; };                  // dH2^T fragments of one 16-row block: [channel block][rows +0..3 | +4..7], hi and lo
 
@@ -95,7 +84,7 @@ __global__ __launch_bounds__(512, 2) void pair_dw_x3_kernel(DxArgs g) {
             const float4 x0 = *reinterpret_cast<const float4*>(base + q * 2048), x1 = *reinterpret_cast<const float4*>(base + q * 2048 + 1024);
             const float x[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
             u32x4_t h, l;
-            dx_split8(x, h, l);
+            split8(x, h, l);
             *reinterpret_cast<u32x4_t*>(base + q * 2048) = h;
             *reinterpret_cast<u32x4_t*>(base + q * 2048 + 1024) = l;
         }
@@ -156,7 +145,7 @@ __global__ __launch_bounds__(512, 2) void pair_dw_x3_kernel(DxArgs g) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) a[e] = fmaxf(fmaf(vc[kk], s_, us[e]), 0.f);
             u32x4_t bh_, bl_;
-            dx_split8(a, bh_, bl_);
+            split8(a, bh_, bl_);
             const bf16x8_t bh = __builtin_bit_cast(bf16x8_t, bh_), bl = __builtin_bit_cast(bf16x8_t, bl_);
             __builtin_amdgcn_sched_barrier(0);
             bf16x8_t ah[4], al[4];
@@ -202,31 +191,21 @@ __global__ __launch_bounds__(512, 2) void pair_dw_x3_kernel(DxArgs g) {
 
 }  // namespace
 
-void p3_tn_reduce_launch(const float* slabs, float* C, int N, int K, int ldc, int splits, hipStream_t s);      // gemm_tn.hip
-
-// p3_gemm_tn_ex's hook for the pair mode with P3_F32X3 operands: 1 when the shape is not this kernel's (the caller goes on with gemm_tn.hip), else the launch status
+// p3_gemm_tn_ex's hook for the pair mode with P3_F32X3 operands: P3_SKIP when the shape is not this kernel's (the caller goes on with gemm_tn.hip), else the launch status
 int p3_pair_dw_x3_try(const void* A, const void* U, float* C, int M, int N, int K, int lda, int ldb, int ldc, const float* scale, const float* shift,
                       const void* pair_V, int pair_n, float* slabs, int max_slabs, hipStream_t s) {
-    if (N != 128 || K != 256 || lda != 128 || ldb != 256 || pair_n < DX_JT || pair_n % DX_JT != 0) return 1;
-    if ((((uintptr_t)A | (uintptr_t)U | (uintptr_t)pair_V) % 16) != 0) return 1;
+    if (N != 128 || K != 256 || lda != 128 || ldb != 256 || pair_n < DX_JT || pair_n % DX_JT != 0) return P3_SKIP;
+    if ((((uintptr_t)A | (uintptr_t)U | (uintptr_t)pair_V) % 16) != 0) return P3_SKIP;
     const int n = pair_n;
     const int64_t B = (int64_t)M / ((int64_t)n * n);
-    if (B * n * n != M || B < 1) return 1;
+    if (B * n * n != M || B < 1) return P3_SKIP;
     DxArgs g;
     g.dH = (const float*)A; g.U = (const float*)U; g.V = (const float*)pair_V; g.sc = scale; g.sh = shift; g.C = C; g.ldc = ldc;
     g.B = (int)B; g.N = n; g.nblk = n / DX_IB; g.units = (int)B * g.nblk;
     int grid = g.units < 256 ? g.units : 256;                // one workgroup per CU, ~6 units each at the bench size
     g.slabs = (slabs && grid <= max_slabs) ? slabs : nullptr;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)pair_dw_x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, DX_LDS);
-        if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
-        attr_set = true;
-    }
-    if (p3_tracing()) p3_note_kernel("pair_dw_x3_kernel");
-    hipLaunchKernelGGL(pair_dw_x3_kernel, dim3(grid), dim3(512), DX_LDS, s, g);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
+    const int rc = p3_launch<pair_dw_x3_kernel>("pair_dw_x3_kernel", dim3(grid), dim3(512), DX_LDS, s, g);
+    if (rc != P3_OK) return rc;
     if (g.slabs) p3_tn_reduce_launch(g.slabs, C, 128, 256, ldc, grid, s);
     return P3_OK;
 }

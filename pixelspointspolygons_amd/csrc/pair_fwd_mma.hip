@@ -25,16 +25,11 @@
 
 #include "p3_common.h"
 
-#define P3_PAIR_FWD_SKIP 0x7fffffff
-
 namespace {
 
 constexpr int QF_IB = 8, QF_JT = 32, QF_KS = 64;
 constexpr int QF_W_BYTES = 128 * 512, QF_A_BYTES = 256 * 128;
 constexpr int QF_LDS = QF_W_BYTES + 2 * QF_A_BYTES + 256 * 4;       // + the scale table
-
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 
 struct QfArgs {
     const bf16_t* U; const bf16_t* V; const bf16_t* W2; bf16_t* Y;
@@ -42,8 +37,6 @@ struct QfArgs {
     float* stats;          // [gridDim.y * gridDim.x][256] (sum | sum of squares) or NULL
     int B, N, ngroups;
 };
-
-__device__ __forceinline__ void lds_only_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 __global__ __launch_bounds__(512, 1) void pair_fwd_mma_kernel(QfArgs g) {
     extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
@@ -139,26 +132,26 @@ __global__ __launch_bounds__(512, 1) void pair_fwd_mma_kernel(QfArgs g) {
         unsigned char* A1 = A0 + QF_A_BYTES;
         // ---- prologue of the group: V of step 0 (all four stages), image of stage 0
         load_v(0, 0); load_v(0, 1); load_v(0, 2); load_v(0, 3);
-        lds_only_barrier();                                   // W2 / table stored (first group); the previous group's last reads of A0 are done
+        lds_barrier();                                        // W2 / table stored (first group); the previous group's last reads of A0 are done
         gen(0, A0);
         zero_acc();
         for (int st = 0; st < nsteps; ++st) {
             const bool more = st + 1 < nsteps;
             // stage 0: multiply A0, generate stage 1 into A1; V of stage 3 was loaded one step (or the prologue) ago
-            lds_only_barrier();
+            lds_barrier();
             gen(1, A1);
             mma(0, A0);
             // stage 1
-            lds_only_barrier();
+            lds_barrier();
             gen(2, A0);
             mma(1, A1);
             // stage 2: generate stage 3, then fetch the next step's stages 0..2 (their slots are free now)
-            lds_only_barrier();
+            lds_barrier();
             gen(3, A1);
             if (more) { load_v(st + 1, 0); load_v(st + 1, 1); load_v(st + 1, 2); }
             mma(2, A0);
             // stage 3: generate the next step's stage 0 (waits for the loads above - no store is pending yet), multiply, epilogue, THEN the stage-3 V loads
-            lds_only_barrier();
+            lds_barrier();
             if (more) gen(0, A0);
             mma(3, A1);
             {
@@ -188,28 +181,28 @@ __global__ __launch_bounds__(512, 1) void pair_fwd_mma_kernel(QfArgs g) {
     }
     // ---- BatchNorm-2 column sums of this workgroup: half-waves, then the four wave rows, in a fixed order
     if (g.stats) {
-        lds_only_barrier();
+        lds_barrier();
         float* red = reinterpret_cast<float*>(lds + QF_W_BYTES);          // [4][256]
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb) {
             const float a1 = s1[cb] + __shfl_xor(s1[cb], 32, 64), a2 = s2[cb] + __shfl_xor(s2[cb], 32, 64);
             if (hi == 0) { red[wr * 256 + wc * 64 + cb * 32 + l31] = a1; red[wr * 256 + 128 + wc * 64 + cb * 32 + l31] = a2; }
         }
-        lds_only_barrier();
+        lds_barrier();
         if (tid < 256) g.stats[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 256 + tid] = ((red[tid] + red[256 + tid]) + red[512 + tid]) + red[768 + tid];
     }
 }
 
 }  // namespace
 
-// p3_gemm's hook for P3_A_PAIR_AFFINE_RELU: P3_PAIR_FWD_SKIP when the problem is not the ScoreNet conv2 shape (the caller goes on with its tile kernel)
+// p3_gemm's hook for P3_A_PAIR_AFFINE_RELU: P3_SKIP when the problem is not the ScoreNet conv2 shape (the caller goes on with its tile kernel)
 int p3_pair_fwd_try(const void* U, const void* W, void* C, const p3_gemm_desc* d, hipStream_t s) {
-    if (d->a_mode != P3_A_PAIR_AFFINE_RELU || d->dtype_in != P3_BF16 || d->dtype_out != P3_BF16 || d->K != 256 || d->N != 128) return P3_PAIR_FWD_SKIP;
-    if (d->lda != 256 || d->ldb != 256 || d->ldc != 128 || d->pair_n < 8 || d->pair_n % QF_IB != 0) return P3_PAIR_FWD_SKIP;
-    if (d->act != P3_ACT_NONE || d->residual || d->aux || d->bwd_saved || (d->drop.seed && d->drop.p > 0.f)) return P3_PAIR_FWD_SKIP;
-    if ((((uintptr_t)U | (uintptr_t)W | (uintptr_t)C | (uintptr_t)d->pair_V) % 16) != 0) return P3_PAIR_FWD_SKIP;
+    if (d->a_mode != P3_A_PAIR_AFFINE_RELU || d->dtype_in != P3_BF16 || d->dtype_out != P3_BF16 || d->K != 256 || d->N != 128) return P3_SKIP;
+    if (d->lda != 256 || d->ldb != 256 || d->ldc != 128 || d->pair_n < 8 || d->pair_n % QF_IB != 0) return P3_SKIP;
+    if (d->act != P3_ACT_NONE || d->residual || d->aux || d->bwd_saved || (d->drop.seed && d->drop.p > 0.f)) return P3_SKIP;
+    if ((((uintptr_t)U | (uintptr_t)W | (uintptr_t)C | (uintptr_t)d->pair_V) % 16) != 0) return P3_SKIP;
     const int N = d->pair_n, B = (int)((int64_t)d->M / ((int64_t)N * N));
-    if ((int64_t)B * N * N != d->M || B > 65535) return P3_PAIR_FWD_SKIP;
+    if ((int64_t)B * N * N != d->M || B > 65535) return P3_SKIP;
     QfArgs g;
     g.U = (const bf16_t*)U; g.V = (const bf16_t*)d->pair_V; g.W2 = (const bf16_t*)W; g.Y = (bf16_t*)C;
     g.bias = d->bias; g.sc = d->a_scale; g.sh = d->a_shift; g.stats = nullptr;
@@ -223,19 +216,11 @@ int p3_pair_fwd_try(const void* U, const void* W, void* C, const p3_gemm_desc* d
     if (d->colsum) {
         const int nch = (int)((nblocks + 127) / 128);
         scratch = p3_reduce_scratch(nblocks * 256 + (int64_t)nch * 256);
-        if (!scratch) return P3_PAIR_FWD_SKIP;
+        if (!scratch) return P3_SKIP;
         g.stats = scratch;
     }
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)pair_fwd_mma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, QF_LDS);
-        if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
-        attr_set = true;
-    }
-    if (p3_tracing()) p3_note_kernel("pair_fwd_mma_kernel");
-    hipLaunchKernelGGL(pair_fwd_mma_kernel, dim3(gx, B), dim3(512), QF_LDS, s, g);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
+    const int rc = p3_launch<pair_fwd_mma_kernel>("pair_fwd_mma_kernel", dim3(gx, B), dim3(512), QF_LDS, s, g);
+    if (rc != P3_OK) return rc;
     if (scratch) return p3_det_reduce2(scratch, (int)nblocks, 256, scratch + nblocks * 256, d->colsum, d->colsumsq, 128, 256, 1, s);
     return P3_OK;
 }

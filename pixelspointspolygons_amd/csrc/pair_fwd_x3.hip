@@ -18,8 +18,6 @@
 
 #include "p3_common.h"
 
-#define P3_PAIR_FWD_SKIP 0x7fffffff
-
 namespace {
 
 constexpr int QX_IB = 8, QX_JT = 16, QX_KS = 64;
@@ -30,9 +28,6 @@ constexpr int QX_US_STRIDE = 260;                         // floats per row of t
 constexpr int QX_OFF_V = 2 * QX_A_BYTES, QX_OFF_US = QX_OFF_V + 2 * QX_V_BYTES, QX_OFF_SC = QX_OFF_US + 8 * QX_US_STRIDE * 4;
 constexpr int QX_LDS = QX_OFF_SC + 256 * 4;
 
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-
 struct QxFrag { u32x4_t ah[2], al[2]; };
 
 struct QxArgs {
@@ -41,17 +36,6 @@ struct QxArgs {
     float* stats;          // [gridDim.y * gridDim.x][256] (sum | sum of squares) or NULL
     int B, N, ngroups;
 };
-
-__device__ __forceinline__ void qx_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-__device__ __forceinline__ void qx_split8(const float (&v)[8], u32x4_t& h, u32x4_t& l) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const uint32_t hw = pack_bf2(v[2 * k], v[2 * k + 1]);
-        h[k] = hw;
-        l[k] = pack_bf2(v[2 * k] - __uint_as_float(hw << 16), v[2 * k + 1] - __uint_as_float(hw & 0xffff0000u));
-    }
-}
 
 __global__ __launch_bounds__(512, 2) void pair_fwd_x3_kernel(QxArgs g) {
     extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
@@ -70,7 +54,7 @@ __global__ __launch_bounds__(512, 2) void pair_fwd_x3_kernel(QxArgs g) {
             const float4 x0 = *reinterpret_cast<const float4*>(wrow + kk * 16), x1 = *reinterpret_cast<const float4*>(wrow + kk * 16 + 4);
             const float v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
             u32x4_t h, l;
-            qx_split8(v, h, l);
+            split8(v, h, l);
             wh[kk] = __builtin_bit_cast(bf16x8_t, h); wl[kk] = __builtin_bit_cast(bf16x8_t, l);
         }
     }
@@ -116,7 +100,7 @@ __global__ __launch_bounds__(512, 2) void pair_fwd_x3_kernel(QxArgs g) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) a[e] = fmaxf(fmaf(vv[e], scv[e], usv[e]), 0.f);
                 u32x4_t h, l;
-                qx_split8(a, h, l);
+                split8(a, h, l);
                 const uint32_t off = (uint32_t)(r * 128 + ((gc ^ ((r & 7) ^ ((r >> 3) & 1))) * 16));
                 *reinterpret_cast<u32x4_t*>(img + off) = h;
                 *reinterpret_cast<u32x4_t*>(img + QX_IMG + off) = l;
@@ -172,7 +156,7 @@ __global__ __launch_bounds__(512, 2) void pair_fwd_x3_kernel(QxArgs g) {
         unsigned char* A0 = lds;
         unsigned char* A1 = lds + QX_A_BYTES;
         // ---- prologue of the group: (U_i scale + shift) table, V rows of step 0, image of stage 0
-        qx_barrier();                                         // the previous group's last reads (images, V copies, table) are done
+        lds_barrier();                                        // the previous group's last reads (images, V copies, table) are done
         {
             const int i = tid >> 6, k4 = (tid & 63) * 4;
             const float4 u = *reinterpret_cast<const float4*>(g.U + ((int64_t)b * N + min(i0 + i, N - 1)) * 256 + k4);
@@ -181,25 +165,25 @@ __global__ __launch_bounds__(512, 2) void pair_fwd_x3_kernel(QxArgs g) {
         }
         fetch_v(0);
         put_v(0);
-        qx_barrier();
+        lds_barrier();
         gen(0, A0, 0, 0); gen(0, A0, 0, 1);
         zero_acc();
         for (int st = 0; st < nsteps; ++st) {
             const bool more = st + 1 < nsteps;
             const int vb = st & 1;
             // stage 0: multiply A0, generate stage 1 into A1; the next step's V rows start their way here
-            qx_barrier();
+            lds_barrier();
             if (more) fetch_v(st + 1);
             stage(0, A0, true, 1, A1, vb);
             // stage 1: the next step's V rows land in the other copy (last read three barriers ago)
-            qx_barrier();
+            lds_barrier();
             if (more) put_v(vb ^ 1);
             stage(1, A1, true, 2, A0, vb);
             // stage 2
-            qx_barrier();
+            lds_barrier();
             stage(2, A0, true, 3, A1, vb);
             // stage 3: generate the next step's stage 0, multiply, epilogue
-            qx_barrier();
+            lds_barrier();
             stage(3, A1, more, 0, A0, vb ^ 1);
             {
                 // N % 8 == 0 (host check): every row i of the group exists; a column j beyond N (ragged last step) is a wave-uniform skip
@@ -224,25 +208,25 @@ __global__ __launch_bounds__(512, 2) void pair_fwd_x3_kernel(QxArgs g) {
     }
     // ---- BatchNorm-2 column sums of this workgroup: half-waves, then the two wave rows, in a fixed order
     if (g.stats) {
-        qx_barrier();
+        lds_barrier();
         float* red = reinterpret_cast<float*>(lds);               // [2][256]
         const float a1 = s1 + __shfl_xor(s1, 32, 64), a2 = s2 + __shfl_xor(s2, 32, 64);
         if (hi == 0) { red[wr * 256 + ch] = a1; red[wr * 256 + 128 + ch] = a2; }
-        qx_barrier();
+        lds_barrier();
         if (tid < 256) g.stats[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 256 + tid] = red[tid] + red[256 + tid];
     }
 }
 
 }  // namespace
 
-// p3_gemm's hook for P3_A_PAIR_AFFINE_RELU with P3_F32X3 operands: P3_PAIR_FWD_SKIP when the problem is not the ScoreNet conv2 shape
+// p3_gemm's hook for P3_A_PAIR_AFFINE_RELU with P3_F32X3 operands: P3_SKIP when the problem is not the ScoreNet conv2 shape
 int p3_pair_fwd_x3_try(const void* U, const void* W, void* C, const p3_gemm_desc* d, hipStream_t s) {
-    if (d->a_mode != P3_A_PAIR_AFFINE_RELU || d->dtype_in != P3_F32 || d->dtype_out != P3_F32 || d->K != 256 || d->N != 128) return P3_PAIR_FWD_SKIP;
-    if (d->lda != 256 || d->ldb != 256 || d->ldc != 128 || d->pair_n < 8 || d->pair_n % QX_IB != 0) return P3_PAIR_FWD_SKIP;
-    if (d->act != P3_ACT_NONE || d->residual || d->aux || d->bwd_saved || (d->drop.seed && d->drop.p > 0.f)) return P3_PAIR_FWD_SKIP;
-    if ((((uintptr_t)U | (uintptr_t)W | (uintptr_t)C | (uintptr_t)d->pair_V | (uintptr_t)d->a_scale | (uintptr_t)d->a_shift) % 16) != 0) return P3_PAIR_FWD_SKIP;
+    if (d->a_mode != P3_A_PAIR_AFFINE_RELU || d->dtype_in != P3_F32 || d->dtype_out != P3_F32 || d->K != 256 || d->N != 128) return P3_SKIP;
+    if (d->lda != 256 || d->ldb != 256 || d->ldc != 128 || d->pair_n < 8 || d->pair_n % QX_IB != 0) return P3_SKIP;
+    if (d->act != P3_ACT_NONE || d->residual || d->aux || d->bwd_saved || (d->drop.seed && d->drop.p > 0.f)) return P3_SKIP;
+    if ((((uintptr_t)U | (uintptr_t)W | (uintptr_t)C | (uintptr_t)d->pair_V | (uintptr_t)d->a_scale | (uintptr_t)d->a_shift) % 16) != 0) return P3_SKIP;
     const int N = d->pair_n, B = (int)((int64_t)d->M / ((int64_t)N * N));
-    if ((int64_t)B * N * N != d->M || B > 65535 || (int64_t)QX_IB * N * 128 + (int64_t)N * 128 >= (1ll << 31)) return P3_PAIR_FWD_SKIP;
+    if ((int64_t)B * N * N != d->M || B > 65535 || (int64_t)QX_IB * N * 128 + (int64_t)N * 128 >= (1ll << 31)) return P3_SKIP;
     QxArgs g;
     g.U = (const float*)U; g.V = (const float*)d->pair_V; g.W2 = (const float*)W; g.Y = (float*)C;
     g.bias = d->bias; g.sc = d->a_scale; g.sh = d->a_shift; g.stats = nullptr;
@@ -256,19 +240,11 @@ int p3_pair_fwd_x3_try(const void* U, const void* W, void* C, const p3_gemm_desc
     if (d->colsum) {
         const int nch = (int)((nblocks + 127) / 128);
         scratch = p3_reduce_scratch(nblocks * 256 + (int64_t)nch * 256);
-        if (!scratch) return P3_PAIR_FWD_SKIP;
+        if (!scratch) return P3_SKIP;
         g.stats = scratch;
     }
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)pair_fwd_x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, QX_LDS);
-        if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
-        attr_set = true;
-    }
-    if (p3_tracing()) p3_note_kernel("pair_fwd_x3_kernel");
-    hipLaunchKernelGGL(pair_fwd_x3_kernel, dim3(gx, B), dim3(512), QX_LDS, s, g);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
+    const int rc = p3_launch<pair_fwd_x3_kernel>("pair_fwd_x3_kernel", dim3(gx, B), dim3(512), QX_LDS, s, g);
+    if (rc != P3_OK) return rc;
     if (scratch) return p3_det_reduce2(scratch, (int)nblocks, 256, scratch + nblocks * 256, d->colsum, d->colsumsq, 128, 256, 1, s);
     return P3_OK;
 }

@@ -748,18 +748,8 @@ __global__ __launch_bounds__(256, 2) void pfn_l2_fused_kernel(const T* __restric
     constexpr int C = 32 * NBW * WPP, NS = 4 / WPP;      // NS: pillars in flight per workgroup
     constexpr bool X3 = sizeof(T) == 4;
     constexpr int XR = X3 ? 8 : 4;                       // 16-byte registers of one lane's share of a 32 x 64 row group
-    typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-    typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, l31 = lane & 31, hi = lane >> 5;
     const int cg = w % WPP, stream = w / WPP, ch0 = cg * 32 * NBW + l31;      // this lane's channels: ch0 + 32 nb
-    auto split8 = [](const float (&v)[8], u32x4_t& h, u32x4_t& l) __attribute__((always_inline)) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t hw = pack_bf2(v[2 * k], v[2 * k + 1]);
-            h[k] = hw;
-            l[k] = pack_bf2(v[2 * k] - __uint_as_float(hw << 16), v[2 * k + 1] - __uint_as_float(hw & 0xffff0000u));
-        }
-    };
     // W2 rows (channels) ch0 + 32 nb, k = 16 s + 8 hi .. + 8
     bf16x8_t wh[NBW][4], wl[X3 ? NBW : 1][X3 ? 4 : 1];
 #pragma unroll
@@ -1348,31 +1338,20 @@ extern "C" int p3_pillar_stem_phased(const float* values, const int64_t* offsets
 
     SortOut so{w.sorted, w.vox_xy, w.vox_start, w.vox_cnt, w.vox_row, w.nvox, w.totals};
     const size_t lds = (size_t)(SORT_WAVES + 5) * g.nc * 4 + 32 * 4;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)pillar_sort_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
     if (d->total_points >= 16 * (int64_t)nslots) {
         // dense clouds: a tile's points over SORT_SPLIT workgroups (count / tables / fill)
-        static bool attr2 = false;
-        if (!attr2) {
-            (void)hipFuncSetAttribute((const void*)pillar_sort_count_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)pillar_sort_fill_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            attr2 = true;
-        }
         unsigned* ghist = w.sort_tmp;
         unsigned* gstart = w.sort_tmp + (size_t)d->B * SORT_SPLIT * g.nc;
         const size_t lds_h = (size_t)SORT_WAVES * g.nc * 4, lds_t = (size_t)5 * g.nc * 4 + 32 * 4;
-        hipLaunchKernelGGL(pillar_sort_count_kernel, dim3(SORT_SPLIT, d->B), dim3(SORT_THREADS), lds_h, s, values, offsets, g, ghist);
-        P3_LAUNCH_CHECK();
+        int rc = p3_launch<pillar_sort_count_kernel>(nullptr, dim3(SORT_SPLIT, d->B), dim3(SORT_THREADS), lds_h, s, values, offsets, g, ghist);
+        if (rc != P3_OK) return rc;
         hipLaunchKernelGGL(pillar_sort_tables_kernel, dim3(d->B), dim3(SORT_THREADS), lds_t, s, offsets, g, d->max_points, d->max_voxels, so, ghist, gstart);
         P3_LAUNCH_CHECK();
-        hipLaunchKernelGGL(pillar_sort_fill_kernel, dim3(SORT_SPLIT, d->B), dim3(SORT_THREADS), lds_h, s, values, offsets, g, ghist, gstart, w.sorted);
-        P3_LAUNCH_CHECK();
+        rc = p3_launch<pillar_sort_fill_kernel>(nullptr, dim3(SORT_SPLIT, d->B), dim3(SORT_THREADS), lds_h, s, values, offsets, g, ghist, gstart, w.sorted);
+        if (rc != P3_OK) return rc;
     } else {
-        hipLaunchKernelGGL(pillar_sort_kernel, dim3(d->B), dim3(SORT_THREADS), lds, s, values, offsets, g, d->max_points, d->max_voxels, so);
-        P3_LAUNCH_CHECK();
+        const int rc = p3_launch<pillar_sort_kernel>(nullptr, dim3(d->B), dim3(SORT_THREADS), lds, s, values, offsets, g, d->max_points, d->max_voxels, so);
+        if (rc != P3_OK) return rc;
     }
     if (d->training) {
         // deterministic mode (p3_set_deterministic covers this dtype): the workgroups' partial sums go to the scratch and are added in workgroup order in float64

@@ -15,12 +15,7 @@
 // = lane % 32), D: lane = out channel, 16 rows -> the column sums are plain per-lane adds.
 #include "p3_common.h"
 
-#define P3_ROWS_SKIP 0x7fffffff     // "not one of my shapes" (no P3_E* / hipError_t value)
-
 namespace {
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 
 struct RGArgs {
     const bf16_t* X;        // [R, K]
@@ -162,37 +157,29 @@ template <int K, int N, int MODE>
 int rows_launch(RGArgs& g, const char* name, float* colsum, float* colsumsq, hipStream_t s) {
     constexpr int P = N + 4;
     const size_t lds_bytes = (size_t)(4 * 32 * P + (MODE == 0 ? 2 * K : 0)) * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)rows_gemm_kernel<K, N, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
-        attr_set = true;
-    }
     int64_t blocks = (g.groups + 3) / 4;
     if (blocks > 512) blocks = 512;                      // 2 workgroups / CU: every wave walks ~36 groups at the bench size
     float* scratch = nullptr;
     if (MODE == 0 && colsum) {
         const int nch = (int)((blocks + 127) / 128);
         scratch = p3_reduce_scratch(blocks * 2 * N + (int64_t)nch * 2 * N);
-        if (!scratch) return P3_ROWS_SKIP;                         // no scratch registered: the caller's tiled path (atomics / persistent sums)
+        if (!scratch) return P3_SKIP;                         // no scratch registered: the caller's tiled path (atomics / persistent sums)
         g.stats = scratch;
     }
-    if (p3_tracing()) p3_note_kernel(name);
-    hipLaunchKernelGGL((rows_gemm_kernel<K, N, MODE>), dim3((unsigned)blocks), dim3(256), lds_bytes, s, g);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
+    const int rc = p3_launch<rows_gemm_kernel<K, N, MODE>>(name, dim3((unsigned)blocks), dim3(256), lds_bytes, s, g);
+    if (rc != P3_OK) return rc;
     if (scratch) return p3_det_reduce2(scratch, (int)blocks, 2 * (int64_t)N, scratch + blocks * 2 * N, colsum, colsumsq, N, 2 * N, 1, s);
     return P3_OK;
 }
 
 }  // namespace
 
-// p3_gemm's hook: returns P3_ROWS_SKIP when the problem is not one of the two shapes (the caller goes on with its tiled kernels), else the launch status.
+// p3_gemm's hook: returns P3_SKIP when the problem is not one of the two shapes (the caller goes on with its tiled kernels), else the launch status.
 int p3_rows_gemm_try(const void* A, const void* W, void* C, const p3_gemm_desc* d, hipStream_t s) {
-    if (d->dtype_in != P3_BF16 || d->dtype_out != P3_BF16 || d->M % 32 != 0 || d->M < 4096) return P3_ROWS_SKIP;
-    if (d->lda != d->K || d->ldb != d->K || d->ldc != d->N) return P3_ROWS_SKIP;
-    if (d->act != P3_ACT_NONE || d->residual || d->aux || (d->drop.seed && d->drop.p > 0.f)) return P3_ROWS_SKIP;
-    if (((uintptr_t)A | (uintptr_t)W | (uintptr_t)C) % 16 != 0) return P3_ROWS_SKIP;
+    if (d->dtype_in != P3_BF16 || d->dtype_out != P3_BF16 || d->M % 32 != 0 || d->M < 4096) return P3_SKIP;
+    if (d->lda != d->K || d->ldb != d->K || d->ldc != d->N) return P3_SKIP;
+    if (d->act != P3_ACT_NONE || d->residual || d->aux || (d->drop.seed && d->drop.p > 0.f)) return P3_SKIP;
+    if (((uintptr_t)A | (uintptr_t)W | (uintptr_t)C) % 16 != 0) return P3_SKIP;
     RGArgs g;
     memset(&g, 0, sizeof(g));
     g.X = (const bf16_t*)A; g.W = (const bf16_t*)W; g.Y = (bf16_t*)C; g.groups = d->M / 32;
@@ -205,5 +192,5 @@ int p3_rows_gemm_try(const void* A, const void* W, void* C, const p3_gemm_desc* 
         g.H = (const bf16_t*)d->bwd_saved; g.bn = d->bwd_bn;
         return rows_launch<64, 128, 1>(g, "rows_gemm_kernel<64, 128, 1>", nullptr, nullptr, s);
     }
-    return P3_ROWS_SKIP;
+    return P3_SKIP;
 }

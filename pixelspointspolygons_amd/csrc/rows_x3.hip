@@ -11,12 +11,7 @@
 // 32) .. + 8); in the accumulator layout a lane holds one channel and 16 rows: 4-byte stores, 32 lanes = 128 contiguous bytes of an output row - no LDS image.
 #include "p3_common.h"
 
-#define P3_ROWS_SKIP 0x7fffffff
-
 namespace {
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 
 struct RXArgs {
     const float* X;         // [R, 128]
@@ -28,15 +23,6 @@ struct RXArgs {
     float* stats;           // [gridDim.x][128] or NULL
     int64_t groups;         // R / 32
 };
-
-__device__ __forceinline__ void rx_split8(const float (&v)[8], u32x4_t& h, u32x4_t& l) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const uint32_t hw = pack_bf2(v[2 * k], v[2 * k + 1]);
-        h[k] = hw;
-        l[k] = pack_bf2(v[2 * k] - __uint_as_float(hw << 16), v[2 * k + 1] - __uint_as_float(hw & 0xffff0000u));
-    }
-}
 
 __global__ __launch_bounds__(256, 2) void rows_x3_fwd_kernel(RXArgs g) {
     constexpr int K = 128, N = 64;
@@ -54,7 +40,7 @@ __global__ __launch_bounds__(256, 2) void rows_x3_fwd_kernel(RXArgs g) {
         const float4 x0 = *reinterpret_cast<const float4*>(wp), x1 = *reinterpret_cast<const float4*>(wp + 4);
         const float v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
         u32x4_t h, l;
-        rx_split8(v, h, l);
+        split8(v, h, l);
         wh[s] = __builtin_bit_cast(bf16x8_t, h); wl[s] = __builtin_bit_cast(bf16x8_t, l);
     }
     // scale / shift of this lane's k positions: k = 16 s + 8 hi + e
@@ -79,7 +65,7 @@ __global__ __launch_bounds__(256, 2) void rows_x3_fwd_kernel(RXArgs g) {
                                 fmaxf(fmaf(x[s][0].w, c0.w, h0.w), 0.f), fmaxf(fmaf(x[s][1].x, c1.x, h1.x), 0.f), fmaxf(fmaf(x[s][1].y, c1.y, h1.y), 0.f),
                                 fmaxf(fmaf(x[s][1].z, c1.z, h1.z), 0.f), fmaxf(fmaf(x[s][1].w, c1.w, h1.w), 0.f)};
             u32x4_t ah_, al_;
-            rx_split8(a, ah_, al_);
+            split8(a, ah_, al_);
             const bf16x8_t ah = __builtin_bit_cast(bf16x8_t, ah_), al = __builtin_bit_cast(bf16x8_t, al_);
             const int ks = half * 4 + s;
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, wh[ks], acc, 0, 0, 0);
@@ -115,13 +101,13 @@ __global__ __launch_bounds__(256, 2) void rows_x3_fwd_kernel(RXArgs g) {
 
 }  // namespace
 
-// p3_gemm's hook for P3_F32X3: P3_ROWS_SKIP when the problem is not the conv3-forward shape (the caller goes on with its tile kernel), else the launch status
+// p3_gemm's hook for P3_F32X3: P3_SKIP when the problem is not the conv3-forward shape (the caller goes on with its tile kernel), else the launch status
 int p3_rows_x3_try(const void* A, const void* W, void* C, const p3_gemm_desc* d, hipStream_t s) {
-    if (d->dtype_in != P3_F32 || d->dtype_out != P3_F32 || d->M % 32 != 0 || d->M < 4096) return P3_ROWS_SKIP;
-    if (d->a_mode != P3_A_AFFINE_RELU || d->K != 128 || d->N != 64 || d->bwd_saved) return P3_ROWS_SKIP;
-    if (d->lda != d->K || d->ldb != d->K || d->ldc != d->N) return P3_ROWS_SKIP;
-    if (d->act != P3_ACT_NONE || d->residual || d->aux || (d->drop.seed && d->drop.p > 0.f)) return P3_ROWS_SKIP;
-    if (((uintptr_t)A | (uintptr_t)W | (uintptr_t)C) % 16 != 0) return P3_ROWS_SKIP;
+    if (d->dtype_in != P3_F32 || d->dtype_out != P3_F32 || d->M % 32 != 0 || d->M < 4096) return P3_SKIP;
+    if (d->a_mode != P3_A_AFFINE_RELU || d->K != 128 || d->N != 64 || d->bwd_saved) return P3_SKIP;
+    if (d->lda != d->K || d->ldb != d->K || d->ldc != d->N) return P3_SKIP;
+    if (d->act != P3_ACT_NONE || d->residual || d->aux || (d->drop.seed && d->drop.p > 0.f)) return P3_SKIP;
+    if (((uintptr_t)A | (uintptr_t)W | (uintptr_t)C) % 16 != 0) return P3_SKIP;
     RXArgs g;
     g.X = (const float*)A; g.W = (const float*)W; g.Y = (float*)C; g.bias = d->bias; g.a_scale = d->a_scale; g.a_shift = d->a_shift; g.stats = nullptr;
     g.groups = d->M / 32;
@@ -131,13 +117,11 @@ int p3_rows_x3_try(const void* A, const void* W, void* C, const p3_gemm_desc* d,
     if (d->colsum) {
         const int nch = (int)((blocks + 127) / 128);
         scratch = p3_reduce_scratch(blocks * 128 + (int64_t)nch * 128);
-        if (!scratch) return P3_ROWS_SKIP;
+        if (!scratch) return P3_SKIP;
         g.stats = scratch;
     }
-    if (p3_tracing()) p3_note_kernel("rows_x3_fwd_kernel");
-    hipLaunchKernelGGL(rows_x3_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, s, g);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
+    const int rc = p3_launch<rows_x3_fwd_kernel>("rows_x3_fwd_kernel", dim3((unsigned)blocks), dim3(256), 0, s, g);
+    if (rc != P3_OK) return rc;
     if (scratch) return p3_det_reduce2(scratch, (int)blocks, 128, scratch + blocks * 128, d->colsum, d->colsumsq, 64, 128, 1, s);
     return P3_OK;
 }

@@ -134,7 +134,7 @@ __global__ __launch_bounds__(1024) void sinkhorn_kernel(const float* __restrict_
                 v[rc] = vn;
                 if (h) h[M1 + rc] = vn;
             }
-            sk::lds_barrier();
+            lds_barrier();
 #pragma unroll
             for (int bb = 0; bb < CB; ++bb) { const int j = tx + 16 * bb; vr[bb] = j < N1 ? v[j] : 0.f; }
         }
@@ -267,13 +267,7 @@ extern "C" int p3_sinkhorn(const float* scores, const float* alpha, int B, int m
         const size_t zf = (size_t)(m + 1) * (n + 1) > (size_t)sk::Slab<CB>::FLOATS ? (size_t)(m + 1) * (n + 1) : (size_t)sk::Slab<CB>::FLOATS; \
         const size_t lds = (zf + 2 * (size_t)(m + 1) + (n + 1) + 2048) * sizeof(float);                                                   \
         P3_CHECK(lds <= 160 * 1024 - 512, P3_EUNSUP, "p3_sinkhorn: coupling matrix does not fit the 160 KB LDS");                         \
-        static bool attr_set = false;                                                                                                     \
-        if (!attr_set) {                                                                                                                  \
-            hipError_t e = hipFuncSetAttribute((const void*)sinkhorn_kernel<RA, CB>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512); \
-            if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }                                                   \
-            attr_set = true;                                                                                                              \
-        }                                                                                                                                 \
-        hipLaunchKernelGGL((sinkhorn_kernel<RA, CB>), dim3(B), dim3(1024), lds, s, scores, alpha, m, n, iters, perm, z_full, uv_hist, force_log); \
+        return p3_launch<sinkhorn_kernel<RA, CB>>(nullptr, dim3(B), dim3(1024), lds, s, scores, alpha, m, n, iters, perm, z_full, uv_hist, force_log); \
     } while (0)
     const int M1 = m + 1, N1 = n + 1;
     if (M1 <= 64 && N1 <= 32) P3_SK_LAUNCH(1, 2);
@@ -282,6 +276,4 @@ extern "C" int p3_sinkhorn(const float* scores, const float* alpha, int B, int m
     else if (M1 <= 256 && N1 <= 208) P3_SK_LAUNCH(4, 13);
     else P3_SK_LAUNCH(4, 16);
 #undef P3_SK_LAUNCH
-    P3_LAUNCH_CHECK();
-    return P3_OK;
 }

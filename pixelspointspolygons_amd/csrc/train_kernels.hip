@@ -269,7 +269,7 @@ __global__ __launch_bounds__(1024) void sinkhorn_bwd_fast_kernel(const float* __
             if (t > 1) cj = hvp;                                                 // V of the previous iteration (V_0 = 1)
             if (rp == 0) { Bl[rc] = bj; vs[2 * M1 + rc] = bj; vs[2 * M1 + N1 + rc] = cj; }
         }
-        sk::lds_barrier();                  // also separates this iteration's slab use from the previous one's
+        lds_barrier();                  // also separates this iteration's slab use from the previous one's
         float br[CB];
 #pragma unroll
         for (int bb = 0; bb < CB; ++bb) { const int j = tx + 16 * bb; br[bb] = j < N1 ? Bl[j] : 0.f; }
@@ -566,12 +566,6 @@ extern "C" int p3_sinkhorn_bwd(const float* scores, const float* alpha, int B, i
     P3_CHECK(lds <= 160 * 1024, P3_EUNSUP, "p3_sinkhorn_bwd: does not fit the 160 KB LDS");
     static int force_log = -1;                        // P3_SINKHORN_LOG=1: log-domain loop only (A/B, tests of the fallback)
     if (force_log < 0) { const char* e = getenv("P3_SINKHORN_LOG"); force_log = (e && e[0] == '1') ? 1 : 0; }
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)sinkhorn_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
-        attr_set = true;
-    }
     hipStream_t s = (hipStream_t)stream;
     int* tile_flags = reinterpret_cast<int*>(workspace);
     float* vecs = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + ((size_t)B * 4 + 255) / 256 * 256);
@@ -585,14 +579,9 @@ extern "C" int p3_sinkhorn_bwd(const float* scores, const float* alpha, int B, i
         const size_t zf = (size_t)(m + 1) * (n + 1) > (size_t)sk::Slab<CB>::FLOATS ? (size_t)(m + 1) * (n + 1) : (size_t)sk::Slab<CB>::FLOATS; \
         const size_t lds_fast = (zf + (size_t)(m + 1) + (size_t)(n + 1) + 2048) * sizeof(float);                                          \
         P3_CHECK(lds_fast <= 160 * 1024 - 512, P3_EUNSUP, "p3_sinkhorn_bwd: does not fit the 160 KB LDS");                                \
-        static bool fattr = false;                                                                                                        \
-        if (!fattr) {                                                                                                                     \
-            hipError_t e = hipFuncSetAttribute((const void*)sinkhorn_bwd_fast_kernel<RA, CB>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512); \
-            if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }                                                   \
-            fattr = true;                                                                                                                 \
-        }                                                                                                                                 \
-        hipLaunchKernelGGL((sinkhorn_bwd_fast_kernel<RA, CB>), dim3(B), dim3(1024), lds_fast, s, scores, alpha, m, n, iters, perm, uv_hist, dperm, dscores, \
-                           dalpha, tile_flags, vecs, rmaxs, force_log);                                                                   \
+        const int rc = p3_launch<sinkhorn_bwd_fast_kernel<RA, CB>>(nullptr, dim3(B), dim3(1024), lds_fast, s, scores, alpha, m, n, iters, perm, uv_hist, dperm, \
+                                                                   dscores, dalpha, tile_flags, vecs, rmaxs, force_log);                          \
+        if (rc != P3_OK) return rc;                                                                                                       \
         const int rpw = (m + 1 + SK_RS - 1) / SK_RS;                                                                                      \
         const size_t lds_dz = (size_t)SK_TC * (2 * rpw + 2 * (n + 1)) * sizeof(float);                                                    \
         hipLaunchKernelGGL((sinkhorn_bwd_dz_kernel<RA2, CB>), dim3(B * SK_RS), dim3(256), lds_dz, s, scores, alpha, m, n, iters, perm, dperm, dscores, \
@@ -607,9 +596,9 @@ extern "C" int p3_sinkhorn_bwd(const float* scores, const float* alpha, int B, i
         else P3_SKB_LAUNCH(4, 16, 2);
     }
 #undef P3_SKB_LAUNCH
-    hipLaunchKernelGGL(sinkhorn_bwd_kernel, dim3(B), dim3(1024), lds, s, scores, alpha, m, n, iters, perm, uv_hist, dperm, dscores, dalpha, tile_flags,
-                       da_slab ? da_slab + (int64_t)B * SK_RS : nullptr);
-    P3_LAUNCH_CHECK();
+    const int rc = p3_launch<sinkhorn_bwd_kernel>(nullptr, dim3(B), dim3(1024), lds, s, scores, alpha, m, n, iters, perm, uv_hist, dperm, dscores, dalpha, tile_flags,
+                                                  da_slab ? da_slab + (int64_t)B * SK_RS : nullptr);
+    if (rc != P3_OK) return rc;
     if (da_slab) return p3_det_reduce(da_slab, B * SK_RS + B, 1, dalpha, 1, 1, s);
     return P3_OK;
 }

@@ -77,13 +77,19 @@ def test_pair_weight_gradient_kernel_of_the_scorenet_conv2(Bn, n):
     out = torch.full((128, 256), 0.25, device=DEV)
     h.gemm_tn_ex(dH.to(DEV), U.to(DEV), out, h.A_PAIR_AFFINE_RELU, sc.to(DEV), sh.to(DEV), pair_v=V.to(DEV), pair_n=n, M=R)
     picked = h.lib().p3_last_kernel().decode()
+    h.lib().p3_trace_kernels(0); h.lib().p3_trace_kernels(1)      # clears the last name: gemm_tn.hip's tile kernel records none
+    out24 = torch.zeros((128, 256), device=DEV)
+    h.gemm_tn_ex(dH[:576].to(DEV), U[:24].to(DEV), out24, h.A_PAIR_AFFINE_RELU, sc.to(DEV), sh.to(DEV), pair_v=V[:24].to(DEV), pair_n=24, M=576)
+    picked24 = h.lib().p3_last_kernel().decode()
     h.lib().p3_trace_kernels(0)
-    assert picked == "pair_dw_mma_kernel", picked
-    pair = (U.float().view(Bn, n, 1, 256) + V.float().view(Bn, 1, n, 256)).reshape(-1, 256)
-    a1 = torch.relu(pair * sc + sh).bfloat16().double()
-    ref = dH.double().t() @ a1
+    assert picked == "pair_dw_mma_kernel" and picked24 != "pair_dw_mma_kernel", (picked, picked24)
+
+    def ref_of(dHh, Uh, Vh, nn):
+        pair = (Uh.float().view(-1, nn, 1, 256) + Vh.float().view(-1, 1, nn, 256)).reshape(-1, 256)
+        return dHh.double().t() @ torch.relu(pair * sc + sh).bfloat16().double()
     # the kernel's fma order may round a generated element to the neighbouring bf16 value: 2e-4 (measured ~3e-5), not the 2e-5 of a plain product
-    assert rel_err(out.cpu() - 0.25, ref.float()) < 2e-4
+    assert rel_err(out.cpu() - 0.25, ref_of(dH, U, V, n).float()) < 2e-4
+    assert rel_err(out24.cpu(), ref_of(dH[:576], U[:24], V[:24], 24).float()) < 2e-4
 
 
 @pytest.mark.parametrize("Bn,n", [(3, 48), (1, 192), (40, 16)])
@@ -717,7 +723,7 @@ def test_bn_sums_from_the_dual_operand_weight_gradient(dtype, tol):
 def test_dual_operand_weight_gradient_streaming_kernel(R):
     """csrc/mask2_dw_mma.hip (p3_gemm_tn_ex P3_A_AFFINE_MASK2 at the ScoreNet conv3 shape, bf16, R % 128 == 0, R >= 32768): G = dH3^T [y > 0] and G2 = dH3^T ([y > 0] H2)
     from transposing reads of the two row tiles, the masks built in registers - against float64 with the kernel's own decisions (y = fma(H2, scale, shift) in fp32),
-    accumulating into a non-zero matrix; 601 steps over 256 workgroups: ragged walk."""
+    accumulating into a non-zero matrix; 601 steps over 256 workgroups: ragged walk; a shorter R (4096 rows) stays on gemm_tn.hip and agrees."""
     h = _h()
     g = torch.Generator().manual_seed(17)
     dH3 = (torch.randn(R, 64, generator=g) * 0.3).bfloat16()
@@ -729,10 +735,16 @@ def test_dual_operand_weight_gradient_streaming_kernel(R):
     G = torch.full((64, 256), 0.5, device=DEV)
     h.gemm_tn_ex(dH3.to(DEV), H2.to(DEV), G, h.A_AFFINE_MASK2, sc.to(DEV), sh.to(DEV))
     picked = h.lib().p3_last_kernel().decode()
+    h.lib().p3_trace_kernels(0); h.lib().p3_trace_kernels(1)      # clears the last name: gemm_tn.hip's tile kernel records none
+    Gt = torch.zeros((64, 256), device=DEV)
+    h.gemm_tn_ex(dH3[:4096].to(DEV), H2[:4096].to(DEV), Gt, h.A_AFFINE_MASK2, sc.to(DEV), sh.to(DEV))
+    picked_t = h.lib().p3_last_kernel().decode()
     h.lib().p3_trace_kernels(0)
-    assert picked == "mask2_dw_mma_kernel", picked
+    assert picked == "mask2_dw_mma_kernel" and picked_t != "mask2_dw_mma_kernel", (picked, picked_t)
     # a decision may differ from this host expression's where y rounds to +-0 (fma vs mul + add): 1e-4 instead of the 2e-5 of a plain product
     assert rel_err(G.cpu() - 0.5, ref.float()) < 1e-4
+    ref_t = torch.cat([dH3[:4096].double().t() @ on[:4096].double(), dH3[:4096].double().t() @ (on * H2.float())[:4096].double()], 1)
+    assert rel_err(Gt.cpu(), ref_t.float()) < 1e-4
 
 
 @pytest.mark.parametrize("R", [64 * 256, 64 * 601])
