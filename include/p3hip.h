@@ -59,7 +59,10 @@ extern "C" {
 int p3_version(void);
 const char* p3_last_error_string(void);
 /* Measurement hook: after p3_trace_kernels(1), p3_last_kernel() names the device kernel the calling thread's last p3_gemm launched, spelled as
- * rocprofv3 --kernel-trace prints it after tools/kstats.py's bf16 rewrite ("gemm_dma_kernel<bf16, 32, 2>"); "" when tracing is off. */
+ * rocprofv3 --kernel-trace prints it after tools/kstats.py's bf16 rewrite ("gemm_dma_kernel<bf16, 32, 2>"); "" when tracing is off.  The other entries
+ * that choose between kernels record theirs too: p3_gemm_x3, p3_gemm_tn_ex ("gemm_tn_kernel<bf16, 0>" or its dedicated kernels), p3_gemm_tn_x3,
+ * p3_attention ("attn_fwd_kernel<bf16_t, 64, false>" / "attn_decode_kernel<64>") and the LayerNorm entries ("ln_fwd_kernel",
+ * "ln_fwd_half_planes_kernel", "ln_bwd_half_kernel", "ln_bwd_kernel").  p3_trace_kernels() itself forgets the last name. */
 void p3_trace_kernels(int on);
 const char* p3_last_kernel(void);
 

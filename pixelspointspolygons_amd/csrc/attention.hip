@@ -538,6 +538,7 @@ extern "C" int p3_attention(const void* Q, const void* K, const void* V, void* O
     constexpr int no_decode = 0;
     if (!no_decode && d->dtype == P3_BF16 && d->Lq == 1 && !d->causal && !drop && !d->lse && d->Lk <= 8192 && d->v_rs % 8 == 0 && d->v_bs % 8 == 0) {
         const size_t lds = (size_t)(((d->Lk + 3) & ~3) + (256 / (d->head_dim / 8)) * d->head_dim) * sizeof(float);
+        if (p3_tracing()) p3_note_kernel(d->head_dim == 64 ? "attn_decode_kernel<64>" : "attn_decode_kernel<32>");
         if (d->head_dim == 64) hipLaunchKernelGGL((attn_decode_kernel<64>), dim3(d->B * d->H), dim3(256), lds, s, a);
         else hipLaunchKernelGGL((attn_decode_kernel<32>), dim3(d->B * d->H), dim3(256), lds, s, a);
         P3_LAUNCH_CHECK();
@@ -548,9 +549,9 @@ extern "C" int p3_attention(const void* Q, const void* K, const void* V, void* O
     static int pad_lds = -1;              // P3_ATTN_PAD_LDS=<bytes> (diagnostic): extra dynamic LDS per workgroup of the fp32x3 kernels - 40000 leaves ONE workgroup per CU
     if (pad_lds < 0) { const char* e = getenv("P3_ATTN_PAD_LDS"); pad_lds = e ? atoi(e) : 0; }
     if (d->dtype == P3_F32X3) dyn += (size_t)pad_lds;
-#define P3_ATTN_FWD(T, D)                                                                  \
-    (drop ? p3_launch<attn_fwd_kernel<T, D, true>>(nullptr, grid, block, dyn, s, a)        \
-          : p3_launch<attn_fwd_kernel<T, D, false>>(nullptr, grid, block, dyn, s, a))
+#define P3_ATTN_FWD(T, D)                                                                                                  \
+    (drop ? p3_launch<attn_fwd_kernel<T, D, true>>("attn_fwd_kernel<" #T ", " #D ", true>", grid, block, dyn, s, a)        \
+          : p3_launch<attn_fwd_kernel<T, D, false>>("attn_fwd_kernel<" #T ", " #D ", false>", grid, block, dyn, s, a))
     if (d->dtype == P3_F32X3) return d->head_dim == 64 ? P3_ATTN_FWD(f32s, 64) : P3_ATTN_FWD(f32s, 32);      // fp32x3 mode: bf16 x 3 products on split images (attn_tile.h)
     if (d->dtype == P3_BF16) return d->head_dim == 64 ? P3_ATTN_FWD(bf16_t, 64) : P3_ATTN_FWD(bf16_t, 32);
     return d->head_dim == 64 ? P3_ATTN_FWD(float, 64) : P3_ATTN_FWD(float, 32);

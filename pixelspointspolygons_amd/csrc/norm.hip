@@ -337,6 +337,7 @@ extern "C" int p3_layernorm(const void* x, const float* gamma, const float* beta
     if (rows <= 0) return P3_OK;
     dim3 grid(p3_ceil_div(rows, 4)), block(256);
     hipStream_t s = (hipStream_t)stream;
+    if (p3_tracing()) p3_note_kernel("ln_fwd_kernel");
 #define LN_LAUNCH(TI, TO) \
     hipLaunchKernelGGL((ln_fwd_kernel<TI, TO>), grid, block, 0, s, (const TI*)x, gamma, beta, (TO*)y, rows, cols, ldx, ldy, eps, save_mean, save_rstd)
     if (dtype_in == P3_F32 && dtype_out == P3_F32) LN_LAUNCH(float, float);
@@ -394,6 +395,7 @@ extern "C" int p3_layernorm_planes(const float* x, const float* gamma, const flo
     if (half_on < 0) { const char* e = getenv("P3_LN_HALF"); half_on = (e && atoi(e) == 0) ? 0 : 1; }
     if (half_on && (cols == 256 || cols == 384 || cols == 768)) {          // at EVERY row count: a tile alone must give the bits it gives in a batch
         constexpr int RPB = 32;             // rows per block: four rows per half-wave, two at a time
+        if (p3_tracing()) p3_note_kernel("ln_fwd_half_planes_kernel");
         const dim3 grid(p3_ceil_div(rows, RPB)), block(256);
 #define LNH(CPL) hipLaunchKernelGGL((ln_fwd_half_planes_kernel<CPL>), grid, block, 0, (hipStream_t)stream, x, gamma, beta, (bf16_t*)y_hi, (bf16_t*)y_lo, rows, ldx, ldy, eps, save_mean, save_rstd, RPB)
         if (cols == 256) LNH(2); else if (cols == 384) LNH(3); else LNH(6);
@@ -401,6 +403,7 @@ extern "C" int p3_layernorm_planes(const float* x, const float* gamma, const flo
         P3_LAUNCH_CHECK();
         return P3_OK;
     }
+    if (p3_tracing()) p3_note_kernel("ln_fwd_kernel");
     hipLaunchKernelGGL((ln_fwd_kernel<float, bf16_t>), dim3(p3_ceil_div(rows, 4)), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, (bf16_t*)y_hi, rows, cols, ldx, ldy, eps,
                        save_mean, save_rstd, (bf16_t*)y_lo);
     P3_LAUNCH_CHECK();
@@ -428,6 +431,7 @@ static int ln_bwd_impl(const void* dy, const void* x, const float* gamma, const 
     hipStream_t s = (hipStream_t)stream;
     // dgamma / dbeta partials of the half-wave kernel go through the registered scratch (none registered / too small: atomics)
     const bool halfk = half_cols;
+    if (p3_tracing()) p3_note_kernel(half_cols ? "ln_bwd_half_kernel" : "ln_bwd_kernel");
     const int nblk = (int)grid.x;
     const int64_t slab_floats = (int64_t)nblk * 2 * cols, tmp_floats = (int64_t)p3_ceil_div(nblk, 128) * 2 * cols;
     // p3_reduce_defer active: the partials are parked and added with every other parked set by ONE p3_reduce_flush launch (42 reduce launches less per train step)

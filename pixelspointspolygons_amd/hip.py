@@ -518,15 +518,26 @@ def _attn_desc(q, k, v, o, heads, scale, causal, key_bias, lse, drop=None, drop_
     return d
 
 
-def attention(q, k, v, heads, scale, causal=False, key_bias=None, need_lse=False, drop=None, drop_rows=None, out_planes=None):
+def attention(q, k, v, heads, scale, causal=False, key_bias=None, need_lse=False, drop=None, drop_rows=None, out_planes=None, out=None, lse_out=None):
     """q [B,Lq,H*D], k/v [B,Lk,H*D] (arbitrary batch/row strides, unit inner stride) -> o [B,Lq,H*D].
+    out: the tensor that receives o (q's shape and dtype, unit inner stride, batch and row strides free: a view of a larger buffer); default a new dense one.
+    lse_out (with need_lse): the contiguous float32 [B, heads, Lq] tensor that receives the log-sum-exp rows.
     out_planes (fp32x3 scope): a Planes [B * Lq, H*D] that receives the output as planes too (the output projection's operand), written by the same launch."""
     _dev(q)
     for t in (q, k, v):
         if t.stride(2) != 1:
             raise P3Error("attention: inner stride must be 1")
-    o = torch.empty((q.shape[0], q.shape[1], q.shape[2]), dtype=q.dtype, device=q.device)
-    lse = torch.empty((q.shape[0], heads, q.shape[1]), dtype=torch.float32, device=q.device) if need_lse else None
+    if out is None:
+        o = torch.empty((q.shape[0], q.shape[1], q.shape[2]), dtype=q.dtype, device=q.device)
+    else:
+        if out.shape != q.shape or out.dtype != q.dtype or out.device != q.device or out.stride(2) != 1:
+            raise P3Error("attention: out must have q's shape, dtype and device and unit inner stride")
+        o = out
+    lse = None
+    if need_lse:
+        lse = lse_out if lse_out is not None else torch.empty((q.shape[0], heads, q.shape[1]), dtype=torch.float32, device=q.device)
+        if tuple(lse.shape) != (q.shape[0], heads, q.shape[1]) or lse.dtype != torch.float32 or not lse.is_contiguous():
+            raise P3Error("attention: lse_out must be a contiguous float32 [B, heads, Lq] tensor")
     d = _attn_desc(q, k, v, o, heads, scale, causal, key_bias, lse, drop, drop_rows)
     if out_planes is not None:
         op = out_planes
