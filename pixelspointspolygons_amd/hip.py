@@ -1,7 +1,11 @@
-"""Thin tensor-level bindings of the C-ABI in include/p3hip.h (PyTorch = device memory + streams only)."""
+"""Thin tensor-level bindings of the C-ABI in include/p3hip.h (PyTorch = device memory + streams only).
+
+The library arrives declared from that header (_lib.declare: argtypes and restype of every function), so a call passes plain Python numbers, ptr(tensor),
+stream() and byref(descriptor); ctypes converts each to the parameter's C type and refuses what does not fit."""
 import ctypes
 import math
-from ctypes import POINTER, Structure, byref, c_float, c_int, c_int64, c_void_p
+import os
+from ctypes import Structure, byref, c_float, c_int, c_int64, c_void_p
 
 import torch
 
@@ -20,11 +24,11 @@ class _KernelTimer:
 
     def enable(self):
         self.on, self.pending = True, []
-        lib().p3_trace_kernels(c_int(1))          # p3_gemm records which device kernel it picked (p3_last_kernel)
+        lib().p3_trace_kernels(1)          # p3_gemm records which device kernel it picked (p3_last_kernel)
 
     def disable(self):
         self.on = False
-        lib().p3_trace_kernels(c_int(0))
+        lib().p3_trace_kernels(0)
 
     def begin(self):
         if not self.on:
@@ -170,12 +174,11 @@ def ptr(t):
 # Deterministic reductions (csrc/det_reduce.hip): P3_DETERMINISTIC = 0 off | 1 (default) every fp32 (parity-mode) launch | 2 bf16 too.
 # A 128 MB scratch (P3_SCRATCH_MB) for workgroup / tile partials is registered with the library at the first launch of the process (one
 # device per process); the GEMM's BatchNorm column sums use it in every dtype (per-tile partials + fixed-order reduce, gemm.hip launch_bk).
-import os as _os0
-DETERMINISTIC = int(_os0.environ.get("P3_DETERMINISTIC", "1"))
+DETERMINISTIC = int(os.environ.get("P3_DETERMINISTIC", "1"))
 _det_state = {"buf": None}
-SIDE_STREAMS = [k for k in ("sn", "dw", "stem") if _os0.environ.get("P3_SIDE_" + k.upper(), "0") == "1"]     # ops.SIDE: branches enqueued on side streams
+SIDE_STREAMS = [k for k in ("sn", "dw", "stem") if os.environ.get("P3_SIDE_" + k.upper(), "0") == "1"]     # ops.SIDE: branches enqueued on side streams
 SCRATCH_REGIONS = 1 + len(SIDE_STREAMS)
-_DET_SCRATCH_BYTES = int(_os0.environ.get("P3_SCRATCH_MB", "128")) << 20     # per-tile BatchNorm partials of the tall ScoreNet / FFL GEMMs: <= 103 MB
+_DET_SCRATCH_BYTES = int(os.environ.get("P3_SCRATCH_MB", "128")) << 20     # per-tile BatchNorm partials of the tall ScoreNet / FFL GEMMs: <= 103 MB
 
 
 def set_deterministic(level):
@@ -185,7 +188,7 @@ def set_deterministic(level):
     if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
         raise P3Error("set_deterministic during a hipGraph capture")
     if DETERMINISTIC <= 0:
-        check(lib().p3_set_deterministic(c_void_p(0), c_int64(0), c_int(0)), "p3_set_deterministic")
+        check(lib().p3_set_deterministic(None, 0, 0), "p3_set_deterministic")
         _det_state["buf"] = False
         return
     buf = _det_state["buf"]
@@ -193,9 +196,9 @@ def set_deterministic(level):
         buf = _det_state.get("keep")
         if buf is None:        # one region per launch stream (SCRATCH_REGIONS: 1 + the side streams switched on, ops.SIDE)
             buf = torch.empty(_DET_SCRATCH_BYTES * SCRATCH_REGIONS, dtype=torch.uint8, device="cuda")
-            check(lib().p3_scratch_regions(c_int(SCRATCH_REGIONS)), "p3_scratch_regions")
+            check(lib().p3_scratch_regions(SCRATCH_REGIONS), "p3_scratch_regions")
     _det_state["buf"] = _det_state["keep"] = buf      # never freed: captured hipGraphs hold its address
-    check(lib().p3_set_deterministic(c_void_p(buf.data_ptr()), c_int64(buf.numel()), c_int(1 if DETERMINISTIC >= 2 else 0)), "p3_set_deterministic")
+    check(lib().p3_set_deterministic(ptr(buf), buf.numel(), 1 if DETERMINISTIC >= 2 else 0), "p3_set_deterministic")
 
 
 def det_on(t):
@@ -207,7 +210,7 @@ _cur_stream = [None]
 
 
 def register_side_stream(s):
-    check(0 if lib().p3_scratch_side_stream(c_void_p(s.cuda_stream)) > 0 else -1, "p3_scratch_side_stream")
+    check(0 if lib().p3_scratch_side_stream(s.cuda_stream) > 0 else -1, "p3_scratch_side_stream")
     _cur_stream[0] = None
 
 
@@ -218,7 +221,7 @@ def stream():
     h = torch.cuda.current_stream().cuda_stream
     if h != _cur_stream[0]:
         _cur_stream[0] = h
-        lib().p3_scratch_stream(c_void_p(h))
+        lib().p3_scratch_stream(h)
     return c_void_p(h)
 
 
@@ -239,7 +242,7 @@ def _drop(spec):
     return d
 
 
-W_PLANES = [_os0.environ.get("P3_W_PLANES", "0") == "1"]      # fp32x3: the register-staged GEMM takes the weight as planes when the caller has them.  OFF: measured no gain (r06, profiles/r06_w_planes_colsum_park_ab.txt: 65.55 vs 65.65 ms same-box) - the option and its test stay
+W_PLANES = [os.environ.get("P3_W_PLANES", "0") == "1"]      # fp32x3: the register-staged GEMM takes the weight as planes when the caller has them.  OFF: measured no gain (r06, profiles/r06_w_planes_colsum_park_ab.txt: 65.55 vs 65.65 ms same-box) - the option and its test stay
 
 
 class GemmDesc(Structure):
@@ -330,7 +333,7 @@ def gemm(a, w, *, bias=None, act=ACT_NONE, residual=None, out=None, out_dtype=No
             d.bwd_scale = bscale
     ev = KTIMER.begin()
     if variant is not None:
-        check(lib().p3_gemm_dma(ptr(a), ptr(w), ptr(out), byref(d), c_int(int(variant)), stream()), "p3_gemm_dma")
+        check(lib().p3_gemm_dma(ptr(a), ptr(w), ptr(out), byref(d), int(variant), stream()), "p3_gemm_dma")
     else:
         check(lib().p3_gemm(ptr(a), ptr(wpl[0] if wpl is not None else w), ptr(out), byref(d), stream()), "p3_gemm")
     if ev is not None:
@@ -367,8 +370,8 @@ def layernorm(x, gamma, beta, eps, out_dtype=None, save_stats=False, out=None):
     if save_stats:
         mean = torch.empty(rows, dtype=torch.float32, device=x.device)
         rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
-    check(lib().p3_layernorm(ptr(x2), ptr(gamma), ptr(beta), ptr(o2), c_int64(rows), c_int(cols), c_int(x2.stride(0)),
-                             c_int(o2.stride(0)), c_float(eps), c_int(dt(x)), c_int(dt(out)), ptr(mean), ptr(rstd),
+    check(lib().p3_layernorm(ptr(x2), ptr(gamma), ptr(beta), ptr(o2), rows, cols, x2.stride(0),
+                             o2.stride(0), eps, dt(x), dt(out), ptr(mean), ptr(rstd),
                              stream()), "p3_layernorm")
     return (out, mean, rstd) if save_stats else out
 
@@ -384,11 +387,11 @@ _park = {"buf": None}
 def param_reduce_arena(mb=None):
     """register (once per process) the arena deferred parameter-gradient reduces park their partials in (p3_reduce_defer); P3_DEFER_MB, default 192"""
     if _park["buf"] is None:
-        mb = int(_os0.environ.get("P3_DEFER_MB", "192")) if mb is None else mb
+        mb = int(os.environ.get("P3_DEFER_MB", "192")) if mb is None else mb
         if mb <= 0:
             return False
         _park["buf"] = torch.empty(mb * (1 << 20) // 4, dtype=torch.float32, device="cuda")
-        check(lib().p3_reduce_defer(ptr(_park["buf"]), c_int64(_park["buf"].numel())), "p3_reduce_defer")
+        check(lib().p3_reduce_defer(ptr(_park["buf"]), _park["buf"].numel()), "p3_reduce_defer")
     return True
 
 
@@ -398,12 +401,12 @@ _tn_park = {"buf": None}
 def tn_defer_arena(mb=None):
     """register (once per process) the arena the deterministic weight-gradient GEMMs park their split-M partial tiles in (p3_tn_defer); P3_TN_DEFER_MB, default 4096 (r06: the 128 x 384 weight-gradient tile runs 21 - 28 splits per launch: 2 GB of partial tiles per backward pass of the 12 blocks)"""
     if _tn_park["buf"] is None:
-        mb = int(_os0.environ.get("P3_TN_DEFER_MB", "4096")) if mb is None else mb
+        mb = int(os.environ.get("P3_TN_DEFER_MB", "4096")) if mb is None else mb
         if mb <= 0:
             _tn_park["buf"] = False
             return False
         _tn_park["buf"] = torch.empty(mb * (1 << 20) // 4, dtype=torch.float32, device="cuda")
-        check(lib().p3_tn_defer(ptr(_tn_park["buf"]), c_int64(_tn_park["buf"].numel())), "p3_tn_defer")
+        check(lib().p3_tn_defer(ptr(_tn_park["buf"]), _tn_park["buf"].numel()), "p3_tn_defer")
     return _tn_park["buf"] is not False
 
 
@@ -413,12 +416,12 @@ def tn_defer_release():
     buf = _tn_park["buf"]
     if buf is not None and buf is not False:
         lib().p3_tn_drop()
-        check(lib().p3_tn_defer(ptr(None), c_int64(0)), "p3_tn_defer")
+        check(lib().p3_tn_defer(ptr(None), 0), "p3_tn_defer")
     _tn_park["buf"] = None
 
 
-COLSUM_PARK = _os0.environ.get("P3_COLSUM_PARK", "1") != "0"   # bias-gradient column sums of the weight-gradient GEMMs park with the deferred reduces (A/B switch)
-CONV_PARK = _os0.environ.get("P3_CONV_PARK", "1") != "0"     # the nine shifted weight-gradient products of a 3 x 3 convolution park their partial tiles, one flush (A/B switch)
+COLSUM_PARK = os.environ.get("P3_COLSUM_PARK", "1") != "0"   # bias-gradient column sums of the weight-gradient GEMMs park with the deferred reduces (A/B switch)
+CONV_PARK = os.environ.get("P3_CONV_PARK", "1") != "0"     # the nine shifted weight-gradient products of a 3 x 3 convolution park their partial tiles, one flush (A/B switch)
 
 
 class tn_parking:
@@ -433,16 +436,16 @@ class tn_parking:
 
     def __enter__(self):
         if self.on:
-            lib().p3_tn_defer_enable(c_int(1))
+            lib().p3_tn_defer_enable(1)
         if self.on_colsum:
-            lib().p3_reduce_defer_enable(c_int(1))
+            lib().p3_reduce_defer_enable(1)
         return self
 
     def __exit__(self, *exc):
         if self.on:
-            lib().p3_tn_defer_enable(c_int(0))
+            lib().p3_tn_defer_enable(0)
         if self.on_colsum:
-            lib().p3_reduce_defer_enable(c_int(0))
+            lib().p3_reduce_defer_enable(0)
         return False
 
 
@@ -482,15 +485,15 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dx_dtype=None, dgamma=None, dbeta=No
     dspec = _drop(lo_drop)
     park = park and dgamma is not None and param_reduce_arena()
     if park:
-        lib().p3_reduce_defer_enable(c_int(1))
+        lib().p3_reduce_defer_enable(1)
     try:
         check(lib().p3_layernorm_bwd_lo_drop(ptr(dy2), ptr(x2), ptr(gamma), ptr(mean), ptr(rstd), ptr(dres), ptr(dx), ptr(lo),
                                              byref(dspec) if lo_drop is not None else None, ptr(dgamma), ptr(dbeta),
-                                             c_int64(rows), c_int(cols), c_int(dt(dy2)), c_int(dt(x2)), c_int(dt(dx)), stream()),
+                                             rows, cols, dt(dy2), dt(x2), dt(dx), stream()),
               "p3_layernorm_bwd")
     finally:
         if park:
-            lib().p3_reduce_defer_enable(c_int(0))
+            lib().p3_reduce_defer_enable(0)
     return (dx, lo) if want_lo else dx
 
 
@@ -601,28 +604,33 @@ def pillar_stem(values, offsets, w1, bn1, w2, bn2, out, *, B, grid, voxel, zmax,
     if w2.dtype != out.dtype:
         raise P3Error("pillar_stem: w2 dtype must equal the canvas dtype")
     L = lib()
-    L.p3_pillar_stem_workspace_bytes.restype = c_int64
     nbytes = L.p3_pillar_stem_workspace_bytes(byref(d))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=values.device) if keep_workspace else workspace(nbytes, values.device, "pillar")
     args = (ptr(values), ptr(offsets), ptr(w1), ptr(bn1[0]), ptr(bn1[1]), ptr(bn1[2]), ptr(bn1[3]), ptr(w2),
             ptr(bn2[0]), ptr(bn2[1]), ptr(bn2[2]), ptr(bn2[3]), ptr(out), ptr(ws), byref(d))
     if phases is not None:
-        check(L.p3_pillar_stem_phased(*args, c_int(int(phases)), stream()), "p3_pillar_stem")
+        check(L.p3_pillar_stem_phased(*args, int(phases), stream()), "p3_pillar_stem")
     elif sync is None or not training:
         check(L.p3_pillar_stem(*args, stream()), "p3_pillar_stem")
     else:   # SyncBatchNorm: all-reduce the pillar count / BatchNorm sums between the phases
         sec = _pillar_sections(ws, d)
-        check(L.p3_pillar_stem_phased(*args, c_int(1), stream()), "p3_pillar_stem")
+        check(L.p3_pillar_stem_phased(*args, 1, stream()), "p3_pillar_stem")
         sync(sec["totals"], sec["sums1"])
-        check(L.p3_pillar_stem_phased(*args, c_int(2), stream()), "p3_pillar_stem")
+        check(L.p3_pillar_stem_phased(*args, 2, stream()), "p3_pillar_stem")
         sync(sec["sums2"])
-        check(L.p3_pillar_stem_phased(*args, c_int(4), stream()), "p3_pillar_stem")
+        check(L.p3_pillar_stem_phased(*args, 4, stream()), "p3_pillar_stem")
     return (out, ws, d) if keep_workspace else out
 
 
-def _pillar_sections(ws, d):
+def _pillar_layout(d):
+    """byte offsets of the 17 sections of a stem workspace (p3_pillar_stem_layout)"""
     off = (c_int64 * 17)()
     check(lib().p3_pillar_stem_layout(byref(d), off), "p3_pillar_stem_layout")
+    return off
+
+
+def _pillar_sections(ws, d):
+    off = _pillar_layout(d)
     sect = lambda o, n, dtype: ws[o:o + 4 * n].view(dtype)
     return dict(totals=sect(off[13], 1, torch.int32), sums1=sect(off[14], 64, torch.float32), sums2=sect(off[15], 2 * d.C, torch.float32),
                 acc1_stat=sect(off[16] + 4 * 520, 64, torch.float32))
@@ -633,8 +641,7 @@ def pillar_tables(ws, d):
     sorted [total_points] global point ids grouped by pillar (ascending id inside a pillar), and per pillar slot b * max_voxels + s
     (s = rank of the kept pillar in ascending hash order): vox_xy (cy * nx + cx, bit 30 = the scatter skips it because the top-z pillar
     of the same (x, y) overwrites it), vox_start (first position in `sorted`), vox_cnt (= num_points, capped), vox_row; nvox [B]."""
-    off = (c_int64 * 17)()
-    check(lib().p3_pillar_stem_layout(byref(d), off), "p3_pillar_stem_layout")
+    off = _pillar_layout(d)
     nv = d.B * d.max_voxels
     sect = lambda o, n: ws[o:o + 4 * n].view(torch.int32)
     return dict(sorted=sect(off[0], max(int(d.total_points), 1)), vox_xy=sect(off[1], nv), vox_start=sect(off[2], nv), vox_cnt=sect(off[3], nv),
@@ -649,19 +656,19 @@ def pillar_stem_bwd(dcanvas, w1, g1, w2t, g2, ws, d, sync=None):
     db2, dg2 = dgb2[:C], dgb2[C:]
     if dt(dcanvas) != (F32 if d.dtype == F32X3 else d.dtype):
         raise P3Error("pillar_stem_bwd: canvas gradient dtype differs from the forward's")
-    args = (ptr(dcanvas), c_int(dcanvas.stride(-2)), ptr(w1), ptr(g1), ptr(w2t), ptr(g2), ptr(ws), byref(d), ptr(dw1),
+    args = (ptr(dcanvas), dcanvas.stride(-2), ptr(w1), ptr(g1), ptr(w2t), ptr(g2), ptr(ws), byref(d), ptr(dw1),
             ptr(dg1), ptr(db1), ptr(dw2), ptr(dg2), ptr(db2))
     L = lib()
     if sync is None or not d.training:
         check(L.p3_pillar_stem_bwd(*args, stream()), "p3_pillar_stem_bwd")
     else:
-        check(L.p3_pillar_stem_bwd_phased(*args, ptr(None), ptr(None), c_int(1), stream()), "p3_pillar_stem_bwd")
+        check(L.p3_pillar_stem_bwd_phased(*args, ptr(None), ptr(None), 1, stream()), "p3_pillar_stem_bwd")
         stat2 = dgb2.clone()
         sync(stat2)
-        check(L.p3_pillar_stem_bwd_phased(*args, ptr(stat2), ptr(None), c_int(2), stream()), "p3_pillar_stem_bwd")
+        check(L.p3_pillar_stem_bwd_phased(*args, ptr(stat2), ptr(None), 2, stream()), "p3_pillar_stem_bwd")
         stat1 = _pillar_sections(ws, d)["acc1_stat"].clone()
         sync(stat1)
-        check(L.p3_pillar_stem_bwd_phased(*args, ptr(stat2), ptr(stat1), c_int(4), stream()), "p3_pillar_stem_bwd")
+        check(L.p3_pillar_stem_bwd_phased(*args, ptr(stat2), ptr(stat1), 4, stream()), "p3_pillar_stem_bwd")
     return dw1, dg1, db1, dw2, dg2, db2
 
 
@@ -670,8 +677,7 @@ def patchify(img, P, dtype):
     _dev(img)
     B, Cin, H, W = img.shape
     out = torch.empty((B * (H // P) * (W // P), Cin * P * P), dtype=dtype, device=img.device)
-    check(lib().p3_patchify(ptr(img), ptr(out), c_int(B), c_int(Cin), c_int(H), c_int(W), c_int(P), c_int(dt(out)), stream()),
-          "p3_patchify")
+    check(lib().p3_patchify(ptr(img), ptr(out), B, Cin, H, W, P, dt(out), stream()), "p3_patchify")
     return out
 
 
@@ -680,8 +686,7 @@ def patchify_ld(img, P, dtype, ldk):
     _dev(img)
     B, Cin, H, W = img.shape
     out = torch.empty((B * (H // P) * (W // P), ldk), dtype=dtype, device=img.device)
-    check(lib().p3_patchify_ld(ptr(img), ptr(out), c_int(B), c_int(Cin), c_int(H), c_int(W), c_int(P), c_int(ldk), c_int(dt(out)), stream()),
-          "p3_patchify_ld")
+    check(lib().p3_patchify_ld(ptr(img), ptr(out), B, Cin, H, W, P, ldk, dt(out), stream()), "p3_patchify_ld")
     return out
 
 
@@ -712,8 +717,7 @@ def posembed_resample(table, wy, wx, n_in, n_out):
     if table.dtype != torch.float32 or table.shape[0] != 1 + n_in * n_in or tuple(wy.shape) != (n_out, n_in) or tuple(wx.shape) != (n_out, n_in):
         raise P3Error("posembed_resample: fp32 table [1 + n_in^2, D] and tap tables [n_out, n_in] expected")
     out = torch.empty((1 + n_out * n_out, D), dtype=torch.float32, device=table.device)
-    check(lib().p3_posembed_resample(ptr(table.contiguous()), ptr(wy), ptr(wx), ptr(out), c_int(n_in), c_int(n_out), c_int(D), stream()),
-          "p3_posembed_resample")
+    check(lib().p3_posembed_resample(ptr(table.contiguous()), ptr(wy), ptr(wx), ptr(out), n_in, n_out, D, stream()), "p3_posembed_resample")
     return out
 
 
@@ -723,8 +727,7 @@ def posembed_resample_bwd(dout, wy, wx, n_in, n_out):
     if dout.dtype != torch.float32 or dout.shape[0] != 1 + n_out * n_out or tuple(wy.shape) != (n_out, n_in) or tuple(wx.shape) != (n_out, n_in):
         raise P3Error("posembed_resample_bwd: fp32 gradient [1 + n_out^2, D] and tap tables [n_out, n_in] expected")
     dtable = torch.empty((1 + n_in * n_in, D), dtype=torch.float32, device=dout.device)
-    check(lib().p3_posembed_resample_bwd(ptr(dout.contiguous()), ptr(wy), ptr(wx), ptr(dtable), c_int(n_in), c_int(n_out), c_int(D), stream()),
-          "p3_posembed_resample_bwd")
+    check(lib().p3_posembed_resample_bwd(ptr(dout.contiguous()), ptr(wy), ptr(wx), ptr(dtable), n_in, n_out, D, stream()), "p3_posembed_resample_bwd")
     return dtable
 
 
@@ -736,8 +739,7 @@ def layerscale_fold(gamma, W, b=None):
         raise P3Error("layerscale_fold: fp32 W [N, K], gamma [N] (and b [N]) expected")
     Wf = torch.empty((N, K), dtype=torch.float32, device=W.device)
     bf = torch.empty(N, dtype=torch.float32, device=W.device) if b is not None else None
-    check(lib().p3_layerscale_fold(ptr(gamma.contiguous()), ptr(W.contiguous()), ptr(b), ptr(Wf), ptr(bf), c_int(N), c_int(K), stream()),
-          "p3_layerscale_fold")
+    check(lib().p3_layerscale_fold(ptr(gamma.contiguous()), ptr(W.contiguous()), ptr(b), ptr(Wf), ptr(bf), N, K, stream()), "p3_layerscale_fold")
     return Wf, bf
 
 
@@ -751,15 +753,15 @@ def layerscale_fold_bwd(gamma, W, b, dWf, dbf):
     db = torch.empty(N, dtype=torch.float32, device=W.device) if b is not None else None
     dgamma = torch.empty(N, dtype=torch.float32, device=W.device)
     check(lib().p3_layerscale_fold_bwd(ptr(gamma.contiguous()), ptr(W.contiguous()), ptr(b), ptr(dWf.contiguous()),
-                                       ptr(dbf.contiguous() if dbf is not None else None), ptr(dW), ptr(db), ptr(dgamma), c_int(N), c_int(K), stream()),
+                                       ptr(dbf.contiguous() if dbf is not None else None), ptr(dW), ptr(db), ptr(dgamma), N, K, stream()),
           "p3_layerscale_fold_bwd")
     return dW, db, dgamma
 
 
 def tokens_assemble(src, cls, pos, B, np_, D, scale=None, shift=None, src_ld=None):
     x = torch.empty((B, np_ + 1, D), dtype=torch.float32, device=src.device)
-    check(lib().p3_tokens_assemble(ptr(src), c_int(src.stride(-2) if src_ld is None else src_ld), c_int(dt(src)), ptr(scale),
-                                   ptr(shift), ptr(cls), ptr(pos), ptr(x), c_int(B), c_int(np_), c_int(D), stream()),
+    check(lib().p3_tokens_assemble(ptr(src), src.stride(-2) if src_ld is None else src_ld, dt(src), ptr(scale),
+                                   ptr(shift), ptr(cls), ptr(pos), ptr(x), B, np_, D, stream()),
           "p3_tokens_assemble")
     return x
 
@@ -768,8 +770,7 @@ def pool_pos(y, pos, Dout, out_dtype, want_nopos=False):
     B, L, Din = y.shape
     out = torch.empty((B, L - 1, Dout), dtype=out_dtype, device=y.device)
     nop = torch.empty_like(out) if want_nopos else None
-    check(lib().p3_pool_pos(ptr(y), c_int(dt(y)), ptr(pos), ptr(out), ptr(nop), c_int(dt(out)), c_int(B), c_int(L - 1),
-                            c_int(Din), c_int(Dout), stream()), "p3_pool_pos")
+    check(lib().p3_pool_pos(ptr(y), dt(y), ptr(pos), ptr(out), ptr(nop), dt(out), B, L - 1, Din, Dout, stream()), "p3_pool_pos")
     return (out, nop) if want_nopos else out
 
 
@@ -778,22 +779,19 @@ def embed_tokens(tokens, emb, pos, pad_idx, dtype):
     D = emb.shape[1]
     x = torch.empty((B, L, D), dtype=dtype, device=tokens.device)
     kb = torch.empty((B, L), dtype=torch.float32, device=tokens.device)
-    check(lib().p3_embed_tokens(ptr(tokens), ptr(emb), ptr(pos), ptr(x), ptr(kb), c_int(B), c_int(L), c_int(D), c_int(pad_idx),
-                                c_int(dt(x)), stream()), "p3_embed_tokens")
+    check(lib().p3_embed_tokens(ptr(tokens), ptr(emb), ptr(pos), ptr(x), ptr(kb), B, L, D, pad_idx, dt(x), stream()), "p3_embed_tokens")
     return x, kb
 
 
 def pair_mean(feats, N):
     B, L, D = feats.shape
     out = torch.empty((B, N, D), dtype=feats.dtype, device=feats.device)
-    check(lib().p3_pair_mean(ptr(feats), ptr(out), c_int(B), c_int(L), c_int(N), c_int(D), c_int(dt(feats)), stream()),
-          "p3_pair_mean")
+    check(lib().p3_pair_mean(ptr(feats), ptr(out), B, L, N, D, dt(feats), stream()), "p3_pair_mean")
     return out
 
 
 def pair_stats(U, V, B, N, sums):
-    check(lib().p3_pair_stats(ptr(U), ptr(V), c_int(B), c_int(N), c_int(U.shape[-1]), c_int(dt(U)), ptr(sums), stream()),
-          "p3_pair_stats")
+    check(lib().p3_pair_stats(ptr(U), ptr(V), B, N, U.shape[-1], dt(U), ptr(sums), stream()), "p3_pair_stats")
 
 
 def bn_finalize(sums, count, gamma, beta, rmean, rvar, eps, momentum, training, save=False):
@@ -802,15 +800,14 @@ def bn_finalize(sums, count, gamma, beta, rmean, rvar, eps, momentum, training, 
     shift = torch.empty_like(scale)
     sm = torch.empty_like(scale) if save else None
     sr = torch.empty_like(scale) if save else None
-    check(lib().p3_bn_finalize(ptr(sums), c_int(C), c_float(count), ptr(gamma), ptr(beta), ptr(rmean), ptr(rvar), c_float(eps),
-                               c_float(momentum), c_int(int(training)), ptr(scale), ptr(shift), ptr(sm), ptr(sr), stream()),
+    check(lib().p3_bn_finalize(ptr(sums), C, count, ptr(gamma), ptr(beta), ptr(rmean), ptr(rvar), eps,
+                               momentum, int(training), ptr(scale), ptr(shift), ptr(sm), ptr(sr), stream()),
           "p3_bn_finalize")
     return (scale, shift, sm, sr) if save else (scale, shift)
 
 
 def score_out(H3, scale, shift, w4, b4, out, B, N, transpose_acc):
-    check(lib().p3_score_out(ptr(H3), c_int(dt(H3)), ptr(scale), ptr(shift), ptr(w4), ptr(b4), ptr(out), c_int(B), c_int(N),
-                             c_int(H3.shape[-1]), c_int(int(transpose_acc)), stream()), "p3_score_out")
+    check(lib().p3_score_out(ptr(H3), dt(H3), ptr(scale), ptr(shift), ptr(w4), ptr(b4), ptr(out), B, N, H3.shape[-1], int(transpose_acc), stream()), "p3_score_out")
     return out
 
 
@@ -820,15 +817,14 @@ def sinkhorn(scores, alpha, iters, want_perm=True, want_z=False, want_hist=False
     perm = torch.empty((B, m, n), dtype=torch.float32, device=dev) if want_perm else None
     z = torch.empty((B, m + 1, n + 1), dtype=torch.float32, device=dev) if want_z else None
     hist = torch.empty((B, iters, m + n + 2), dtype=torch.float32, device=dev) if want_hist else None
-    check(lib().p3_sinkhorn(ptr(scores), ptr(alpha), c_int(B), c_int(m), c_int(n), c_int(iters), ptr(perm), ptr(z), ptr(hist),
-                            stream()), "p3_sinkhorn")
+    check(lib().p3_sinkhorn(ptr(scores), ptr(alpha), B, m, n, iters, ptr(perm), ptr(z), ptr(hist), stream()), "p3_sinkhorn")
     return perm, z, hist
 
 
 def argmax(x):
     rows, cols = x.shape
     out = torch.empty(rows, dtype=torch.int64, device=x.device)
-    check(lib().p3_argmax(ptr(x), ptr(out), c_int(rows), c_int(cols), c_int(x.stride(0)), stream()), "p3_argmax")
+    check(lib().p3_argmax(ptr(x), ptr(out), rows, cols, x.stride(0), stream()), "p3_argmax")
     return out
 
 
@@ -904,8 +900,7 @@ def assignment(scores, maximize=True, want_perm=True):
     col = torch.empty((B, N), dtype=torch.int32, device=sc.device)
     perm = torch.empty((B, N, N), dtype=torch.float32, device=sc.device) if want_perm else None
     status = torch.empty(B, dtype=torch.int32, device=sc.device)
-    check(lib().p3_assignment(ptr(sc), c_int(B), c_int(N), c_int(1 if maximize else 0), ptr(col), ptr(perm), ptr(status), stream()),
-          "p3_assignment")
+    check(lib().p3_assignment(ptr(sc), B, N, 1 if maximize else 0, ptr(col), ptr(perm), ptr(status), stream()), "p3_assignment")
     return col, perm, status
 
 
@@ -920,8 +915,7 @@ def image_prepare(src_u8, group=None, sub=(0.0, 0.0, 0.0), mul=(1.0 / 255.0,) * 
         out = torch.empty((B, C, H, W), dtype=torch.float32, device=src.device)
     subc = (c_float * 4)(*([float(v) for v in sub] + [0.0] * 4)[:4])
     mulc = (c_float * 4)(*([float(v) for v in mul] + [1.0] * 4)[:4])
-    check(lib().p3_image_prepare(ptr(src), ptr(group), ptr(out), c_int(B), c_int(H), c_int(W), c_int(C), ctypes.cast(subc, c_void_p),
-                                 ctypes.cast(mulc, c_void_p), stream()), "p3_image_prepare")
+    check(lib().p3_image_prepare(ptr(src), ptr(group), ptr(out), B, H, W, C, subc, mulc, stream()), "p3_image_prepare")
     return out
 
 
@@ -941,7 +935,7 @@ def ffl_targets_prepare(gt_u8=None, angle_u8=None, distances=None, sizes=None, g
     sizes = c(sizes.float()) if sizes is not None else None
     mk = lambda t, ch: torch.empty((B, ch, H, W), dtype=torch.float32, device=dev) if t is not None else None
     o_gt, o_an, o_di, o_si = mk(gt_u8, 3), mk(angle_u8, 1), mk(distances, 1), mk(sizes, 1)
-    check(lib().p3_ffl_targets_prepare(ptr(gt_u8), ptr(angle_u8), ptr(distances), ptr(sizes), ptr(group), c_int(B), c_int(H), c_int(W), ptr(o_gt),
+    check(lib().p3_ffl_targets_prepare(ptr(gt_u8), ptr(angle_u8), ptr(distances), ptr(sizes), ptr(group), B, H, W, ptr(o_gt),
                                        ptr(o_an), ptr(o_di), ptr(o_si), stream()), "p3_ffl_targets_prepare")
     out = {"gt_polygons_image": o_gt, "gt_crossfield_angle": o_an, "distances": o_di, "sizes": o_si}
     return {k: v for k, v in out.items() if v is not None}
@@ -952,8 +946,7 @@ def points_d4_(values, offsets, group, cx, cy):
     _dev(values)
     if values.dtype != torch.float32 or not values.is_contiguous() or values.shape[-1] != 3:
         raise P3Error("points_d4_: values must be contiguous float32 [T, 3]")
-    check(lib().p3_points_d4(ptr(values), ptr(offsets), ptr(group), c_int(offsets.numel() - 1), c_int64(values.shape[0]), c_float(cx),
-                             c_float(cy), stream()), "p3_points_d4")
+    check(lib().p3_points_d4(ptr(values), ptr(offsets), ptr(group), offsets.numel() - 1, values.shape[0], cx, cy, stream()), "p3_points_d4")
     return values
 
 
@@ -965,8 +958,7 @@ def ffl_loss(seg, crossfield, gt_polygons_image, gt_crossfield_angle, coef, bce_
     if ts[0].shape != (B, 1, H, W) or ts[1].shape != (B, 4, H, W) or ts[2].shape != (B, 3, H, W) or ts[3].numel() != B * H * W:
         raise P3Error(f"ffl_loss: shapes seg {tuple(seg.shape)} crossfield {tuple(crossfield.shape)} gt {tuple(gt_polygons_image.shape)} "
                       f"angle {tuple(gt_crossfield_angle.shape)}")
-    lib().p3_ffl_loss_workspace_bytes.restype = c_int64
-    ws = workspace(int(lib().p3_ffl_loss_workspace_bytes(c_int(B), c_int(H), c_int(W))), seg.device, "ffl_loss")
+    ws = workspace(int(lib().p3_ffl_loss_workspace_bytes(B, H, W)), seg.device, "ffl_loss")
     losses = torch.empty(6, dtype=torch.float32, device=seg.device)
     dseg = torch.empty_like(ts[0]) if need_grad else None
     dcf = torch.empty_like(ts[1]) if need_grad else None
@@ -974,8 +966,8 @@ def ffl_loss(seg, crossfield, gt_polygons_image, gt_crossfield_angle, coef, bce_
     sw = seg_weights.contiguous().float() if seg_weights is not None else None
     if sw is not None and sw.numel() != B * H * W:
         raise P3Error(f"ffl_loss: seg_weights must hold one weight per pixel of the seg channel, got {tuple(seg_weights.shape)}")
-    check(lib().p3_ffl_loss(ptr(ts[0]), ptr(ts[1]), ptr(ts[2]), ptr(ts[3]), ptr(sw), c_int(B), c_int(H), c_int(W), ctypes.cast(cc, c_void_p),
-                            c_float(bce_coef), c_float(dice_coef), ptr(losses), ptr(dseg), ptr(dcf), ptr(ws), stream()), "p3_ffl_loss")
+    check(lib().p3_ffl_loss(ptr(ts[0]), ptr(ts[1]), ptr(ts[2]), ptr(ts[3]), ptr(sw), B, H, W, cc,
+                            bce_coef, dice_coef, ptr(losses), ptr(dseg), ptr(dcf), ptr(ws), stream()), "p3_ffl_loss")
     return losses, dseg, dcf
 
 
@@ -987,7 +979,7 @@ def afm(lines, shape_info, height, width):
     B = si.shape[0]
     afmap = torch.empty((B, 2, height, width), dtype=torch.float32, device=si.device)
     lab = torch.empty((B, 1, height, width), dtype=torch.int32, device=si.device)
-    check(lib().p3_afm(ptr(ln), ptr(si), c_int(B), c_int(height), c_int(width), ptr(afmap), ptr(lab), stream()), "p3_afm")
+    check(lib().p3_afm(ptr(ln), ptr(si), B, height, width, ptr(afmap), ptr(lab), stream()), "p3_afm")
     return afmap, lab
 
 
@@ -1032,10 +1024,9 @@ def hisup_junctions(jloc, joff, scale_x=1.0, scale_y=1.0, shape=None):
     scores = torch.empty((B, 2 * HISUP_TOPK), dtype=torch.float32, device=dev)
     index = torch.empty((B, 2 * HISUP_TOPK), dtype=torch.int32, device=dev)
     counts = torch.empty((B, 2), dtype=torch.int32, device=dev)
-    lib().p3_hisup_junctions_workspace_bytes.restype = c_int64
-    ws = workspace(int(lib().p3_hisup_junctions_workspace_bytes(c_int(B), c_int(H), c_int(W))), dev, "hisup_junctions")
-    check(lib().p3_hisup_junctions(ptr(jl), c_int64(sl[0]), c_int64(sl[1]), c_int64(sl[2]), ptr(jo), c_int64(so[0]), c_int64(so[1]), c_int64(so[2]),
-                                   c_int(B), c_int(H), c_int(W), c_float(scale_x), c_float(scale_y), ptr(juncs), ptr(scores), ptr(index), ptr(counts),
+    ws = workspace(int(lib().p3_hisup_junctions_workspace_bytes(B, H, W)), dev, "hisup_junctions")
+    check(lib().p3_hisup_junctions(ptr(jl), sl[0], sl[1], sl[2], ptr(jo), so[0], so[1], so[2],
+                                   B, H, W, scale_x, scale_y, ptr(juncs), ptr(scores), ptr(index), ptr(counts),
                                    ptr(ws), stream()), "p3_hisup_junctions")
     return juncs, scores, index, counts
 
@@ -1058,9 +1049,8 @@ def hisup_regions_device(remask, max_regions=1024, shape=None, _guard=0):
                status=torch.empty(B, dtype=torch.int32, device=dev))
     if g:
         out["_arena"] = arena
-    lib().p3_hisup_regions_workspace_bytes.restype = c_int64
-    ws = workspace(int(lib().p3_hisup_regions_workspace_bytes(c_int(B), c_int(H), c_int(W), c_int(R))), dev, "hisup_regions")
-    check(lib().p3_hisup_regions(ptr(rm), c_int64(st[0]), c_int64(st[1]), c_int64(st[2]), c_int(B), c_int(H), c_int(W), c_int(R), ptr(out["mask"]),
+    ws = workspace(int(lib().p3_hisup_regions_workspace_bytes(B, H, W, R)), dev, "hisup_regions")
+    check(lib().p3_hisup_regions(ptr(rm), st[0], st[1], st[2], B, H, W, R, ptr(out["mask"]),
                                  ptr(out["labels"]), ptr(out["n_regions"]), ptr(area), ptr(bbox), ptr(score), ptr(out["status"]), ptr(ws), stream()),
           "p3_hisup_regions")
     return out
@@ -1089,10 +1079,9 @@ def hisup_val_loss(jloc, joff, mask, afm_pred, remask, t_jloc, t_joff, t_mask, t
     tj = t_jloc.contiguous().to(torch.int64)
     tt = [t.contiguous().float() for t in (t_joff, t_mask, t_afm)]
     losses = torch.empty(5, dtype=torch.float32, device=jloc.device)
-    lib().p3_hisup_val_loss_workspace_bytes.restype = c_int64
-    ws = workspace(int(lib().p3_hisup_val_loss_workspace_bytes(c_int(B), c_int(H), c_int(W))), jloc.device, "hisup_val_loss")
-    check(lib().p3_hisup_val_loss(ptr(f[0]), ptr(f[1]), ptr(f[2]), ptr(f[3]), ptr(f[4]), ptr(tj), ptr(tt[0]), ptr(tt[1]), ptr(tt[2]), c_int(B),
-                                  c_int(H), c_int(W), ptr(losses), ptr(ws), stream()), "p3_hisup_val_loss")
+    ws = workspace(int(lib().p3_hisup_val_loss_workspace_bytes(B, H, W)), jloc.device, "hisup_val_loss")
+    check(lib().p3_hisup_val_loss(ptr(f[0]), ptr(f[1]), ptr(f[2]), ptr(f[3]), ptr(f[4]), ptr(tj), ptr(tt[0]), ptr(tt[1]), ptr(tt[2]), B,
+                                  H, W, ptr(losses), ptr(ws), stream()), "p3_hisup_val_loss")
     return losses
 
 
@@ -1135,11 +1124,10 @@ def acm_optimize(pos, poly_slice, batch, is_endpoint, indicator, c0c2, data_coef
         max_len = int((poly_slice[:, 1] - poly_slice[:, 0]).max())
     ws = None
     if force_fallback or max_len > ACM_LDS_CAP or max_len <= 0:
-        lib().p3_acm_workspace_bytes.restype = c_int64
-        ws = workspace(int(lib().p3_acm_workspace_bytes(c_int64(N))), pos.device, "acm")
-    check(lib().p3_acm_optimize(ptr(pos), c_int64(N), ptr(sl), ptr(pb), c_int(P), ptr(ep), ptr(ind), ptr(cf), c_int(B), c_int(H), c_int(W), c_float(data_coef),
-                                c_float(length_coef), c_float(crossfield_coef), c_float(data_level), ctypes.c_double(poly_lr), c_int(int(warmup_iters)),
-                                ctypes.c_double(warmup_factor), c_int(int(first_iter)), c_int(int(steps)), c_int(int(max_len)), c_int(int(bool(force_fallback))),
+        ws = workspace(int(lib().p3_acm_workspace_bytes(N)), pos.device, "acm")
+    check(lib().p3_acm_optimize(ptr(pos), N, ptr(sl), ptr(pb), P, ptr(ep), ptr(ind), ptr(cf), B, H, W, data_coef,
+                                length_coef, crossfield_coef, data_level, poly_lr, int(warmup_iters),
+                                warmup_factor, int(first_iter), int(steps), int(max_len), int(bool(force_fallback)),
                                 ptr(out), ptr(ws), stream()), "p3_acm_optimize")
     return (pos, out) if losses else pos
 
@@ -1189,11 +1177,10 @@ def init_contours_device(indicator, level=0.5, max_vertices=None, max_contours=N
                status=_ic_out((1,), torch.int32, dev, g, arenas))
     if g:
         out["_arenas"] = arenas
-    lib().p3_init_contours_workspace_bytes.restype = c_int64
-    ws = workspace(int(lib().p3_init_contours_workspace_bytes(c_int(B), c_int(H), c_int(W))), dev, "init_contours")
+    ws = workspace(int(lib().p3_init_contours_workspace_bytes(B, H, W)), dev, "init_contours")
     sb, sr, sc = indicator.stride()
-    check(lib().p3_init_contours(ptr(indicator), c_int64(sb), c_int64(sr), c_int64(sc), c_int(B), c_int(H), c_int(W), ctypes.c_double(float(level)), c_int(nv),
-                                 c_int(nc), ptr(out["pos"]), ptr(out["poly_slice"]), ptr(out["poly_batch"]), ptr(out["batch"]), ptr(out["is_endpoint"]),
+    check(lib().p3_init_contours(ptr(indicator), sb, sr, sc, B, H, W, float(level), nv,
+                                 nc, ptr(out["pos"]), ptr(out["poly_slice"]), ptr(out["poly_batch"]), ptr(out["batch"]), ptr(out["is_endpoint"]),
                                  ptr(out["counts"]), ptr(out["n_contours"]), ptr(out["n_vertices"]), ptr(out["status"]), ptr(ws), stream()), "p3_init_contours")
     return out
 
@@ -1257,11 +1244,10 @@ def corner_split_device(pos, index, poly_slice, closed, poly_batch, c0c2, tol_pr
     p32, cf = pos.contiguous(), c0c2.contiguous().float()
     idx = None if index is None else index.to(torch.int64).contiguous()
     sl, cl, pb = poly_slice.to(torch.int64).contiguous(), closed.to(torch.uint8).contiguous(), poly_batch.to(torch.int32).contiguous()
-    lib().p3_corner_split_workspace_bytes.restype = c_int64
-    ws = workspace(int(lib().p3_corner_split_workspace_bytes(c_int64(E), c_int(P))), dev, "corner_split")
-    check(lib().p3_corner_split(ptr(p32), c_int64(N), ptr(idx), c_int64(K), ptr(sl), ptr(cl), ptr(pb), c_int(P), ptr(cf), c_int(B), c_int(H), c_int(W),
-                                ctypes.c_double(float(tol_pre)), ctypes.c_double(float(tol)), c_int(int(max_len or 0)), c_int(int(bool(force_fallback))),
-                                c_int(nv), c_int(nq), ptr(out["out_pos"]), ptr(out["out_src"]), ptr(out["piece_slice"]), ptr(out["piece_poly"]),
+    ws = workspace(int(lib().p3_corner_split_workspace_bytes(E, P)), dev, "corner_split")
+    check(lib().p3_corner_split(ptr(p32), N, ptr(idx), K, ptr(sl), ptr(cl), ptr(pb), P, ptr(cf), B, H, W,
+                                float(tol_pre), float(tol), int(max_len or 0), int(bool(force_fallback)),
+                                nv, nq, ptr(out["out_pos"]), ptr(out["out_src"]), ptr(out["piece_slice"]), ptr(out["piece_poly"]),
                                 ptr(out["piece_batch"]), ptr(out.get("stage_flags")), ptr(out["counts"]), ptr(out["status"]), ptr(ws), stream()),
           "p3_corner_split")
     return out
@@ -1303,7 +1289,7 @@ def asm_schedule(iter_num, knots, lr=0.1, gamma=0.995):
     """p3_asm_schedule (host only, needs no device): the (data, length, crossfield, lr) floats the kernel uses at iteration iter_num, as Python floats"""
     arr, nk = _asm_knots(knots)
     out = (ctypes.c_double * 4)()
-    check(lib().p3_asm_schedule(c_int(int(iter_num)), arr, c_int(nk), ctypes.c_double(lr), ctypes.c_double(gamma), out), "p3_asm_schedule")
+    check(lib().p3_asm_schedule(int(iter_num), arr, nk, lr, gamma, out), "p3_asm_schedule")
     return tuple(out)
 
 
@@ -1335,26 +1321,25 @@ def asm_optimize(pos, sq, plan, is_tip, batch, indicator, c0c2, knots, data_leve
     tip8, batch32 = is_tip.to(torch.uint8).contiguous(), i32(batch)
     ws = None
     if force_fallback or plan.max_comp > ASM_LDS_CAP or plan.max_comp <= 0:
-        lib().p3_asm_workspace_bytes.restype = c_int64
-        ws = workspace(int(lib().p3_asm_workspace_bytes(c_int64(N), c_int64(CN))), pos.device, "asm")
-    check(lib().p3_asm_optimize(ptr(pos), ptr(sq), c_int64(N), ptr(comp_ptr), c_int(C), ptr(cn_node), ptr(cn_occ), c_int64(CN),
-                                ptr(slot_nb), c_int64(S), ptr(tip8), ptr(batch32), ptr(ind), ptr(cf), c_int(B),
-                                c_int(H), c_int(W), c_float(data_level), arr, c_int(nk), ctypes.c_double(lr), ctypes.c_double(gamma), c_int(int(first_iter)),
-                                c_int(int(steps)), c_int(int(plan.max_comp)), c_int(int(bool(force_fallback))), ptr(grad_out), ptr(out), ptr(ws), stream()),
+        ws = workspace(int(lib().p3_asm_workspace_bytes(N, CN)), pos.device, "asm")
+    check(lib().p3_asm_optimize(ptr(pos), ptr(sq), N, ptr(comp_ptr), C, ptr(cn_node), ptr(cn_occ), CN,
+                                ptr(slot_nb), S, ptr(tip8), ptr(batch32), ptr(ind), ptr(cf), B,
+                                H, W, data_level, arr, nk, lr, gamma, int(first_iter),
+                                int(steps), int(plan.max_comp), int(bool(force_fallback)), ptr(grad_out), ptr(out), ptr(ws), stream()),
           "p3_asm_optimize")
     return (pos, out) if losses else pos
 
 
 def cast(a, dtype):
     out = torch.empty(a.shape, dtype=dtype, device=a.device)
-    check(lib().p3_cast(ptr(a.contiguous()), c_int(dt(a)), ptr(out), c_int(dt(out)), c_int64(a.numel()), stream()), "p3_cast")
+    check(lib().p3_cast(ptr(a.contiguous()), dt(a), ptr(out), dt(out), a.numel(), stream()), "p3_cast")
     return out
 
 
 def add_pos(x, pos):
     B, L, D = x.shape
     out = torch.empty_like(x)
-    check(lib().p3_add_pos(ptr(x), ptr(pos), ptr(out), c_int(B), c_int(L), c_int(D), c_int(dt(x)), stream()), "p3_add_pos")
+    check(lib().p3_add_pos(ptr(x), ptr(pos), ptr(out), B, L, D, dt(x), stream()), "p3_add_pos")
     return out
 
 
@@ -1374,7 +1359,7 @@ def attention_bwd(q, k, v, o, lse, do, heads, scale, causal=False, key_bias=None
         d.grad_planes, d.g_rs, d.g_bs, d.g_lo = 1, gp.ld, L * gp.ld, gp.cols
         delta = torch.empty((B, heads, L), dtype=torch.float32, device=q.device)
         base, es = gp.hi.data_ptr(), 2
-        check(lib().p3_attention_bwd(ptr(q), ptr(k), ptr(v), ptr(o), ptr(do), ptr(lse), c_void_p(base), c_void_p(base + D * es), c_void_p(base + 2 * D * es),
+        check(lib().p3_attention_bwd(ptr(q), ptr(k), ptr(v), ptr(o), ptr(do), ptr(lse), base, base + D * es, base + 2 * D * es,
                                      ptr(delta), byref(d), stream()), "p3_attention_bwd")
         return gp
     dq = torch.empty_like(q) if dq is None else dq
@@ -1415,10 +1400,10 @@ def gemm_tn(a, b, out=None, colsum_out=None):
     slabs, ns = _tn_slabs(N, K, a)
     ev = KTIMER.begin()
     if ev is not None:
-        lib().p3_trace_kernels(c_int(1))                        # forget the previous launch's name: an untraced kernel must not inherit it
-    check(lib().p3_gemm_tn_ex(ptr(a), ptr(b), ptr(out), c_int(M), c_int(N), c_int(K), c_int(a.stride(0)), c_int(b.stride(0)),
-                              c_int(out.stride(0)), c_int(dt_mm(a)), c_int(0), ptr(None), ptr(None), ptr(None), c_int(0), ptr(colsum_out),
-                              ptr(slabs), c_int(ns), stream()), "p3_gemm_tn")
+        lib().p3_trace_kernels(1)                        # forget the previous launch's name: an untraced kernel must not inherit it
+    check(lib().p3_gemm_tn_ex(ptr(a), ptr(b), ptr(out), M, N, K, a.stride(0), b.stride(0),
+                              out.stride(0), dt_mm(a), 0, ptr(None), ptr(None), ptr(None), 0, ptr(colsum_out),
+                              ptr(slabs), ns, stream()), "p3_gemm_tn")
     if ev is not None:                                          # operands once, the fp32 output tile once (split-M partials are not algorithmic)
         kname = lib().p3_last_kernel().decode() or f"gemm_tn_kernel<{'bf16' if dt(a) == BF16 else 'float'}, 0>"
         KTIMER.end(ev, kname, 2.0 * M * N * K, float(M * (N + K) * a.element_size() + N * K * 4))
@@ -1429,7 +1414,7 @@ def colsum(x, out=None):
     M, N = x.shape
     if out is None:
         out = torch.zeros(N, dtype=torch.float32, device=x.device)
-    check(lib().p3_colsum(ptr(x), ptr(out), c_int64(M), c_int(N), c_int(x.stride(0)), c_int(dt(x)), stream()), "p3_colsum")
+    check(lib().p3_colsum(ptr(x), ptr(out), M, N, x.stride(0), dt(x), stream()), "p3_colsum")
     return out
 
 
@@ -1442,8 +1427,7 @@ def batch_sum(x):
 def act_bwd(dy, saved, act, out_dtype, scale=1.0):
     out = torch.empty(dy.shape, dtype=out_dtype, device=dy.device)
     dyc, sc = dy.contiguous(), saved.contiguous()
-    check(lib().p3_act_bwd(ptr(dyc), c_int(dt(dyc)), ptr(sc), c_int(dt(sc)), ptr(out), c_int(dt(out)), c_int64(dy.numel()), c_int(act),
-                           c_float(scale), stream()), "p3_act_bwd")
+    check(lib().p3_act_bwd(ptr(dyc), dt(dyc), ptr(sc), dt(sc), ptr(out), dt(out), dy.numel(), act, scale, stream()), "p3_act_bwd")
     return out
 
 
@@ -1451,8 +1435,7 @@ def embed_tokens_bwd(dx, tokens, emb_shape, pos_shape):
     B, L, D = dx.shape
     demb = torch.zeros(emb_shape, dtype=torch.float32, device=dx.device)
     dpos = torch.zeros(pos_shape, dtype=torch.float32, device=dx.device)
-    check(lib().p3_embed_tokens_bwd_v(ptr(dx), c_int(dt(dx)), ptr(tokens), ptr(demb), c_int(B), c_int(L), c_int(D), c_int(emb_shape[0]), stream()),
-          "p3_embed_tokens_bwd_v")
+    check(lib().p3_embed_tokens_bwd_v(ptr(dx), dt(dx), ptr(tokens), ptr(demb), B, L, D, emb_shape[0], stream()), "p3_embed_tokens_bwd_v")
     colsum(dx.reshape(B, L * D), out=dpos.reshape(-1)[:L * D])          # dpos[t] = sum over the batch: column sums, no atomics
     return demb, dpos
 
@@ -1461,8 +1444,8 @@ def tokens_assemble_bwd(dx, tok, scale, shift, B, np_, D, src_ld, mean=None):
     dsrc = torch.empty((B * np_, D), dtype=tok.dtype, device=dx.device)
     dscale = torch.zeros(D, dtype=torch.float32, device=dx.device) if scale is not None else None
     dshift = torch.zeros(D, dtype=torch.float32, device=dx.device) if scale is not None else None
-    check(lib().p3_tokens_assemble_bwd(ptr(dx.contiguous()), ptr(tok), c_int(tok.stride(-2) if src_ld is None else src_ld), c_int(dt(tok)),
-                                       ptr(scale), ptr(shift), ptr(mean), ptr(dsrc), ptr(dscale), ptr(dshift), c_int(B), c_int(np_), c_int(D), stream()),
+    check(lib().p3_tokens_assemble_bwd(ptr(dx.contiguous()), ptr(tok), tok.stride(-2) if src_ld is None else src_ld, dt(tok),
+                                       ptr(scale), ptr(shift), ptr(mean), ptr(dsrc), ptr(dscale), ptr(dshift), B, np_, D, stream()),
           "p3_tokens_assemble_bwd")
     return dsrc, dscale, dshift
 
@@ -1470,15 +1453,13 @@ def tokens_assemble_bwd(dx, tok, scale, shift, B, np_, D, src_ld, mean=None):
 def pool_pos_bwd(dout, yshape, ydtype):
     B, L, Din = yshape
     dy = torch.empty(yshape, dtype=ydtype, device=dout.device)
-    check(lib().p3_pool_pos_bwd(ptr(dout), c_int(dt(dout)), ptr(dy), c_int(dt(dy)), c_int(B), c_int(L - 1), c_int(Din), c_int(dout.shape[-1]),
-                                stream()), "p3_pool_pos_bwd")
+    check(lib().p3_pool_pos_bwd(ptr(dout), dt(dout), ptr(dy), dt(dy), B, L - 1, Din, dout.shape[-1], stream()), "p3_pool_pos_bwd")
     return dy
 
 
 def pair_mean_bwd(dF, B, L, N, D, dtype, accumulate_into=None):
     out = accumulate_into if accumulate_into is not None else torch.empty((B, L, D), dtype=dtype, device=dF.device)
-    check(lib().p3_pair_mean_bwd(ptr(dF.contiguous()), ptr(out), c_int(dt(out)), c_int(B), c_int(L), c_int(N), c_int(D),
-                                 c_int(int(accumulate_into is not None)), stream()), "p3_pair_mean_bwd")
+    check(lib().p3_pair_mean_bwd(ptr(dF.contiguous()), ptr(out), dt(out), B, L, N, D, int(accumulate_into is not None), stream()), "p3_pair_mean_bwd")
     return out
 
 
@@ -1486,9 +1467,8 @@ def sinkhorn_bwd(scores, alpha, perm, hist, dperm, iters):
     B, m, n = scores.shape
     dscores = torch.empty_like(scores)
     dalpha = torch.zeros(1, dtype=torch.float32, device=scores.device)
-    lib().p3_sinkhorn_bwd_workspace_bytes.restype = c_int64
-    ws = workspace(int(lib().p3_sinkhorn_bwd_workspace_bytes(c_int(B), c_int(m), c_int(n), c_int(iters))), scores.device, "sinkhorn_bwd")
-    check(lib().p3_sinkhorn_bwd(ptr(scores), ptr(alpha), c_int(B), c_int(m), c_int(n), c_int(iters), ptr(perm), ptr(hist), ptr(dperm),
+    ws = workspace(int(lib().p3_sinkhorn_bwd_workspace_bytes(B, m, n, iters)), scores.device, "sinkhorn_bwd")
+    check(lib().p3_sinkhorn_bwd(ptr(scores), ptr(alpha), B, m, n, iters, ptr(perm), ptr(hist), ptr(dperm),
                                 ptr(dscores), ptr(dalpha), ptr(ws), stream()), "p3_sinkhorn_bwd")
     return dscores, dalpha
 
@@ -1497,8 +1477,7 @@ def ce_loss_fwd(logits2d, targets, ignore_index):
     R, V = logits2d.shape
     lse = torch.empty(R, dtype=torch.float32, device=logits2d.device)
     acc = torch.zeros(2, dtype=torch.float32, device=logits2d.device)
-    check(lib().p3_ce_loss_fwd(ptr(logits2d), c_int(logits2d.stride(0)), ptr(targets), c_int(R), c_int(V), c_int(ignore_index), ptr(lse),
-                               ptr(acc), stream()), "p3_ce_loss_fwd")
+    check(lib().p3_ce_loss_fwd(ptr(logits2d), logits2d.stride(0), ptr(targets), R, V, ignore_index, ptr(lse), ptr(acc), stream()), "p3_ce_loss_fwd")
     return lse, acc
 
 
@@ -1506,35 +1485,33 @@ def ce_loss_bwd(logits2d, targets, ignore_index, lse, acc, gscale, out_dtype=tor
     R, V = logits2d.shape
     vpad = vpad or V
     out = torch.empty((R, vpad), dtype=out_dtype, device=logits2d.device)
-    check(lib().p3_ce_loss_bwd(ptr(logits2d), c_int(logits2d.stride(0)), ptr(targets), c_int(R), c_int(V), c_int(ignore_index), ptr(lse),
-                               ptr(acc), ptr(gscale), ptr(out), c_int(dt(out)), c_int(vpad), c_int(vpad), stream()), "p3_ce_loss_bwd")
+    check(lib().p3_ce_loss_bwd(ptr(logits2d), logits2d.stride(0), ptr(targets), R, V, ignore_index, ptr(lse),
+                               ptr(acc), ptr(gscale), ptr(out), dt(out), vpad, vpad, stream()), "p3_ce_loss_bwd")
     return out
 
 
 def bce_loss_fwd(p, y):
     acc = torch.zeros(1, dtype=torch.float32, device=p.device)
-    check(lib().p3_bce_loss_fwd(ptr(p), ptr(y), c_int64(p.numel()), ptr(acc), stream()), "p3_bce_loss_fwd")
+    check(lib().p3_bce_loss_fwd(ptr(p), ptr(y), p.numel(), ptr(acc), stream()), "p3_bce_loss_fwd")
     return acc
 
 
 def bce_loss_bwd(p, y, gscale):
     dp = torch.empty_like(p)
-    check(lib().p3_bce_loss_bwd(ptr(p), ptr(y), c_int64(p.numel()), ptr(gscale), ptr(dp), stream()), "p3_bce_loss_bwd")
+    check(lib().p3_bce_loss_bwd(ptr(p), ptr(y), p.numel(), ptr(gscale), ptr(dp), stream()), "p3_bce_loss_bwd")
     return dp
 
 
 def adamw_schedule(step, hyper, base_lr, kind, warmup, total, beta1, beta2):
-    check(lib().p3_adamw_schedule(ptr(step), ptr(hyper), c_float(base_lr), c_int(kind), c_int(warmup), c_int(total), c_float(beta1),
-                                  c_float(beta2), stream()), "p3_adamw_schedule")
+    check(lib().p3_adamw_schedule(ptr(step), ptr(hyper), base_lr, kind, warmup, total, beta1, beta2, stream()), "p3_adamw_schedule")
 
 
 def adamw_schedule_dev(step, hyper, sched, beta1, beta2):
-    check(lib().p3_adamw_schedule_dev(ptr(step), ptr(hyper), ptr(sched), c_float(beta1), c_float(beta2), stream()), "p3_adamw_schedule_dev")
+    check(lib().p3_adamw_schedule_dev(ptr(step), ptr(hyper), ptr(sched), beta1, beta2, stream()), "p3_adamw_schedule_dev")
 
 
 def adamw(params, grads, m, v, hyper, beta1, beta2, eps, wd, grad_scale=1.0, shadow=None):
-    check(lib().p3_adamw(ptr(params), ptr(grads), ptr(m), ptr(v), c_int64(params.numel()), ptr(hyper), c_float(beta1), c_float(beta2),
-                         c_float(eps), c_float(wd), c_float(grad_scale), ptr(shadow), stream()), "p3_adamw")
+    check(lib().p3_adamw(ptr(params), ptr(grads), ptr(m), ptr(v), params.numel(), ptr(hyper), beta1, beta2, eps, wd, grad_scale, ptr(shadow), stream()), "p3_adamw")
 
 
 # ------------------------------------------------------------------------------------------ ScoreNet backward
@@ -1544,8 +1521,7 @@ A_AFFINE_MASK2 = 5
 def bn_sums_from_g(G, W, scale, shift, mean, dW, acc):
     """see p3_bn_sums_from_g: G [N, 2K] fp32 from gemm_tn_ex(..., A_AFFINE_MASK2); dW [N, K] and acc [2K] are accumulated into"""
     N, K = W.shape
-    check(lib().p3_bn_sums_from_g(ptr(G), c_int(G.stride(0)), ptr(W), ptr(scale), ptr(shift), ptr(mean), ptr(dW), ptr(acc), c_int(N), c_int(K), stream()),
-          "p3_bn_sums_from_g")
+    check(lib().p3_bn_sums_from_g(ptr(G), G.stride(0), ptr(W), ptr(scale), ptr(shift), ptr(mean), ptr(dW), ptr(acc), N, K, stream()), "p3_bn_sums_from_g")
 
 
 def gemm_tn_ex(a, b, out, b_mode, b_scale, b_shift, pair_v=None, pair_n=0, M=None):
@@ -1554,9 +1530,9 @@ def gemm_tn_ex(a, b, out, b_mode, b_scale, b_shift, pair_v=None, pair_n=0, M=Non
     if tuple(out.shape) != (N, K * (2 if b_mode == A_AFFINE_MASK2 else 1)) or out.dtype != torch.float32:
         raise P3Error(f"gemm_tn_ex: out must be float32 [{N}, {K * (2 if b_mode == A_AFFINE_MASK2 else 1)}], got {out.dtype} {tuple(out.shape)}")
     slabs, ns = _tn_slabs(N, K * (2 if b_mode == A_AFFINE_MASK2 else 1), a)
-    check(lib().p3_gemm_tn_ex(ptr(a), ptr(b), ptr(out), c_int(M_), c_int(N), c_int(K), c_int(a.stride(0)), c_int(b.stride(0)),
-                              c_int(out.stride(0)), c_int(dt_mm(a)), c_int(b_mode), ptr(b_scale), ptr(b_shift), ptr(pair_v), c_int(pair_n),
-                              ptr(None), ptr(slabs), c_int(ns), stream()), "p3_gemm_tn_ex")
+    check(lib().p3_gemm_tn_ex(ptr(a), ptr(b), ptr(out), M_, N, K, a.stride(0), b.stride(0),
+                              out.stride(0), dt_mm(a), b_mode, ptr(b_scale), ptr(b_shift), ptr(pair_v), pair_n,
+                              ptr(None), ptr(slabs), ns, stream()), "p3_gemm_tn_ex")
     return out
 
 
@@ -1569,7 +1545,7 @@ def row_affine_bwd(H, scale, shift, mean, acc, *, dA=None, dS=None, w4=None, N=0
         out = None
     fa, fb = fix if fix is not None else (None, None)
     check(lib().p3_row_affine_bwd2(ptr(dA), ptr(dS), ptr(H), ptr(scale), ptr(shift), ptr(mean), ptr(w4), ptr(out), ptr(acc), ptr(fa), ptr(fb),
-                                   c_int64(R), c_int(C), c_int(N), c_int(int(transpose)), c_int(dt(H)), stream()), "p3_row_affine_bwd")
+                                   R, C, N, int(transpose), dt(H), stream()), "p3_row_affine_bwd")
     return out
 
 
@@ -1578,8 +1554,8 @@ def bn_bwd_coeffs(dscale, dshift, gamma, mean, rstd, count, training, acc=None):
     C = gamma.shape[0]
     o = torch.empty((4, C), dtype=torch.float32, device=gamma.device)
     dg, db = (acc[0], acc[1]) if acc is not None else (o[0], o[1])
-    check(lib().p3_bn_bwd_coeffs(ptr(dscale), ptr(dshift), ptr(gamma), ptr(mean), ptr(rstd), c_float(count),
-                                 c_int(int(bool(training)) | (2 if acc is not None else 0)), c_int(C),
+    check(lib().p3_bn_bwd_coeffs(ptr(dscale), ptr(dshift), ptr(gamma), ptr(mean), ptr(rstd), count,
+                                 int(bool(training)) | (2 if acc is not None else 0), C,
                                  ptr(dg), ptr(db), ptr(o[2]), ptr(o[3]), stream()), "p3_bn_bwd_coeffs")
     return (None, None, o[2], o[3]) if acc is not None else (o[0], o[1], o[2], o[3])
 
@@ -1587,8 +1563,7 @@ def bn_bwd_coeffs(dscale, dshift, gamma, mean, rstd, count, training, acc=None):
 def affine_fix(dH, H, a, b, ldh=None):
     """dH [R, C] (dense) += a + b * H;  H may be a strided view (row stride ldh)."""
     R, C = dH.shape
-    check(lib().p3_affine_fix_ld(ptr(dH), ptr(H), c_int(ldh if ldh is not None else H.stride(0)), ptr(a), ptr(b), c_int64(R), c_int(C),
-                                 c_int(dt(dH)), stream()), "p3_affine_fix")
+    check(lib().p3_affine_fix_ld(ptr(dH), ptr(H), ldh if ldh is not None else H.stride(0), ptr(a), ptr(b), R, C, dt(dH), stream()), "p3_affine_fix")
     return dH
 
 
@@ -1599,13 +1574,11 @@ def pair_bwd(dA, U, V, scale, shift, mean, B, N, acc):
     L = lib()
     # dV partials through a scratch slab instead of global atomics: the bf16 form always, the fp32 one in deterministic launches
     if dt(U) == BF16 or (dt(U) == F32 and det_on(U)):
-        L.p3_pair_bwd_workspace_bytes_dt.restype = c_int64
-        ws = workspace(L.p3_pair_bwd_workspace_bytes_dt(c_int(B), c_int(N), c_int(C), c_int(dt(U))), U.device, "pair_bwd")
-        check(L.p3_pair_bwd_ws(ptr(dA), ptr(U), ptr(V), ptr(scale), ptr(shift), ptr(mean), ptr(dU), ptr(dV), ptr(acc), c_int(B), c_int(N), c_int(C),
-                               c_int(dt(U)), ptr(ws), stream()), "p3_pair_bwd_ws")
+        ws = workspace(L.p3_pair_bwd_workspace_bytes_dt(B, N, C, dt(U)), U.device, "pair_bwd")
+        check(L.p3_pair_bwd_ws(ptr(dA), ptr(U), ptr(V), ptr(scale), ptr(shift), ptr(mean), ptr(dU), ptr(dV), ptr(acc), B, N, C,
+                               dt(U), ptr(ws), stream()), "p3_pair_bwd_ws")
     else:
-        check(L.p3_pair_bwd(ptr(dA), ptr(U), ptr(V), ptr(scale), ptr(shift), ptr(mean), ptr(dU), ptr(dV), ptr(acc), c_int(B), c_int(N), c_int(C),
-                            c_int(dt(U)), stream()), "p3_pair_bwd")
+        check(L.p3_pair_bwd(ptr(dA), ptr(U), ptr(V), ptr(scale), ptr(shift), ptr(mean), ptr(dU), ptr(dV), ptr(acc), B, N, C, dt(U), stream()), "p3_pair_bwd")
     return dU, dV
 
 
@@ -1619,20 +1592,18 @@ def pair_bwd_fused(dH2, w2t, U, V, scale, shift, mean, B, N, acc):
     dU = torch.empty((B * N, 256), dtype=torch.float32, device=U.device)
     dV = torch.zeros((B * N, 256), dtype=torch.float32, device=U.device)
     L = lib()
-    L.p3_pair_bwd_fused_workspace_bytes.restype = c_int64
-    ws = workspace(L.p3_pair_bwd_fused_workspace_bytes(c_int(B), c_int(N)), U.device, "pair_bwd")
+    ws = workspace(L.p3_pair_bwd_fused_workspace_bytes(B, N), U.device, "pair_bwd")
     if x3:
-        check(L.p3_pair_bwd_fused_x3(ptr(dH2), ptr(w2t), ptr(U), ptr(V), ptr(scale), ptr(shift), ptr(mean), ptr(dU), ptr(dV), ptr(acc), c_int(B), c_int(N),
+        check(L.p3_pair_bwd_fused_x3(ptr(dH2), ptr(w2t), ptr(U), ptr(V), ptr(scale), ptr(shift), ptr(mean), ptr(dU), ptr(dV), ptr(acc), B, N,
                                      ptr(ws), stream()), "p3_pair_bwd_fused_x3")
         return dU, dV
-    check(L.p3_pair_bwd_fused(ptr(dH2), ptr(w2t), ptr(U), ptr(V), ptr(scale), ptr(shift), ptr(mean), ptr(dU), ptr(dV), ptr(acc), c_int(B), c_int(N),
+    check(L.p3_pair_bwd_fused(ptr(dH2), ptr(w2t), ptr(U), ptr(V), ptr(scale), ptr(shift), ptr(mean), ptr(dU), ptr(dV), ptr(acc), B, N,
                               ptr(ws), stream()), "p3_pair_bwd_fused")
     return dU, dV
 
 
 def pair_stats_bwd(U, V, a, b, dU, dV, B, N):
-    check(lib().p3_pair_stats_bwd(ptr(U), ptr(V), ptr(a), ptr(b), ptr(dU), ptr(dV), c_int(B), c_int(N), c_int(U.shape[1]), c_int(dt(U)),
-                                  stream()), "p3_pair_stats_bwd")
+    check(lib().p3_pair_stats_bwd(ptr(U), ptr(V), ptr(a), ptr(b), ptr(dU), ptr(dV), B, N, U.shape[1], dt(U), stream()), "p3_pair_stats_bwd")
 
 
 # ------------------------------------------------------------------------------------------ FFL / *CNN tails
@@ -1642,23 +1613,22 @@ A_CONV3X3_AFFINE_RELU = 4
 def upsample_bilinear(tokens, B, h, w, H, W, out, tok_off=1):
     """tokens [B, tok_off + h*w, C] -> out [B, H, W, ld] (writes channels 0..C-1)."""
     C = tokens.shape[-1]
-    check(lib().p3_upsample_bilinear(ptr(tokens), c_int(dt(tokens)), ptr(out), c_int(dt(out)), c_int(B), c_int(h), c_int(w), c_int(C), c_int(H),
-                                     c_int(W), c_int(out.stride(-2)), c_int(tok_off), c_int(tokens.shape[1]), stream()), "p3_upsample_bilinear")
+    check(lib().p3_upsample_bilinear(ptr(tokens), dt(tokens), ptr(out), dt(out), B, h, w, C, H,
+                                     W, out.stride(-2), tok_off, tokens.shape[1], stream()), "p3_upsample_bilinear")
     return out
 
 
 def head1x1(X, ld, scale, shift, W, bias, act, post_mul, B, HW, copy_dst=None, copy_ld=0):
     n_out = W.shape[0]
     out = torch.empty((B, n_out, HW), dtype=torch.float32, device=X.device)
-    check(lib().p3_head1x1(ptr(X), c_int(ld), c_int(dt(X)), ptr(scale), ptr(shift), ptr(W), ptr(bias), c_int(n_out), c_int(act), c_float(post_mul),
-                           ptr(out), ptr(copy_dst), c_int(copy_ld), c_int64(B * HW), c_int64(HW), stream()), "p3_head1x1")
+    check(lib().p3_head1x1(ptr(X), ld, dt(X), ptr(scale), ptr(shift), ptr(W), ptr(bias), n_out, act, post_mul,
+                           ptr(out), ptr(copy_dst), copy_ld, B * HW, HW, stream()), "p3_head1x1")
     return out
 
 
 def nhwc_to_nchw(X, ld, scale, shift, B, C, HW):
     out = torch.empty((B, C, HW), dtype=torch.float32, device=X.device)
-    check(lib().p3_nhwc_to_nchw(ptr(X), c_int(ld), c_int(dt(X)), ptr(scale), ptr(shift), ptr(out), c_int(B), c_int(C), c_int64(HW), stream()),
-          "p3_nhwc_to_nchw")
+    check(lib().p3_nhwc_to_nchw(ptr(X), ld, dt(X), ptr(scale), ptr(shift), ptr(out), B, C, HW, stream()), "p3_nhwc_to_nchw")
     return out
 
 
@@ -1672,8 +1642,7 @@ def dropout_apply(x, out_dtype, drop, out=None):
     xc = x.contiguous()
     out = torch.empty(xc.shape, dtype=out_dtype, device=x.device) if out is None else out
     d = _drop(drop)
-    check(lib().p3_dropout_apply(ptr(xc), c_int(dt(xc)), ptr(out), c_int(dt(out)), c_int64(xc.numel()), c_int64(xc.shape[-1]), byref(d), stream()),
-          "p3_dropout_apply")
+    check(lib().p3_dropout_apply(ptr(xc), dt(xc), ptr(out), dt(out), xc.numel(), xc.shape[-1], byref(d), stream()), "p3_dropout_apply")
     return out
 
 
@@ -1684,16 +1653,15 @@ def head1x1_bwd(H, scale, shift, mean, W, out_nchw, dout_nchw, act, post_mul, B,
     R = B * HW
     dHd = torch.empty((R, 256), dtype=H.dtype, device=H.device)
     acc = torch.zeros(512 + n_out * 256 + n_out, dtype=torch.float32, device=H.device)
-    check(lib().p3_head1x1_bwd(ptr(H), c_int(dt(H)), ptr(scale), ptr(shift), ptr(mean), ptr(W), c_int(n_out), ptr(out_nchw), ptr(dout_nchw),
-                               c_int(act), c_float(post_mul), ptr(dHd), ptr(acc), c_int64(R), c_int64(HW), stream()), "p3_head1x1_bwd")
+    check(lib().p3_head1x1_bwd(ptr(H), dt(H), ptr(scale), ptr(shift), ptr(mean), ptr(W), n_out, ptr(out_nchw), ptr(dout_nchw),
+                               act, post_mul, ptr(dHd), ptr(acc), R, HW, stream()), "p3_head1x1_bwd")
     return dHd, acc
 
 
 def affine_relu_bwd256(dA, H, ldh, scale, shift, mean, R, out=None):
     out = dA if out is None else out
     acc = torch.zeros(512, dtype=torch.float32, device=dA.device)
-    check(lib().p3_affine_relu_bwd256(ptr(dA), ptr(H), c_int(ldh), c_int(dt(dA)), ptr(scale), ptr(shift), ptr(mean), ptr(out), ptr(acc), c_int64(R),
-                                      stream()), "p3_affine_relu_bwd256")
+    check(lib().p3_affine_relu_bwd256(ptr(dA), ptr(H), ldh, dt(dA), ptr(scale), ptr(shift), ptr(mean), ptr(out), ptr(acc), R, stream()), "p3_affine_relu_bwd256")
     return out, acc
 
 
@@ -1701,8 +1669,7 @@ def pad_nhwc(src, ld_src, scale, shift, c_aff, C, Cp, B, H, W, out=None):
     """-> zero-bordered [B, H+2, W+2, Cp] copy (channels < c_aff through relu(x*scale + shift) when scale is given)."""
     if out is None:
         out = torch.empty((B, H + 2, W + 2, Cp), dtype=src.dtype, device=src.device)
-    check(lib().p3_pad_nhwc(ptr(src), c_int(ld_src), c_int(dt(src)), ptr(scale), ptr(shift), c_int(c_aff), c_int(C), c_int(Cp), ptr(out), c_int(B),
-                            c_int(H), c_int(W), stream()), "p3_pad_nhwc")
+    check(lib().p3_pad_nhwc(ptr(src), ld_src, dt(src), ptr(scale), ptr(shift), c_aff, C, Cp, ptr(out), B, H, W, stream()), "p3_pad_nhwc")
     return out
 
 
@@ -1713,8 +1680,7 @@ def nchw_to_nhwc(x, dtype, ld=None):
     B, C, H, W = x.shape
     ld = ld or C
     out = torch.zeros((B * H * W, ld), dtype=dtype, device=x.device) if ld != C else torch.empty((B * H * W, ld), dtype=dtype, device=x.device)
-    check(lib().p3_nchw_to_nhwc(ptr(x.contiguous().float()), ptr(out), c_int(ld), c_int(dt(out)), c_int(B), c_int(C), c_int64(H * W), stream()),
-          "p3_nchw_to_nhwc")
+    check(lib().p3_nchw_to_nhwc(ptr(x.contiguous().float()), ptr(out), ld, dt(out), B, C, H * W, stream()), "p3_nchw_to_nhwc")
     return out
 
 
@@ -1723,8 +1689,8 @@ def eca_gate(a1, aff1, a2, aff2, conv_w, B, HW, C):
     pooled = torch.empty((B, C), dtype=torch.float32, device=a1.device)
     gate = torch.empty_like(pooled)
     w = conv_w.detach().reshape(-1).float().contiguous()
-    check(lib().p3_eca_gate(ptr(a1), c_int(a1.stride(0)), ptr(aff1[0]), ptr(aff1[1]), ptr(a2), c_int(a2.stride(0)), ptr(aff2[0]), ptr(aff2[1]), ptr(w),
-                            c_int(w.numel()), ptr(pooled), ptr(gate), c_int(B), c_int64(HW), c_int(C), c_int(dt(a1)), stream()), "p3_eca_gate")
+    check(lib().p3_eca_gate(ptr(a1), a1.stride(0), ptr(aff1[0]), ptr(aff1[1]), ptr(a2), a2.stride(0), ptr(aff2[0]), ptr(aff2[1]), ptr(w),
+                            w.numel(), ptr(pooled), ptr(gate), B, HW, C, dt(a1), stream()), "p3_eca_gate")
     return gate
 
 
@@ -1733,8 +1699,8 @@ def affine_relu_mix(out, a, aff_a, HW, C, gate=None, b=None, aff_b=None):
     R = a.shape[0]
     sa, ha = aff_a if aff_a is not None else (None, None)
     sb, hb = aff_b if aff_b is not None else (None, None)
-    check(lib().p3_affine_relu_mix(ptr(out), c_int(out.stride(0)), ptr(a), c_int(a.stride(0)), ptr(sa), ptr(ha), ptr(gate), ptr(b),
-                                   c_int(b.stride(0) if b is not None else 0), ptr(sb), ptr(hb), c_int64(R), c_int(C), c_int64(HW), c_int(dt(a)),
+    check(lib().p3_affine_relu_mix(ptr(out), out.stride(0), ptr(a), a.stride(0), ptr(sa), ptr(ha), ptr(gate), ptr(b),
+                                   b.stride(0) if b is not None else 0, ptr(sb), ptr(hb), R, C, HW, dt(a),
                                    stream()), "p3_affine_relu_mix")
     return out
 
@@ -1744,13 +1710,12 @@ def upsample_bilinear_bwd(dUp, B, h, w, H, W, tok_off=1):
     C = dUp.shape[-1]
     tmp = torch.empty((B, H, w, C), dtype=torch.float32, device=dUp.device)
     dtok = torch.zeros((B, tok_off + h * w, C), dtype=dUp.dtype, device=dUp.device)
-    check(lib().p3_upsample_bilinear_bwd(ptr(dUp), c_int(dt(dUp)), ptr(tmp), ptr(dtok), c_int(B), c_int(h), c_int(w), c_int(C), c_int(H), c_int(W),
-                                         c_int(tok_off), c_int(tok_off + h * w), stream()), "p3_upsample_bilinear_bwd")
+    check(lib().p3_upsample_bilinear_bwd(ptr(dUp), dt(dUp), ptr(tmp), ptr(dtok), B, h, w, C, H, W, tok_off, tok_off + h * w, stream()), "p3_upsample_bilinear_bwd")
     return dtok
 
 
 def transpose_many(src, dst, table, n_entries, total_tiles):
-    check(lib().p3_transpose_many(ptr(src), ptr(dst), ptr(table), c_int(n_entries), c_int(total_tiles), stream()), "p3_transpose_many")
+    check(lib().p3_transpose_many(ptr(src), ptr(dst), ptr(table), n_entries, total_tiles, stream()), "p3_transpose_many")
 
 
 def attention_mask_words(B, heads, Lq, Lk, device):
@@ -1791,20 +1756,20 @@ def to_planes(x, out=None, pad=64):
     rows, cols = x.shape
     if out is None:
         out = Planes.empty(rows, cols, x.device, pad)
-    check(lib().p3_to_planes(ptr(x), c_int(x.stride(0)), ptr(out.hi), ptr(out.lo), c_int(out.ld), c_int64(rows), c_int(cols), stream()), "p3_to_planes")
+    check(lib().p3_to_planes(ptr(x), x.stride(0), ptr(out.hi), ptr(out.lo), out.ld, rows, cols, stream()), "p3_to_planes")
     return out
 
 
 def to_planes_into(x, hi, lo):
     """fp32 [rows, cols] -> the given bf16 hi / lo matrices (same shape, one row stride)"""
     rows, cols = x.shape
-    check(lib().p3_to_planes(ptr(x), c_int(x.stride(0)), ptr(hi), ptr(lo), c_int(hi.stride(0)), c_int64(rows), c_int(cols), stream()), "p3_to_planes")
+    check(lib().p3_to_planes(ptr(x), x.stride(0), ptr(hi), ptr(lo), hi.stride(0), rows, cols, stream()), "p3_to_planes")
 
 
 def from_planes(p, out=None):
     if out is None:
         out = torch.empty((p.rows, p.cols), dtype=torch.float32, device=p.buf.device)
-    check(lib().p3_from_planes(ptr(p.hi), ptr(p.lo), c_int(p.ld), ptr(out), c_int(out.stride(0)), c_int64(p.rows), c_int(p.cols), stream()), "p3_from_planes")
+    check(lib().p3_from_planes(ptr(p.hi), ptr(p.lo), p.ld, ptr(out), out.stride(0), p.rows, p.cols, stream()), "p3_from_planes")
     return out
 
 
@@ -1831,7 +1796,7 @@ def x3_cus(device):
     return _x3_cus[idx]
 
 
-X3_RAGGED_SPLIT = [_os0.environ.get("P3_X3_RAGGED", "1") != "0"]               # A/B switch of the ragged-round rule below
+X3_RAGGED_SPLIT = [os.environ.get("P3_X3_RAGGED", "1") != "0"]               # A/B switch of the ragged-round rule below
 
 
 def gemm_x3(a, w, *, bias=None, act=ACT_NONE, residual=None, aux=None, mul=None, out=None, out_planes=False, ln=None):
@@ -1914,8 +1879,8 @@ def gemm_tn_x3(a, b, out=None, colsum_out=None):
         out = torch.zeros((N, K), dtype=torch.float32, device=a.buf.device)
     slabs, ns = _tn_slabs(N, K, out)
     ev = KTIMER.begin()
-    check(lib().p3_gemm_tn_x3(ptr(a.hi), ptr(a.lo), c_int(a.ld), ptr(b.hi), ptr(b.lo), c_int(b.ld), ptr(out), c_int(out.stride(0)), c_int(M), c_int(N), c_int(K),
-                              ptr(colsum_out), ptr(slabs), c_int(ns), stream()), "p3_gemm_tn_x3")
+    check(lib().p3_gemm_tn_x3(ptr(a.hi), ptr(a.lo), a.ld, ptr(b.hi), ptr(b.lo), b.ld, ptr(out), out.stride(0), M, N, K,
+                              ptr(colsum_out), ptr(slabs), ns, stream()), "p3_gemm_tn_x3")
     if ev is not None:
         KTIMER.end(ev, lib().p3_last_kernel().decode() or "gemm_tn_x3_kernel<4>", 2.0 * a.rows * N * K, float(4 * a.rows * (N + K) + N * K * 4))
     return out
@@ -1928,7 +1893,7 @@ def layernorm_planes(x, gamma, beta, eps, out=None, save_stats=True):
         out = Planes.empty(rows, cols, x.device)
     mean = torch.empty(rows, dtype=torch.float32, device=x.device) if save_stats else None
     rstd = torch.empty(rows, dtype=torch.float32, device=x.device) if save_stats else None
-    check(lib().p3_layernorm_planes(ptr(x), ptr(gamma), ptr(beta), ptr(out.hi), ptr(out.lo), c_int64(rows), c_int(cols), c_int(x.stride(0)), c_int(out.ld), c_float(eps),
+    check(lib().p3_layernorm_planes(ptr(x), ptr(gamma), ptr(beta), ptr(out.hi), ptr(out.lo), rows, cols, x.stride(0), out.ld, eps,
                                     ptr(mean), ptr(rstd), stream()), "p3_layernorm_planes")
     return out, mean, rstd
 
@@ -1942,11 +1907,11 @@ def layernorm_bwd_planes(dy, x, gamma, mean, rstd, dres, dgamma, dbeta, out=None
     L = lib()
     park = park and dgamma is not None and param_reduce_arena()
     if park:
-        L.p3_reduce_defer_enable(c_int(1))
+        L.p3_reduce_defer_enable(1)
     try:
-        check(L.p3_layernorm_bwd_planes(ptr(dy), ptr(x), ptr(gamma), ptr(mean), ptr(rstd), ptr(dres), ptr(dx), ptr(out.hi), ptr(out.lo), c_int(out.ld),
-                                        ptr(dgamma), ptr(dbeta), c_int64(rows), c_int(cols), stream()), "p3_layernorm_bwd_planes")
+        check(L.p3_layernorm_bwd_planes(ptr(dy), ptr(x), ptr(gamma), ptr(mean), ptr(rstd), ptr(dres), ptr(dx), ptr(out.hi), ptr(out.lo), out.ld,
+                                        ptr(dgamma), ptr(dbeta), rows, cols, stream()), "p3_layernorm_bwd_planes")
     finally:
         if park:
-            L.p3_reduce_defer_enable(c_int(0))
+            L.p3_reduce_defer_enable(0)
     return dx, out

@@ -18,9 +18,9 @@ def _declared():
 
 @pytest.fixture(scope="module")
 def lib():
+    from pixelspointspolygons_amd._lib import load
     from pixelspointspolygons_amd.build import build_library
-    so = build_library(verbose=False)
-    return ctypes.CDLL(so)
+    return load(build_library(verbose=False))
 
 
 def test_header_declares_the_expected_surface():
@@ -37,14 +37,56 @@ def test_library_exports_every_declared_symbol(lib):
 
 
 def test_version_and_error_convention_without_gpu(lib):
-    lib.p3_version.restype = ctypes.c_int
-    lib.p3_last_error_string.restype = ctypes.c_char_p
     assert lib.p3_version() >= 100
     # null pointers are rejected before any device work: P3_EINVAL (-1) + message
     rc = lib.p3_gemm(None, None, None, None, None)
     assert rc == -1 and b"p3_gemm" in lib.p3_last_error_string()
     rc = lib.p3_sinkhorn(None, None, 0, 0, 0, 0, None, None, None, None)
     assert rc == -1
+
+
+def test_every_prototype_is_declared_on_the_loaded_library(lib):
+    """_lib.declare gives every function the header declares its argtypes and restype: the parameter count (split here, independently of the loader) and the
+    class of the return type (int64_t for the *_workspace_bytes family, char pointers, void, int)."""
+    from pixelspointspolygons_amd._lib import prototypes
+    text = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
+    seen = {}
+    for m in re.finditer(r"([\w \t*]+?)\b(p3_\w+)\s*\(([^;{}]*?)\)\s*;", text):
+        ret, args = " ".join(m.group(1).split()), m.group(3).strip()
+        want = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "const char*": ctypes.c_char_p, "void": None}[ret]
+        seen[m.group(2)] = (want, 0 if args in ("", "void") else len(_split_top_level(args)))
+    assert sorted(seen) == _declared() == sorted(prototypes())
+    for name, (restype, nargs) in seen.items():
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None and len(fn.argtypes) == nargs, (name, fn.argtypes, nargs)
+        assert fn.restype is restype, (name, fn.restype, restype)
+    assert seen["p3_acm_workspace_bytes"] == (ctypes.c_int64, 1) and seen["p3_last_kernel"] == (ctypes.c_char_p, 0) and seen["p3_trace_kernels"] == (None, 1)
+
+
+def test_int64_return_above_32_bits_arrives_intact(lib):
+    assert lib.p3_acm_workspace_bytes(1 << 28) == 20 << 28          # 20 bytes per vertex (test_acm_cpu): 5 GiB, no restype line anywhere
+
+
+def test_ctypes_refuses_arguments_that_do_not_fit_the_prototype(lib):
+    """all on null / tiny arguments: refused by ctypes before the call, nothing reaches the device"""
+    with pytest.raises(TypeError):
+        lib.p3_gemm(None, None, None, None)                          # one argument short
+    with pytest.raises(ctypes.ArgumentError):
+        lib.p3_acm_workspace_bytes(ctypes.c_int(5))                  # a 32-bit wrapper for an int64_t parameter
+    with pytest.raises(ctypes.ArgumentError):
+        lib.p3_scratch_regions(1.0)                                  # a float for an int parameter
+    assert lib.p3_acm_workspace_bytes(5) == 100
+
+
+def test_unknown_parameter_type_in_the_header_is_an_error(tmp_path):
+    from pixelspointspolygons_amd._lib import P3Error, prototypes
+    h = tmp_path / "p3hip.h"
+    h.write_text("int p3_fine(int a, const float* b, void* stream);\nint p3_odd(int a, size_t n);\n")
+    with pytest.raises(P3Error, match="p3_odd"):
+        prototypes(str(h))
+    h.write_text("long p3_odd_return(int a);\n")
+    with pytest.raises(P3Error, match="p3_odd_return"):
+        prototypes(str(h))
 
 
 def test_product_fails_loudly_on_host_tensors():

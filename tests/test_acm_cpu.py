@@ -85,16 +85,15 @@ def test_reference_alone_stays_within_half_of_the_gpu_caps(gold):
 
 
 def test_entry_is_declared_exported_and_validates_before_any_device_work():
+    from pixelspointspolygons_amd._lib import load
     from pixelspointspolygons_amd.build import build_library
-    lib = ctypes.CDLL(build_library(verbose=False))
+    lib = load(build_library(verbose=False))
     raw = open(HEADER).read()
     assert "polygonize_acm.py:77-220" in raw
     text = re.sub(r"/\*.*?\*/", " ", raw, flags=re.S)
     m = re.search(r"\bint\s+p3_acm_optimize\s*\(([^;{}]*?)\)\s*;", text, flags=re.S)
     assert m and len(m.group(1).split(",")) == 25
     assert hasattr(lib, "p3_acm_optimize") and hasattr(lib, "p3_acm_workspace_bytes")
-    lib.p3_last_error_string.restype = ctypes.c_char_p
-    lib.p3_acm_workspace_bytes.restype = ctypes.c_int64
     f, dbl, n64 = ctypes.c_float, ctypes.c_double, ctypes.c_int64
 
     def call(N, P, steps, B=1, first_iter=0):

@@ -214,16 +214,15 @@ def test_reference_alone_stays_within_the_generators_conditions(gold):
 
 
 def test_entries_are_declared_exported_and_validate_before_any_device_work():
+    from pixelspointspolygons_amd._lib import load
     from pixelspointspolygons_amd.build import build_library
-    lib = ctypes.CDLL(build_library(verbose=False))
+    lib = load(build_library(verbose=False))
     raw = open(HEADER).read()
     assert "polygonize_asm.py:133-421" in raw and "tensorskeleton.py" in raw
     text = re.sub(r"/\*.*?\*/", " ", raw, flags=re.S)
     m = re.search(r"\bint\s+p3_asm_optimize\s*\(([^;{}]*?)\)\s*;", text, flags=re.S)
     assert m and len(m.group(1).split(",")) == 30
     assert hasattr(lib, "p3_asm_optimize") and hasattr(lib, "p3_asm_workspace_bytes") and hasattr(lib, "p3_asm_schedule")
-    lib.p3_last_error_string.restype = ctypes.c_char_p
-    lib.p3_asm_workspace_bytes.restype = ctypes.c_int64
     f, dbl, n64 = ctypes.c_float, ctypes.c_double, ctypes.c_int64
     knots = (ctypes.c_double * 16)(*[float(v) for r in KNOTS for v in r])
 

@@ -138,8 +138,9 @@ def test_pieces_of_a_rectangle():
 
 
 def test_entries_are_declared_exported_and_validate_before_any_device_work():
+    from pixelspointspolygons_amd._lib import load
     from pixelspointspolygons_amd.build import build_library
-    lib = ctypes.CDLL(build_library(verbose=False))
+    lib = load(build_library(verbose=False))
     raw = open(HEADER).read()
     text = re.sub(r"/\*.*?\*/", " ", raw, flags=re.S)
     m = re.search(r"\bint\s+p3_corner_split\s*\(([^;{}]*?)\)\s*;", text, flags=re.S)
@@ -148,8 +149,6 @@ def test_entries_are_declared_exported_and_validate_before_any_device_work():
     comment = [c for c in re.findall(r"/\*.*?\*/", raw, flags=re.S) if "FFL corner-aware contour simplification" in c]
     assert comment and "frame_field_utils.detect_corners" in comment[0] and "split_polylines_corner" in comment[0]
     assert hasattr(lib, "p3_corner_split") and hasattr(lib, "p3_corner_split_workspace_bytes")
-    lib.p3_last_error_string.restype = ctypes.c_char_p
-    lib.p3_corner_split_workspace_bytes.restype = ctypes.c_int64
     n64, dbl = ctypes.c_int64, ctypes.c_double
     one = ctypes.c_void_p(8)          # a non-null pointer that is never followed: every call below fails its checks first
 

@@ -146,8 +146,9 @@ def test_annotation_encoder_bound_check_and_empty_edges():
 
 # ------------------------------------------------------------------------------------------------ C-ABI
 def test_new_entries_are_exported_with_the_declared_arity():
+    from pixelspointspolygons_amd._lib import load
     from pixelspointspolygons_amd.build import build_library
-    lib = ctypes.CDLL(build_library(verbose=False))
+    lib = load(build_library(verbose=False))
     text = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
     arity = {"p3_hisup_junctions": 19, "p3_hisup_regions": 17, "p3_hisup_val_loss": 15, "p3_hisup_junctions_workspace_bytes": 3,
              "p3_hisup_regions_workspace_bytes": 4, "p3_hisup_val_loss_workspace_bytes": 3}
@@ -165,7 +166,6 @@ def test_new_entries_are_exported_with_the_declared_arity():
             commas += src[j] == "," and depth == 1
             j += 1
         assert commas + 1 == n, (name, commas + 1)
-    lib.p3_last_error_string.restype = ctypes.c_char_p
     z = ctypes.c_int64(0)
     assert lib.p3_hisup_junctions(None, z, z, z, None, z, z, z, 1, 8, 8, ctypes.c_float(1), ctypes.c_float(1), None, None, None, None, None, None) == -1
     assert b"p3_hisup_junctions" in lib.p3_last_error_string()

@@ -50,8 +50,9 @@ def test_the_inputs_cover_what_they_are_meant_to():
 
 
 def test_entries_are_declared_exported_and_validate_before_any_device_work():
+    from pixelspointspolygons_amd._lib import load
     from pixelspointspolygons_amd.build import build_library
-    lib = ctypes.CDLL(build_library(verbose=False))
+    lib = load(build_library(verbose=False))
     raw = open(HEADER).read()
     text = re.sub(r"/\*.*?\*/", " ", raw, flags=re.S)
     m = re.search(r"\bint\s+p3_init_contours\s*\(([^;{}]*?)\)\s*;", text, flags=re.S)
@@ -60,8 +61,6 @@ def test_entries_are_declared_exported_and_validate_before_any_device_work():
     comment = [c for c in re.findall(r"/\*.*?\*/", raw, flags=re.S) if "FFL initial contours" in c]
     assert comment and "polygonize_utils.py:15-44" in comment[0]
     assert hasattr(lib, "p3_init_contours") and hasattr(lib, "p3_init_contours_workspace_bytes")
-    lib.p3_last_error_string.restype = ctypes.c_char_p
-    lib.p3_init_contours_workspace_bytes.restype = ctypes.c_int64
     n64, dbl = ctypes.c_int64, ctypes.c_double
 
     def call(B=1, H=8, W=8, nv=16, nc=8):

@@ -61,7 +61,7 @@ def main():
            "vertices_in": int(pos.shape[0]), "vertices_out": V, "pieces": NP, "longest_piece": longest,
            "download_bytes_in": int(pos.shape[0]) * 8, "download_bytes_out": V * 8 + NP * 20,
            "launches": {"kernels": 4, "memsets": 2},
-           "workspace_MB": round(int(hip.lib().p3_corner_split_workspace_bytes(hip.c_int64(int(pos.shape[0]) + int(sl.shape[0])), int(sl.shape[0]))) / 2 ** 20, 2)}
+           "workspace_MB": round(int(hip.lib().p3_corner_split_workspace_bytes(int(pos.shape[0]) + int(sl.shape[0]), int(sl.shape[0]))) / 2 ** 20, 2)}
 
     def device(fallback):
         return hip.corner_split_device(pos, None, sl, closed, pb, cf, tol_pre, tol, max_len=tp.max_len, force_fallback=fallback)
