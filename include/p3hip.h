@@ -826,6 +826,49 @@ int p3_corner_split(const float* pos, int64_t N, const int64_t* index, int64_t K
                     uint8_t* stage_flags, int32_t* counts, int32_t* status, void* workspace, void* stream);
 int64_t p3_corner_split_workspace_bytes(int64_t E, int P);
 
+/* ------------------------------------------------------------------------------------------
+ * HiSup polygons: models/hisup/polygon.py:56-93,111-169 (`ext_c_to_poly_coco`, `diagonal_to_square`, `simple_polygon`, `get_poly_crowdai` with
+ * test_inria = False) on the device: the OUTER polygon of every region of p3_hisup_regions, what `forward_val` returns as `polys_pred`.
+ * Inputs as the two kernels above write them: labels int32 [B,H,W], n_regions int32 [B], bbox int32 [B,max_regions,4], juncs fp32 [B,600,2] (x, y),
+ * junc_counts int32 [B,2]; an image has n = min(600, counts[b,0] + counts[b,1]) junctions.  Every count and box read is clamped.  H, W <= 32766.
+ * Region (b, l), l <= min(n_regions[b], max_regions), pixel set M, coordinates (x, y) = (column, row):
+ *   A  F = M and every background pixel that no 4-connected background path joins to the outside of the bounding box; hole_pixels = |F| - |M|.
+ *   B  corner grid T [(H+1),(W+1)]: T[y,x] = F[y,x] | F[y-1,x] | F[y,x-1] | F[y-1,x-1], pixels outside the image are 0.
+ *   C  outer border of T, 8-connected border following.  Directions s = 0 E (+x), 1 NE (+x,-y), 2 N, 3 NW, 4 W, 5 SW, 6 S, 7 SE.  p0 = first set cell in
+ *      raster order; from s = 4, s = (s - 1) mod 8 until the neighbour p1 of p0 in direction s is set.  p = p0; repeat: s = (s + 1) mod 8 until the
+ *      neighbour q of p in direction s is set; emit p; stop when q == p0 and p == p1; else p = q, s = (s + 4) mod 8.
+ *   D  after every emitted p whose step to its cyclic successor is diagonal one point is inserted: (+1,+1): (p.x+1, p.y), (-1,-1): (p.x-1, p.y),
+ *      (+1,-1): (p.x, p.y-1), (-1,+1): (p.x, p.y+1).  The ring r_0 .. r_{m-1} has unit axis steps only.
+ *   E  (n > 0) every ring point takes d_j = sqrt(dx dx + dy dy) in float64 (correctly rounded products, sum and root, no fused multiply-add) to every
+ *      junction; j* = the lowest index among the minima; the point votes for j* when d_j* < 5; first[j] = the smallest ring index that votes for j.
+ *      More than two junctions with a vote: the polygon is those junctions in ascending `first` (flag bit 0); otherwise it is the ring.
+ *   F  of the sequence q_0 .. q_{k-1}: e_i = q_{(i+1) mod k} - q_i, a_i = atan2(e.y, e.x) 180 / pi in float64, t_i = |a_i - a_{(i+1) mod k}|; vertex
+ *      (i+1) mod k is kept when 10 < t_i < 350; output = the kept vertices in ascending index, then the first kept one once more.  Nothing kept: the
+ *      region gives no polygon (flag bit 2; the reference raises there).
+ * Inner rings are NOT built: a region with holes gets its outer polygon, flag bit 1 and hole_pixels, and is left to the host for its courtyards.
+ * Outputs, polygons packed in the order (image, label): pos fp32 [max_vertices,2] (x, y; ring corners are integers, junctions bit copies of juncs); src
+ * int32 [max_vertices] the ring index or junction index of each vertex; poly_slice int64 [B,max_regions,2] = [first, one past the last) in pos (empty
+ * for a region without polygon and for labels past n_regions); poly_flags int32 [B,max_regions] bit 0 junction polygon, bit 1 hole_pixels > 0, bit 2 no
+ * polygon; hole_pixels int32 [B,max_regions]; n_vertices int32 [B]; counts int32 [2] = (vertices, vertices of the longest polygon); status int32 [1]:
+ * bit 0 = more vertices than max_vertices: counts, poly_slice, flags, hole_pixels and n_vertices still hold the true values, pos and src are left
+ * untouched and nothing is written past a capacity; bit 1 = a ring was longer than the bound below (never seen; that region gives no polygon); bit 2 = the run was cut short by the measurement
+ * switch P3_HISUP_POLY_STOP of tools/bench_hisup_polygons.py and its outputs are no result.
+ * Ring bound: every visit of the border follower to a cell uses up a side of that cell that faces the outer background, so it emits at most c(T) cells,
+ * c = the number of such sides; a diagonal step adds one point: m <= 2 c(T).  Dilating by the 2 x 2 block adds at most 4 sides, and a pixel side
+ * belongs to one region only, so m <= 2 (c(M) + 4) <= 2 (H (W+1) + W (H+1)) + 8 for one region, and the regions of an image together have at most
+ * 2 (H (W+1) + W (H+1)) + 8 n_regions ring points.  A polygon has at most m + 1 vertices (junctions with a vote have distinct `first`), so
+ * max_vertices = B (2 (H (W+1) + W (H+1)) + 9 min(max_regions, ceil(H/2) ceil(W/2))) can never overflow.
+ * Execution: a region whose padded box (h + 3) (w + 3) has at most 16384 cells and whose ring has at most 5120 points runs with its bitmaps and ring in
+ * LDS, one workgroup per region; the others (all of them with force_fallback != 0) run the same device function over slabs of `workspace`.  Four launches
+ * whatever the data; no host synchronisation; two runs, either form, an image alone or inside a batch give the same bits.  B == 0 or max_regions == 0:
+ * returns 0 without a launch.  workspace: p3_hisup_polygons_workspace_bytes(B, H, W, max_regions, max_vertices) bytes.
+ * ------------------------------------------------------------------------------------------ */
+int p3_hisup_polygons(const int32_t* labels, const int32_t* n_regions, const int32_t* bbox, const float* juncs, const int32_t* junc_counts, int B,
+                      int H, int W, int max_regions, int max_vertices, int force_fallback, float* pos, int32_t* src, int64_t* poly_slice,
+                      int32_t* poly_flags, int32_t* hole_pixels, int32_t* n_vertices, int32_t* counts, int32_t* status, void* workspace,
+                      void* stream);
+int64_t p3_hisup_polygons_workspace_bytes(int B, int H, int W, int max_regions, int max_vertices);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1085,6 +1085,74 @@ def hisup_val_loss(jloc, joff, mask, afm_pred, remask, t_jloc, t_joff, t_mask, t
     return losses
 
 
+HISUP_MAX_EDGE = 32766      # csrc/hisup_polygon.hip: ring coordinates are packed into 16 bits each
+
+
+def hisup_polygons_capacity(B, H, W, max_regions):
+    """the max_vertices that can never overflow (include/p3hip.h, the ring bound of p3_hisup_polygons)"""
+    return B * (2 * (H * (W + 1) + W * (H + 1)) + 9 * min(max_regions, ((H + 1) // 2) * ((W + 1) // 2)))
+
+
+def hisup_polygons_device(labels, n_regions, bbox, juncs, junc_counts, max_vertices=None, force_fallback=False, _guard=0):
+    """p3_hisup_polygons (models/hisup/polygon.py `get_poly_crowdai`, outer polygons only) without any synchronisation.
+    labels i32 [B,H,W], n_regions i32 [B], bbox i32 [B,R,4] as hisup_regions_device returns them, juncs f32 [B,600,2], junc_counts i32 [B,2] as
+    hisup_junctions returns them.  -> dict(pos f32 [max_vertices,2] (x, y), src i32 [max_vertices] (ring or junction index), poly_slice i64 [B,R,2],
+    poly_flags i32 [B,R] (bit 0 junction polygon, bit 1 the region has holes - their rings are NOT built -, bit 2 no polygon), hole_pixels i32 [B,R],
+    n_vertices i32 [B], counts i32 [2] = (vertices, longest polygon), status i32 [1] (bit 0: max_vertices was too small; the counts are the true totals
+    then, pos / src are not written)).  The default max_vertices cannot overflow but is large: 12 bytes of output and 12 of workspace per vertex, about
+    2 x 41 MB at B = 16, 224 x 224, where real outputs have a few thousand vertices; a caller that holds many batches passes its own max_vertices and
+    checks status.  _guard: test hook, guard bytes around every output (out["_arenas"])."""
+    if labels.dim() != 3 or labels.dtype != torch.int32 or min(labels.shape) < 1:
+        raise P3Error(f"hisup_polygons: labels int32 [B, H, W] expected, got {labels.dtype} {tuple(labels.shape)}")
+    B, H, W = labels.shape
+    if bbox.dim() != 3 or bbox.shape[0] != B or bbox.shape[2] != 4 or bbox.shape[1] < 1 or bbox.dtype != torch.int32 or tuple(n_regions.shape) != (B,) \
+            or n_regions.dtype != torch.int32:
+        raise P3Error(f"hisup_polygons: n_regions int32 [{B}] and bbox int32 [{B}, R, 4] expected, got {tuple(n_regions.shape)}, {tuple(bbox.shape)}")
+    if tuple(juncs.shape) != (B, 2 * HISUP_TOPK, 2) or juncs.dtype != torch.float32 or tuple(junc_counts.shape) != (B, 2) or junc_counts.dtype != torch.int32:
+        raise P3Error(f"hisup_polygons: juncs float32 [{B}, {2 * HISUP_TOPK}, 2] and junc_counts int32 [{B}, 2] expected, got {tuple(juncs.shape)}, "
+                      f"{tuple(junc_counts.shape)}")
+    if H > HISUP_MAX_EDGE or W > HISUP_MAX_EDGE or H * W > HISUP_MAX_HW:
+        raise P3Error(f"hisup_polygons: {H} x {W} is beyond the {HISUP_MAX_EDGE} pixels per edge / {HISUP_MAX_HW} pixels per map the kernel supports")
+    R = bbox.shape[1]
+    nv = hisup_polygons_capacity(B, H, W, R) if max_vertices is None else int(max_vertices)
+    if nv < 1 or nv >= 1 << 31:
+        raise P3Error(f"hisup_polygons: max_vertices = {nv}")
+    for t in (labels, n_regions, bbox, juncs, junc_counts):
+        _dev(t)
+    dev, arenas, g = labels.device, [], int(_guard)
+    out = dict(pos=_ic_out((nv, 2), torch.float32, dev, g, arenas), src=_ic_out((nv,), torch.int32, dev, g, arenas),
+               poly_slice=_ic_out((B, R, 2), torch.int64, dev, g, arenas), poly_flags=_ic_out((B, R), torch.int32, dev, g, arenas),
+               hole_pixels=_ic_out((B, R), torch.int32, dev, g, arenas), n_vertices=_ic_out((B,), torch.int32, dev, g, arenas),
+               counts=_ic_out((2,), torch.int32, dev, g, arenas), status=_ic_out((1,), torch.int32, dev, g, arenas))
+    if g:
+        out["_arenas"] = arenas
+    lab, nr, bb, jc, cn = labels.contiguous(), n_regions.contiguous(), bbox.contiguous(), juncs.contiguous(), junc_counts.contiguous()
+    ws = workspace(int(lib().p3_hisup_polygons_workspace_bytes(B, H, W, R, nv)), dev, "hisup_polygons")
+    check(lib().p3_hisup_polygons(ptr(lab), ptr(nr), ptr(bb), ptr(jc), ptr(cn), B, H, W, R, nv, int(bool(force_fallback)),
+                                  ptr(out["pos"]), ptr(out["src"]), ptr(out["poly_slice"]), ptr(out["poly_flags"]), ptr(out["hole_pixels"]),
+                                  ptr(out["n_vertices"]), ptr(out["counts"]), ptr(out["status"]), ptr(ws), stream()), "p3_hisup_polygons")
+    return out
+
+
+def hisup_polygons(labels, n_regions, bbox, juncs, junc_counts, max_vertices=None, force_fallback=False):
+    """the checking form of hisup_polygons_device: reads counts and status once (the only read-back), raises when max_vertices was too small and narrows
+    pos / src to the vertices found; counts = (vertices, longest polygon) as Python ints."""
+    return hisup_polygons_checked(hisup_polygons_device(labels, n_regions, bbox, juncs, junc_counts, max_vertices, force_fallback))
+
+
+def hisup_polygons_checked(out, who="hisup_polygons"):
+    """the one read-back of counts and status of a hisup_polygons_device result: raises on any status bit, narrows pos / src, counts as Python ints"""
+    V, longest, status = torch.cat([out["counts"], out["status"]]).tolist()
+    if status & 1:
+        raise P3Error(f"{who}: {V} vertices do not fit max_vertices = {out['pos'].shape[0]}")
+    if status & 4:
+        raise P3Error(f"{who}: P3_HISUP_POLY_STOP is set: the run was cut short for a measurement and has no result")
+    if status & 2:
+        raise P3Error(f"{who}: a region's ring is longer than the bound the workspace is sized for (include/p3hip.h)")
+    out["pos"], out["src"], out["counts"] = out["pos"][:V], out["src"][:V], (V, longest)
+    return out
+
+
 # ------------------------------------------------------------------------------------------ FFL active-contour polygon optimiser
 ACM_LDS_CAP = 4096          # csrc/acm.hip: vertices of one polygon that fit the one-launch LDS path
 

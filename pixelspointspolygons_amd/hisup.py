@@ -10,7 +10,7 @@ BatchNorm + ReLU is never applied in a pass of its own: it travels as per-channe
 Forward only (eval and train-mode BatchNorm incl. the running-statistic updates); there is no hand-written backward for this head set.
 
 The whole model for inference (second half of this file): `HiSupModel` (the reference's factory, model_hisup.py:312-360), `EncoderDecoder` (`HiSupHeads` + encoder;
-`forward_val` of :229-293 on the device up to the hand-over to the OpenCV polygonizer: csrc/hisup_predict.hip) and `AnnotationEncoder` (:66-120).
+`forward_val` of :229-293 on the device: csrc/hisup_predict.hip, and csrc/hisup_polygon.hip for the polygons) and `AnnotationEncoder` (:66-120).
 """
 import math
 
@@ -244,8 +244,8 @@ class AnnotationEncoder:
 class EncoderDecoder(HiSupHeads):
     """model_hisup.py:122-308, inference: encoder + head set (`HiSupHeads` is the base class, so the state_dict is the reference's: `encoder.*`
     and the head keys at the top level) + what `forward_val` does after the heads, on the device: validation losses (p3_hisup_val_loss),
-    junctions (p3_hisup_junctions), building regions (p3_hisup_regions).  Polygonization (`generate_polygon`, OpenCV contours) is host code of
-    the reference and starts from `output["regions"]`, see INTEGRATION.md."""
+    junctions (p3_hisup_junctions), building regions (p3_hisup_regions) and, with polygons=True, the outer polygon of every region (p3_hisup_polygons,
+    `get_poly_crowdai`).  Inner rings of regions with holes stay host code of the reference (OpenCV contours), see INTEGRATION.md."""
 
     def __init__(self, cfg, encoder, max_regions=1024):
         super().__init__(cfg)
@@ -289,10 +289,11 @@ class EncoderDecoder(HiSupHeads):
         return targets, HiSupHeads.forward(self, features)
 
     @torch.no_grad()
-    def forward_val_device(self, x_images, x_lidar, y=None):
+    def forward_val_device(self, x_images, x_lidar, y=None, polygons=False):
         """`forward_val` without any host synchronisation: -> (output, loss_dict) of device tensors.  output: juncs [B,600,2], junc_scores [B,600],
         junc_index [B,600], junc_counts [B,2] (hip.hisup_junctions), mask [B,H,W], regions = dict(labels, n_regions, area, bbox, score, status)
-        (hip.hisup_regions_device; status[b] = 1: more than max_regions regions in image b) and `heads`, the five NCHW maps."""
+        (hip.hisup_regions_device; status[b] = 1: more than max_regions regions in image b) and `heads`, the five NCHW maps.  polygons=True adds
+        output["polygons"], the dict of hip.hisup_polygons_device (outer polygons; a region with holes is flagged, its inner rings are not built)."""
         targets, heads = self.forward_common(x_images, x_lidar, y)
         B, _, H, W = heads["joff"].shape
         assert H == self.pred_height and W == self.pred_width
@@ -309,14 +310,19 @@ class EncoderDecoder(HiSupHeads):
         reg = hip.hisup_regions_device(heads["remask"], self.max_regions)
         output = {"juncs": juncs, "junc_scores": scores, "junc_index": index, "junc_counts": counts, "mask": reg.pop("mask"), "regions": reg,
                   "heads": heads}
+        if polygons:
+            output["polygons"] = hip.hisup_polygons_device(reg["labels"], reg["n_regions"], reg["bbox"], juncs, counts)
         return output, loss_dict
 
     @torch.no_grad()
-    def forward_val(self, x_images, x_lidar, y=None):
-        """model_hisup.py:229-293 up to the hand-over to `generate_polygon`: -> (output, loss_dict).  output["juncs_pred"]: list of [n, 2] fp32 numpy
-        arrays (x, y), class 2 first; output["mask_pred"]: list of [H, W] fp32 numpy arrays; output["regions"]: per image dict(labels int32 [H, W],
-        area int32 [n], bbox int32 [n, 4], score fp32 [n]) in place of the reference's `polys_pred` / `scores`.  One device-to-host copy per kind."""
-        out, loss_dict = self.forward_val_device(x_images, x_lidar, y)
+    def forward_val(self, x_images, x_lidar, y=None, polygons=False):
+        """model_hisup.py:229-293: -> (output, loss_dict).  output["juncs_pred"]: list of [n, 2] fp32 numpy arrays (x, y), class 2 first;
+        output["mask_pred"]: list of [H, W] fp32 numpy arrays; output["regions"]: per image dict(labels int32 [H, W], area int32 [n], bbox int32 [n, 4],
+        score fp32 [n]).  One device-to-host copy per kind.  polygons=True adds the reference's `polys_pred` (per image a list of closed float64 [k+1, 2]
+        arrays (x, y), one per region that has a polygon, in label order) and `scores` (per image the matching regions' scores), and `poly_flags` (per image
+        int32 [n]: bit 0 junction polygon, bit 1 the region has holes, bit 2 no polygon).  Only OUTER polygons are built: for a region with bit 1 the
+        reference may add inner rings, see INTEGRATION.md for the host hand-over."""
+        out, loss_dict = self.forward_val_device(x_images, x_lidar, y, polygons=polygons)
         reg = out["regions"]
         status, n_reg = reg["status"].cpu().numpy(), reg["n_regions"].cpu().numpy()
         if status.any():
@@ -328,6 +334,12 @@ class EncoderDecoder(HiSupHeads):
         output = {"juncs_pred": [juncs[b, :counts[b].sum()].copy() for b in range(B)], "mask_pred": [mask[b] for b in range(B)],
                   "regions": [{"labels": labels[b], "area": area[b, :n_reg[b]].copy(), "bbox": bbox[b, :n_reg[b]].copy(),
                                "score": score[b, :n_reg[b]].copy()} for b in range(B)]}
+        if polygons:
+            pg = hip.hisup_polygons_checked(dict(out["polygons"]), "forward_val(polygons=True)")
+            pos, sl, flags = pg["pos"].cpu().numpy().astype("float64"), pg["poly_slice"].cpu().numpy(), pg["poly_flags"].cpu().numpy()
+            output["polys_pred"] = [[pos[sl[b, i, 0]:sl[b, i, 1]] for i in range(n_reg[b]) if not flags[b, i] & 4] for b in range(B)]
+            output["scores"] = [score[b, :n_reg[b]][(flags[b, :n_reg[b]] & 4) == 0].copy() for b in range(B)]
+            output["poly_flags"] = [flags[b, :n_reg[b]].copy() for b in range(B)]
         return output, loss_dict
 
 
