@@ -203,7 +203,7 @@ __global__ __launch_bounds__(256, (Kind<T>::X3 ? 2 : 3)) void attn_fwd_kernel(At
 
     if (ntiles > 0) load_tile(0);
     for (int t = 0; t < ntiles; ++t) {
-        if constexpr (DMA) p3attn::wait_vm0();        // this wave's DMA pieces of the tile have landed
+        if constexpr (DMA) wait_vm<0>();        // this wave's DMA pieces of the tile have landed
         __syncthreads();  // previous tile's LDS reads are done (DMA: and every wave's pieces are in LDS)
         if constexpr (DMA) { SD::split_store(attn_raw, reinterpret_cast<bf16_t*>(Ks), tid); SD::split_store(attn_raw + SD::RAW_B, reinterpret_cast<bf16_t*>(Vs), tid); }
         else if constexpr (X3) { ksp.store(reinterpret_cast<bf16_t*>(Ks), tid); vsp.store(reinterpret_cast<bf16_t*>(Vs), tid); }

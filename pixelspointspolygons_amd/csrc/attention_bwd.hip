@@ -351,7 +351,7 @@ __global__ __launch_bounds__(256, (D == 32 && !Kind<T>::X3 ? 3 : 2)) void attn_b
     if (ntiles > 0) load_tile(0);
     for (int t = 0; t < ntiles; ++t) {
         const int kv0 = t * KT;
-        if constexpr (X3) p3attn::wait_vm0();
+        if constexpr (X3) wait_vm<0>();
         __syncthreads();
         if constexpr (X3) { SD::split_store(attn_raw, reinterpret_cast<bf16_t*>(Krow), tid); SD::split_store(attn_raw + SD::RAW_B, reinterpret_cast<bf16_t*>(Vrow), tid); }
         else { kreg.store(Krow, tid); vreg.store(Vrow, tid); }
@@ -493,7 +493,7 @@ __global__ __launch_bounds__(256, (D == 32 && !Kind<T>::X3 ? P3_DKV32_WAVES : 2)
 #endif
     for (int q0 = q_begin; q0 < d.Lq; q0 += QT) {
         TM(6);
-        if constexpr (X3) p3attn::wait_vm0();
+        if constexpr (X3) wait_vm<0>();
         __syncthreads();
         TM(0);
         if constexpr (X3) { SD::split_store(attn_raw, reinterpret_cast<bf16_t*>(Qrow), tid); SD::split_store(attn_raw + SD::RAW_B, reinterpret_cast<bf16_t*>(Grow), tid); }

@@ -149,16 +149,7 @@ template <int D, int R> struct SplitStage {
 // front of anything but the tile switch) into a RAW image - R rows x D fp32, linear, 1 KB pieces of 1024 / (4 D) rows, wave w of the four issues pieces w, w + 4, ... -
 // and are split into the hi / lo bf16 images LDS -> registers -> LDS at the tile switch.  The register-staged form (SplitStage) kept 32 registers per thread in flight
 // across the whole tile: the dK / dV kernel spilled, and every reload of a spilled register (scratch_load + s_waitcnt vmcnt(0)) drained the prefetch it was issued behind.
-__device__ __forceinline__ void lds_dma16(const void* sbase, uint32_t lds_dst, uint32_t voff) {      // 64 lanes x 16 B -> LDS [lds_dst, lds_dst + 1 KB), lane order
-    uint32_t keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
+// lds_dma16 and the wait_vm<0>() of the tile switch: gfx950_asm.h.
 template <int D, int R> struct SplitDma {
     static constexpr int VPR = D / 4, ITEMS = R * VPR, N = ITEMS / 256, RPP = 1024 / (D * 4), PIECES = R / RPP, PW = PIECES / 4, RAW_B = R * D * 4;
     static_assert(ITEMS % 256 == 0 && PIECES % 4 == 0, "whole pieces per wave");

@@ -31,7 +31,6 @@ struct GDArgs {
     int ablate;                 // diagnostic (-DP3_GD_DIAG build, P3_GD_ABLATE): 1 no C / aux stores, 2 no MFMAs, 4 only the first slices are loaded
 };
 
-
 __device__ __forceinline__ float gd_act_grad(float x, int act) {
     if (act == P3_ACT_MUL) return x;
     if (act == P3_ACT_GELU) { float h, g; gelu_and_grad(x, h, g); return g; }
@@ -102,16 +101,6 @@ __device__ __forceinline__ void gd_epi8(const p3_gemm_desc& d, const DropKey& dk
     else { *reinterpret_cast<float4*>(C + co) = make_float4(v[0], v[1], v[2], v[3]); *reinterpret_cast<float4*>(C + co + 4) = make_float4(v[4], v[5], v[6], v[7]); }
 }
 
-template <int N> __device__ __forceinline__ void wait_vm() {
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else if constexpr (N == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-    else if constexpr (N == 32) asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
-    else static_assert(N == 0, "add the immediate");
-}
-
 template <typename TO, int BK, int NBUF>
 __global__ __launch_bounds__(256, BK == 32 ? (NBUF == 2 ? 4 : 3) : 2) void gemm_dma_kernel(GDArgs g) {
     constexpr int CPR = BK / 8;                 // 16-byte chunks per row
@@ -146,25 +135,16 @@ __global__ __launch_bounds__(256, BK == 32 ? (NBUF == 2 ? 4 : 3) : 2) void gemm_
         voffB[q] = (uint32_t)(((int64_t)rb * d.ldb + c * 8) * 2);
     }
     const uint32_t lds_addr = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(&lds[0]));
-    auto dma2 = [&](const bf16_t* base, uint32_t dst, uint32_t v0, uint32_t v1) __attribute__((always_inline)) {
-        uint32_t keep;
-        asm volatile(
-            "s_mov_b32 %0, m0\n\t"
-            "s_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\t"
-            "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\t"
-            "s_mov_b32 m0, %0"
-            : "=&s"(keep) : "v"(v0), "v"(v1), "s"(base), "s"(dst) : "memory");
-    };
     auto stage = [&](int kt) __attribute__((always_inline)) {        // slice kt -> buffer kt % NBUF (caller: kt < nk)
         const int buf = kt % NBUF;
         const bf16_t* ab = g.A + (int64_t)kt * BK;
         const bf16_t* wb = g.W + (int64_t)kt * BK;
         const uint32_t da = lds_addr + (uint32_t)(((buf * 2 + 0) * TILE_U4 + wave * PW * 64) * 16);
         const uint32_t db = lds_addr + (uint32_t)(((buf * 2 + 1) * TILE_U4 + wave * PW * 64) * 16);
-        dma2(ab, da, voffA[0], voffA[1]);
-        if constexpr (PW == 4) dma2(ab, da + 0x800, voffA[2], voffA[3]);
-        dma2(wb, db, voffB[0], voffB[1]);
-        if constexpr (PW == 4) dma2(wb, db + 0x800, voffB[2], voffB[3]);
+        lds_dma16x2(ab, da, voffA[0], voffA[1]);
+        if constexpr (PW == 4) lds_dma16x2(ab, da + 0x800, voffA[2], voffA[3]);
+        lds_dma16x2(wb, db, voffB[0], voffB[1]);
+        if constexpr (PW == 4) lds_dma16x2(wb, db + 0x800, voffB[2], voffB[3]);
     };
 
     f32x16 acc[2][2];
@@ -214,7 +194,7 @@ __global__ __launch_bounds__(256, BK == 32 ? (NBUF == 2 ? 4 : 3) : 2) void gemm_
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, af[i][kk]), __builtin_bit_cast(bf16x8_t, bfr[j][kk]), acc[i][j], 0, 0, 0);
         __builtin_amdgcn_s_setprio(0);
     }
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    wait_vm_lgkm0<0>();
     __builtin_amdgcn_s_barrier();                   // every wave is done with the operands: the epilogue may overwrite them
     GD_T(2);
 
@@ -249,7 +229,7 @@ __global__ __launch_bounds__(256, BK == 32 ? (NBUF == 2 ? 4 : 3) : 2) void gemm_
             gd_epi8<TO>(d, dk, C, aux, bwd_saved, has_res, res_bf, aux_grad, act, row, col, v);
         }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     GD_T(3);
 }
 
@@ -286,15 +266,7 @@ __global__ __launch_bounds__(512, 4) void gemm_dma_n384_kernel(GDArgs g) {
         const bf16_t* wb = g.W + (int64_t)kt * BK;
         const uint32_t da = lds_addr + (uint32_t)((buf * BUF_U4 + wave * 64) * 16);
         const uint32_t db = lds_addr + (uint32_t)((buf * BUF_U4 + A_U4 + wave * 3 * 64) * 16);
-        uint32_t keep;
-        asm volatile(
-            "s_mov_b32 %0, m0\n\t"
-            "s_mov_b32 m0, %7\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %5\n\t"
-            "s_mov_b32 m0, %8\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %6\n\t"
-            "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %6\n\t"
-            "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %6\n\t"
-            "s_mov_b32 m0, %0"
-            : "=&s"(keep) : "v"(voffA), "v"(voffB[0]), "v"(voffB[1]), "v"(voffB[2]), "s"(ab), "s"(wb), "s"(da), "s"(db) : "memory");
+        lds_dma16x1p3(ab, da, voffA, wb, db, voffB[0], voffB[1], voffB[2]);
     };
     f32x16 acc[2][3];
 #pragma unroll
@@ -326,7 +298,7 @@ __global__ __launch_bounds__(512, 4) void gemm_dma_n384_kernel(GDArgs g) {
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, af[i]), __builtin_bit_cast(bf16x8_t, bfr[j]), acc[i][j], 0, 0, 0);
         }
     }
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    wait_vm_lgkm0<0>();
     __builtin_amdgcn_s_barrier();
     // epilogue: 32 x 32 blocks through a private fp32 image [32][36]
     constexpr int EP = 36;

@@ -264,8 +264,8 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(TnArgs g) {
 #pragma unroll
                     for (int hh = 0; hh < 2; ++hh) {
                         const uint32_t off = (uint32_t)(((kk * 16 + hh * 4) * PITCH + i * 32) * 2);
-                        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(fa[slot][i][hh]) : "v"(abase + off));
-                        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(fb[slot][i][hh]) : "v"(bbase + off));
+                        lds_read_tr16_b64(fa[slot][i][hh], abase + off);
+                        lds_read_tr16_b64(fb[slot][i][hh], bbase + off);
                     }
             };
             auto wait = [&](int slot) __attribute__((always_inline)) {
@@ -307,8 +307,8 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(TnArgs g) {
 #pragma unroll
                     for (int hh = 0; hh < 2; ++hh) {
                         const uint32_t off = (uint32_t)(im * TS_IMG_B + (hh * 4 * TS_PITCH + i * 32) * 2);
-                        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(fa[im][i][hh]) : "v"(abase + off));
-                        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(fb[im][i][hh]) : "v"(bbase + off));
+                        lds_read_tr16_b64(fa[im][i][hh], abase + off);
+                        lds_read_tr16_b64(fb[im][i][hh], bbase + off);
                     }
             asm volatile("s_waitcnt lgkmcnt(0)"
                          : "+v"(fa[0][0][0]), "+v"(fa[0][0][1]), "+v"(fa[0][1][0]), "+v"(fa[0][1][1]), "+v"(fb[0][0][0]), "+v"(fb[0][0][1]), "+v"(fb[0][1][0]), "+v"(fb[0][1][1]),

@@ -34,14 +34,6 @@ struct TdArgs {
     float* cs_slab;     // deterministic mode: [splits][N]
 };
 
-template <int N> __device__ __forceinline__ void td_wait_vm() {
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else static_assert(N == 0, "add the immediate");
-}
-
 template <int NBUF>
 __global__ __launch_bounds__(512, 2) void gemm_tn_dma_kernel(TdArgs g) {
     constexpr int LA = NBUF - 1;
@@ -70,21 +62,12 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_dma_kernel(TdArgs g) {
             voffB[q] = (uint32_t)(((int64_t)r * g.ldb + tk * 128 + chunk * 8) * 2);
         }
     }
-    auto dma2 = [&](const bf16_t* base, uint32_t dst, uint32_t v0, uint32_t v1) __attribute__((always_inline)) {
-        uint32_t keep;
-        asm volatile(
-            "s_mov_b32 %0, m0\n\t"
-            "s_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\t"
-            "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\t"
-            "s_mov_b32 m0, %0"
-            : "=&s"(keep) : "v"(v0), "v"(v1), "s"(base), "s"(dst) : "memory");
-    };
     auto stage = [&](int st) __attribute__((always_inline)) {      // step st -> buffer st % NBUF (caller: st < nsteps)
         const int buf = st % NBUF;
         const int64_t m0 = (int64_t)m_beg + (int64_t)st * TD_BM;
         const uint32_t da = lds_addr + (uint32_t)(buf * TD_STEP_BYTES + wave * 2048);
-        dma2(g.A + m0 * g.lda, da, voffA[0], voffA[1]);
-        dma2(g.B + m0 * g.ldb, da + TD_BM * 256, voffB[0], voffB[1]);
+        lds_dma16x2(g.A + m0 * g.lda, da, voffA[0], voffA[1]);
+        lds_dma16x2(g.B + m0 * g.ldb, da + TD_BM * 256, voffB[0], voffB[1]);
     };
 
     f32x16 acc[2][2];
@@ -123,10 +106,10 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_dma_kernel(TdArgs g) {
         // is outstanding); the barrier extends that to every wave's pieces.  WAR: a wave reaches the barrier after its reads of step st - 1, whose
         // buffer step st + LA takes.
         const int ahead = min(LA - 1, nsteps - 1 - st);
-        if (ahead <= 0) td_wait_vm<0>();
-        else if (ahead == 1) td_wait_vm<4>();
-        else if (ahead == 2) td_wait_vm<8>();
-        else td_wait_vm<12>();
+        if (ahead <= 0) wait_vm<0>();
+        else if (ahead == 1) wait_vm<4>();
+        else if (ahead == 2) wait_vm<8>();
+        else wait_vm<12>();
         __builtin_amdgcn_s_barrier();
         if (st + LA < nsteps) stage(st + LA);
         const uint32_t bo = (uint32_t)((st % NBUF) * TD_STEP_BYTES);
@@ -138,8 +121,8 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_dma_kernel(TdArgs g) {
 #pragma unroll
                 for (int hh = 0; hh < 2; ++hh) {
                     const uint32_t ro = bo + (uint32_t)((kk * 16 + hh * 4) * 256);
-                    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(fa[kk][i][hh]) : "v"(offA[i] + ro));
-                    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(fb[kk][i][hh]) : "v"(offB[i] + ro));
+                    lds_read_tr16_b64(fa[kk][i][hh], offA[i] + ro);
+                    lds_read_tr16_b64(fb[kk][i][hh], offB[i] + ro);
                 }
         if (do_cs) {
             const unsigned char* ab = lds_raw + bo;
@@ -171,7 +154,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_dma_kernel(TdArgs g) {
         }
         __builtin_amdgcn_s_setprio(0);
     }
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    wait_vm_lgkm0<0>();
     __builtin_amdgcn_s_barrier();                   // every wave is done with the operand images: the epilogue reuses the LDS
 
     // ---- bias gradient: fold the 32 row lanes of a chunk through LDS, one value per column

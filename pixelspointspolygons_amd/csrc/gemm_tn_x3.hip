@@ -27,14 +27,6 @@ struct TdArgs {
     float* cs_slab;     // deterministic mode: [splits][N]
 };
 
-template <int N> __device__ __forceinline__ void td_wait_vm() {
-    if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else static_assert(N == 0, "add the immediate");
-}
-
 template <int NBUF>
 __global__ __launch_bounds__(512, 2) void gemm_tn_x3_kernel(TdArgs g) {
     constexpr int LA = NBUF - 1;
@@ -65,21 +57,12 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_x3_kernel(TdArgs g) {
             voff[q] = (uint32_t)(((int64_t)r * sld + scol + chunk * 8) * 2);
         }
     }
-    auto dma2 = [&](const bf16_t* base, uint32_t dst, uint32_t v0, uint32_t v1) __attribute__((always_inline)) {
-        uint32_t keep;
-        asm volatile(
-            "s_mov_b32 %0, m0\n\t"
-            "s_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\t"
-            "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\t"
-            "s_mov_b32 m0, %0"
-            : "=&s"(keep) : "v"(v0), "v"(v1), "s"(base), "s"(dst) : "memory");
-    };
     auto stage = [&](int st) __attribute__((always_inline)) {      // step st -> buffer st % NBUF (caller: st < nsteps)
         const int buf = st % NBUF;
         const int64_t m0 = (int64_t)m_beg + (int64_t)st * TD_BM;
         const uint32_t da = lds_addr + (uint32_t)(buf * TD_STEP_BYTES + wave * 4096);
-        dma2(src + m0 * sld, da, voff[0], voff[1]);
-        dma2(src + m0 * sld, da + 2048, voff[2], voff[3]);
+        lds_dma16x2(src + m0 * sld, da, voff[0], voff[1]);
+        lds_dma16x2(src + m0 * sld, da + 2048, voff[2], voff[3]);
     };
 
     f32x16 acc[2][2];
@@ -115,9 +98,9 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_x3_kernel(TdArgs g) {
         // RAW: this wave's pieces of step st have landed once at most `ahead` younger steps stay in flight (loads retire in order; nothing else is outstanding);
         // the barrier extends that to every wave's pieces.  WAR: a wave reaches the barrier after its reads of step st - 1, whose buffer step st + LA takes.
         const int ahead = min(LA - 1, nsteps - 1 - st);
-        if (ahead >= 2) td_wait_vm<8>();
-        else if (ahead == 1) td_wait_vm<4>();
-        else td_wait_vm<0>();
+        if (ahead >= 2) wait_vm<8>();
+        else if (ahead == 1) wait_vm<4>();
+        else wait_vm<0>();
         __builtin_amdgcn_s_barrier();
         if (st + LA < nsteps) stage(st + LA);
         const uint32_t bo = (uint32_t)((st % NBUF) * TD_STEP_BYTES);
@@ -139,10 +122,10 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_x3_kernel(TdArgs g) {
 #pragma unroll
                 for (int hh = 0; hh < 2; ++hh) {
                     const uint32_t ro = bo + (uint32_t)((kk * 16 + hh * 4) * 256);
-                    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(fah[i][hh]) : "v"(offA[i] + ro));
-                    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(fal[i][hh]) : "v"(offA[i] + ro + TD_IMG));
-                    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(fbh[i][hh]) : "v"(offB[i] + ro));
-                    asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(fbl[i][hh]) : "v"(offB[i] + ro + TD_IMG));
+                    lds_read_tr16_b64(fah[i][hh], offA[i] + ro);
+                    lds_read_tr16_b64(fal[i][hh], offA[i] + ro + TD_IMG);
+                    lds_read_tr16_b64(fbh[i][hh], offB[i] + ro);
+                    lds_read_tr16_b64(fbl[i][hh], offB[i] + ro + TD_IMG);
                 }
             asm volatile("s_waitcnt lgkmcnt(0)"
                          : "+v"(fah[0][0]), "+v"(fah[0][1]), "+v"(fah[1][0]), "+v"(fah[1][1]), "+v"(fal[0][0]), "+v"(fal[0][1]), "+v"(fal[1][0]), "+v"(fal[1][1]),
@@ -172,7 +155,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_x3_kernel(TdArgs g) {
             __builtin_amdgcn_s_setprio(0);
         }
     }
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    wait_vm_lgkm0<0>();
     __builtin_amdgcn_s_barrier();                   // every wave is done with the operand images: the epilogue reuses the LDS
 
     // ---- bias gradient: fold the 32 row lanes of a chunk through LDS, one value per column
@@ -251,20 +234,11 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_x3_wide_kernel(TdArgs g) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) voff[q] = (uint32_t)(((int64_t)(q * 4 + prow) * sld + scol + chunk * 8) * 2);
     }
-    auto dma2 = [&](const bf16_t* base, uint32_t dst, uint32_t v0, uint32_t v1) __attribute__((always_inline)) {
-        uint32_t keep;
-        asm volatile(
-            "s_mov_b32 %0, m0\n\t"
-            "s_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\t"
-            "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\t"
-            "s_mov_b32 m0, %0"
-            : "=&s"(keep) : "v"(v0), "v"(v1), "s"(base), "s"(dst) : "memory");
-    };
     auto stage = [&](int st) __attribute__((always_inline)) {
         const int64_t m0 = (int64_t)m_beg + (int64_t)st * TW_BM;
         const uint32_t da = lds_addr + (uint32_t)((st % NBUF) * TW_STEP_BYTES + wave * TW_IMG);
-        dma2(src + m0 * sld, da, voff[0], voff[1]);
-        dma2(src + m0 * sld, da + 2048, voff[2], voff[3]);
+        lds_dma16x2(src + m0 * sld, da, voff[0], voff[1]);
+        lds_dma16x2(src + m0 * sld, da + 2048, voff[2], voff[3]);
     };
 
     f32x16 acc[2][3];
@@ -300,9 +274,9 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_x3_wide_kernel(TdArgs g) {
         if (p < nsteps) stage(p);
     for (int st = 0; st < nsteps; ++st) {
         const int ahead = min(LA - 1, nsteps - 1 - st);
-        if (ahead >= 2) td_wait_vm<8>();
-        else if (ahead == 1) td_wait_vm<4>();
-        else td_wait_vm<0>();
+        if (ahead >= 2) wait_vm<8>();
+        else if (ahead == 1) wait_vm<4>();
+        else wait_vm<0>();
         __builtin_amdgcn_s_barrier();
         if (st + LA < nsteps) stage(st + LA);
         const uint32_t bo = (uint32_t)((st % NBUF) * TW_STEP_BYTES);
@@ -321,13 +295,13 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_x3_wide_kernel(TdArgs g) {
             const uint32_t ro = bo + (uint32_t)(hh * 4 * 256);
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(fah[i][hh]) : "v"(offA[i] + ro));
-                asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(fal[i][hh]) : "v"(offA[i] + ro + TW_IMG));
+                lds_read_tr16_b64(fah[i][hh], offA[i] + ro);
+                lds_read_tr16_b64(fal[i][hh], offA[i] + ro + TW_IMG);
             }
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
-                asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(fbh[j][hh]) : "v"(offB[j] + ro));
-                asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(fbl[j][hh]) : "v"(offB[j] + ro + TW_IMG));
+                lds_read_tr16_b64(fbh[j][hh], offB[j] + ro);
+                lds_read_tr16_b64(fbl[j][hh], offB[j] + ro + TW_IMG);
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)"
@@ -361,7 +335,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_x3_wide_kernel(TdArgs g) {
             for (int j = 0; j < 3; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
         __builtin_amdgcn_s_setprio(0);
     }
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    wait_vm_lgkm0<0>();
     __builtin_amdgcn_s_barrier();                   // every wave is done with the operand images: the bias fold reuses the LDS
 
     if (do_cs) {                                     // wave-uniform (tk is)

@@ -27,27 +27,6 @@ struct X3Args {
     int tiles_m, tiles_n;
 };
 
-__device__ __forceinline__ void x3_wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-// two 1 KB LDS-DMA pieces (consecutive in LDS) from one base pointer
-__device__ __forceinline__ void x3_dma2(const bf16_t* base, uint32_t dst, uint32_t v0, uint32_t v1) {
-    uint32_t keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\t"
-        "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep) : "v"(v0), "v"(v1), "s"(base), "s"(dst) : "memory");
-}
-__device__ __forceinline__ void x3_dma1(const bf16_t* base, uint32_t dst, uint32_t v0) {
-    uint32_t keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep) : "v"(v0), "s"(base), "s"(dst) : "memory");
-}
-
 // ---- 128 x 128 tile, 4 waves, 64 KB of LDS -> TWO workgroups per CU ---------------------------------------------------------------------------
 // Same software-pipelined loop as the 128 x 384 kernel below (fragments double-buffered per 16-deep block, the next slice's DMA pieces and the next block's
 // fragment reads issued in the gaps between the MFMAs, one barrier in the middle of the iteration).  What the smaller tile buys: two INDEPENDENT workgroups
@@ -87,10 +66,10 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(X3Args g) {
     auto dma_part = [&](int kt, int n) __attribute__((always_inline)) {      // n = 0 a_hi, 1 a_lo, 2 w_hi, 3 w_lo: two pieces each
         const uint32_t base = lds_addr + (uint32_t)(((kt & 1) * STAGE_U4 + n * TILE_U4 + wave * 2 * 64) * 16);
         const int64_t ko = (int64_t)kt * 32;
-        if (n == 0) x3_dma2(Ah + ko, base, voffA[0], voffA[1]);
-        else if (n == 1) x3_dma2(Al + ko, base, voffA[0], voffA[1]);
-        else if (n == 2) x3_dma2(Wh + ko, base, voffB[0], voffB[1]);
-        else x3_dma2(Wl + ko, base, voffB[0], voffB[1]);
+        if (n == 0) lds_dma16x2(Ah + ko, base, voffA[0], voffA[1]);
+        else if (n == 1) lds_dma16x2(Al + ko, base, voffA[0], voffA[1]);
+        else if (n == 2) lds_dma16x2(Wh + ko, base, voffB[0], voffB[1]);
+        else lds_dma16x2(Wl + ko, base, voffB[0], voffB[1]);
     };
 
     f32x16 acc[2][2];
@@ -122,9 +101,9 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(X3Args g) {
     if (nk > 1) {
 #pragma unroll
         for (int n = 0; n < 4; ++n) dma_part(1, n);
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");      // slice 0 landed (this wave's pieces); slice 1 stays in flight
+        wait_vm<8>();      // slice 0 landed (this wave's pieces); slice 1 stays in flight
     } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vm<0>();
     }
     __builtin_amdgcn_s_barrier();
 #pragma unroll
@@ -145,7 +124,7 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(X3Args g) {
             }
         }
         __builtin_amdgcn_s_setprio(0);
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");       // slice kt + 1 landed (this wave's pieces); this wave's reads of slice kt done
+        wait_vm_lgkm0<0>();       // slice kt + 1 landed (this wave's pieces); this wave's reads of slice kt done
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -161,7 +140,7 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(X3Args g) {
         }
         __builtin_amdgcn_s_setprio(0);
     }
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    wait_vm_lgkm0<0>();
     __builtin_amdgcn_s_barrier();                      // every wave is done with the operands: the epilogue may overwrite them
 
     // ---- epilogue: per wave, two 32 x 64 blocks through a private fp32 image [32][72]
@@ -237,12 +216,12 @@ __global__ __launch_bounds__(512, 2) void gemm_x3_n384_kernel(X3Args g) {
         const int64_t ko = (int64_t)kt * 32;
         const uint32_t da = sbase + (uint32_t)(wave * 64 * 16);
         const uint32_t db = sbase + (uint32_t)((2 * A_U4 + wave * 3 * 64) * 16);
-        if (n == 0) x3_dma1(Ah + ko, da, voffA);
-        else if (n == 1) x3_dma1(Al + ko, da + A_U4 * 16, voffA);
-        else if (n == 2) x3_dma2(Wh + ko, db, voffB[0], voffB[1]);
-        else if (n == 3) x3_dma1(Wh + ko, db + 0x800, voffB[2]);
-        else if (n == 4) x3_dma2(Wl + ko, db + B_U4 * 16, voffB[0], voffB[1]);
-        else x3_dma1(Wl + ko, db + B_U4 * 16 + 0x800, voffB[2]);
+        if (n == 0) lds_dma16(Ah + ko, da, voffA);
+        else if (n == 1) lds_dma16(Al + ko, da + A_U4 * 16, voffA);
+        else if (n == 2) lds_dma16x2(Wh + ko, db, voffB[0], voffB[1]);
+        else if (n == 3) lds_dma16(Wh + ko, db + 0x800, voffB[2]);
+        else if (n == 4) lds_dma16x2(Wl + ko, db + B_U4 * 16, voffB[0], voffB[1]);
+        else lds_dma16(Wl + ko, db + B_U4 * 16 + 0x800, voffB[2]);
     };
     f32x16 acc[2][3];
 #pragma unroll
@@ -274,9 +253,9 @@ __global__ __launch_bounds__(512, 2) void gemm_x3_n384_kernel(X3Args g) {
     if (nk > 1) {
 #pragma unroll
         for (int n = 0; n < 6; ++n) dma_part(1, n);
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");      // slice 0 landed (this wave's pieces); slice 1 stays in flight
+        wait_vm<8>();      // slice 0 landed (this wave's pieces); slice 1 stays in flight
     } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vm<0>();
     }
     __builtin_amdgcn_s_barrier();
 #pragma unroll
@@ -300,7 +279,7 @@ __global__ __launch_bounds__(512, 2) void gemm_x3_n384_kernel(X3Args g) {
         __builtin_amdgcn_s_setprio(0);
         // ---- middle of the iteration: slice kt + 1 readable for everyone, slice kt's image dead (every wave has read its block (kt, 1) fragments - the
         // s_waitcnt lgkmcnt(0) keeps them out of the next slice's DMA writes)
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        wait_vm_lgkm0<0>();
         __builtin_amdgcn_s_barrier();
         // ---- block (kt, 1) on F1; DMA of slice kt + 2 (into slice kt's buffer) and the reads of block (kt + 1, 0) into F0 in the gaps
         __builtin_amdgcn_s_setprio(1);
@@ -317,7 +296,7 @@ __global__ __launch_bounds__(512, 2) void gemm_x3_n384_kernel(X3Args g) {
         }
         __builtin_amdgcn_s_setprio(0);
     }
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    wait_vm_lgkm0<0>();
     __builtin_amdgcn_s_barrier();
     // ---- epilogue: 32 x 32 blocks through a private fp32 image [32][36] (8 waves x 4.5 KB); LN: + row statistics [128 rows][4 column waves] behind the images
     constexpr int EP = 36;

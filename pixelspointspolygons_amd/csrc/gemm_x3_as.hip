@@ -43,15 +43,6 @@ struct AsArgs {
 
 typedef uint32_t as_u32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ void as_dma1(const bf16_t* base, uint32_t dst, uint32_t v0) {
-    uint32_t keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep) : "v"(v0), "s"(base), "s"(dst) : "memory");
-}
-
 // 16- / 8-byte stores at wave-uniform base + 32-bit byte offset; SC1: write-through (the line is not kept in this XCD's L2, where the weight stream lives)
 typedef float as_f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t as_u32x2 __attribute__((ext_vector_type(2)));
@@ -119,7 +110,7 @@ __global__ __launch_bounds__(512, 2) void gemm_x3_as_kernel(AsArgs g) {
     // piece x of the next half block: x < GH: w_hi, 64-deep group x; else w_lo, group x - GH
     auto dma_piece = [&](int x) __attribute__((always_inline)) {
         const int64_t so = (int64_t)d_cb * 32 * d.ldb + (d_hb & 1) * (GH * 64) + (x % GH) * 64;
-        as_dma1((x < GH ? Wh_ : Wl_) + so, dst_w + (uint32_t)(d_slot * HALF_B + x * 4096), voffW);
+        lds_dma16((x < GH ? Wh_ : Wl_) + so, dst_w + (uint32_t)(d_slot * HALF_B + x * 4096), voffW);
     };
     auto dma_advance = [&]() __attribute__((always_inline)) {
         if (d_hb & 1) { if (++d_cb == CB) d_cb = 0; }
@@ -345,7 +336,7 @@ __global__ __launch_bounds__(512, 2) void gemm_x3_as_kernel(AsArgs g) {
 
     unsigned long long tsum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     auto now = [&]() __attribute__((always_inline)) -> unsigned long long {
-        if constexpr (DBG) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); return __builtin_amdgcn_s_memtime(); }
+        if constexpr (DBG) { wait_lgkm0(); return __builtin_amdgcn_s_memtime(); }
         return 0ull;
     };
     const unsigned long long t_start = now();
@@ -379,23 +370,23 @@ __global__ __launch_bounds__(512, 2) void gemm_x3_as_kernel(AsArgs g) {
                 // the stores in keeps them in flight for ~3 ticks instead of ~1.5 - the HBM write stream needs that window; r06: fc1 150 us without epilogue,
                 // 210 with its stores folded onto cache-resident rows, 279 real)
                 const int extra = S1 + S2 + (F3 ? S3 : 0);
-                switch (extra >> 1) {
-                    case 0: if constexpr (GH == 3) asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory"); break;
-                    case 1: if constexpr (GH == 3) asm volatile("s_waitcnt vmcnt(14) lgkmcnt(0)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(10) lgkmcnt(0)" ::: "memory"); break;
-                    case 2: if constexpr (GH == 3) asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)" ::: "memory"); break;
-                    case 3: if constexpr (GH == 3) asm volatile("s_waitcnt vmcnt(18) lgkmcnt(0)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(14) lgkmcnt(0)" ::: "memory"); break;
-                    case 4: if constexpr (GH == 3) asm volatile("s_waitcnt vmcnt(20) lgkmcnt(0)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)" ::: "memory"); break;
-                    case 5: if constexpr (GH == 3) asm volatile("s_waitcnt vmcnt(22) lgkmcnt(0)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(18) lgkmcnt(0)" ::: "memory"); break;
-                    case 6: if constexpr (GH == 3) asm volatile("s_waitcnt vmcnt(24) lgkmcnt(0)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(20) lgkmcnt(0)" ::: "memory"); break;
-                    case 7: if constexpr (GH == 3) asm volatile("s_waitcnt vmcnt(26) lgkmcnt(0)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(22) lgkmcnt(0)" ::: "memory"); break;
-                    case 8: if constexpr (GH == 3) asm volatile("s_waitcnt vmcnt(28) lgkmcnt(0)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(24) lgkmcnt(0)" ::: "memory"); break;
-                    default: if constexpr (GH == 3) asm volatile("s_waitcnt vmcnt(30) lgkmcnt(0)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(26) lgkmcnt(0)" ::: "memory"); break;
+                switch (extra >> 1) {                   // 4 GH pieces + the stores, in pairs; capped at 18 more
+                    case 0: wait_vm_lgkm0<4 * GH + 0>(); break;
+                    case 1: wait_vm_lgkm0<4 * GH + 2>(); break;
+                    case 2: wait_vm_lgkm0<4 * GH + 4>(); break;
+                    case 3: wait_vm_lgkm0<4 * GH + 6>(); break;
+                    case 4: wait_vm_lgkm0<4 * GH + 8>(); break;
+                    case 5: wait_vm_lgkm0<4 * GH + 10>(); break;
+                    case 6: wait_vm_lgkm0<4 * GH + 12>(); break;
+                    case 7: wait_vm_lgkm0<4 * GH + 14>(); break;
+                    case 8: wait_vm_lgkm0<4 * GH + 16>(); break;
+                    default: wait_vm_lgkm0<4 * GH + 18>(); break;
                 }
             } else {
-                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+                wait_vm_lgkm0<0>();
             }
         } else {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            wait_lgkm0();
         }
         S3 = S2; F3 = F2; S2 = S1; F2 = F1; S1 = 0; F1 = false;          // tick tt's own counts are filled in below
         __builtin_amdgcn_s_barrier();

@@ -28,11 +28,6 @@ __global__ __launch_bounds__(512, 1) void mask2_dw_mma_kernel(MdArgs g) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31;
     const int mi = wave & 1, nq = wave >> 1;                     // dH3 channels [32 mi, +32) x H2 columns [32 nq, +32)
     const uint32_t lds_addr = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)lds);
-    auto dma1 = [&](const void* base, uint32_t dst, uint32_t voff) __attribute__((always_inline)) {
-        uint32_t keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff), "s"(base), "s"(dst) : "memory");
-    };
     const int64_t my_steps = (g.steps - (int64_t)blockIdx.x + (int64_t)gridDim.x - 1) / (int64_t)gridDim.x;
     // step q of this workgroup = rows [128 (blockIdx.x + q gridDim.x), +128): dH3 rows are 128 bytes (8 slots, slot ^ (((row >> 1) & 1) << 2)), H2 rows 256 bytes (16 slots, ^ ((row & 3) << 2))
     auto stage = [&](int64_t q) __attribute__((always_inline)) {
@@ -44,12 +39,12 @@ __global__ __launch_bounds__(512, 1) void mask2_dw_mma_kernel(MdArgs g) {
 #pragma unroll
         for (int p2 = 0; p2 < 2; ++p2) {
             const int p = wave * 2 + p2, r = p * 8 + (lane >> 3), slot = lane & 7;
-            dma1(ab, da + (uint32_t)(p * 1024), (uint32_t)((r * 64 + ((slot ^ (((r >> 1) & 1) << 2)) * 8)) * 2));
+            lds_dma16(ab, da + (uint32_t)(p * 1024), (uint32_t)((r * 64 + ((slot ^ (((r >> 1) & 1) << 2)) * 8)) * 2));
         }
 #pragma unroll
         for (int p4 = 0; p4 < 4; ++p4) {
             const int p = wave * 4 + p4, r = p * 4 + (lane >> 4), slot = lane & 15;
-            dma1(bb, db + (uint32_t)(p * 1024), (uint32_t)((r * 128 + ((slot ^ ((r & 3) << 2)) * 8)) * 2));
+            lds_dma16(bb, db + (uint32_t)(p * 1024), (uint32_t)((r * 128 + ((slot ^ ((r & 3) << 2)) * 8)) * 2));
         }
     };
     f32x16 acc[2];
@@ -71,7 +66,7 @@ __global__ __launch_bounds__(512, 1) void mask2_dw_mma_kernel(MdArgs g) {
     const float s_ = g.sc[nq * 32 + l31], h_ = g.sh[nq * 32 + l31];
     if (my_steps > 0) stage(0);
     for (int64_t q = 0; q < my_steps; ++q) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vm<0>();
         __builtin_amdgcn_s_barrier();
         if (q + 1 < my_steps) stage(q + 1);
         const uint32_t base = lds_addr + (uint32_t)((q & 1) * MD_STEP);
@@ -80,8 +75,8 @@ __global__ __launch_bounds__(512, 1) void mask2_dw_mma_kernel(MdArgs g) {
             u32x2_t fa[2], fb[2];
 #pragma unroll
             for (int hh = 0; hh < 2; ++hh) {
-                asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(fa[hh]) : "v"(base + (uint32_t)(kk * 16 * 128) + offa[hh]));
-                asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(fb[hh]) : "v"(base + (uint32_t)(kk * 16 * 256) + offb[hh]));
+                lds_read_tr16_b64(fa[hh], base + (uint32_t)(kk * 16 * 128) + offa[hh]);
+                lds_read_tr16_b64(fb[hh], base + (uint32_t)(kk * 16 * 256) + offb[hh]);
             }
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa[0]), "+v"(fa[1]), "+v"(fb[0]), "+v"(fb[1]));
             const uint32_t hw[4] = {fb[0].x, fb[0].y, fb[1].x, fb[1].y};

@@ -107,11 +107,11 @@ __global__ __launch_bounds__(512, 2) void mask2_dw_x3_kernel(MxArgs g) {
 #pragma unroll
             for (int hh = 0; hh < 2; ++hh) {
                 const uint32_t oa = base + (uint32_t)(kk * 16 * 128) + offa[hh], ob = base + (uint32_t)(kk * 16 * 256) + offb[hh];
-                asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(fah[hh]) : "v"(oa));
-                asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(fal[hh]) : "v"(oa + (uint32_t)MX_OFF_AL));
-                asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(f1[hh]) : "v"(ob + (uint32_t)MX_OFF_M1));
-                asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(f2h[hh]) : "v"(ob + (uint32_t)MX_OFF_M2H));
-                asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(f2l[hh]) : "v"(ob + (uint32_t)MX_OFF_M2L));
+                lds_read_tr16_b64(fah[hh], oa);
+                lds_read_tr16_b64(fal[hh], oa + (uint32_t)MX_OFF_AL);
+                lds_read_tr16_b64(f1[hh], ob + (uint32_t)MX_OFF_M1);
+                lds_read_tr16_b64(f2h[hh], ob + (uint32_t)MX_OFF_M2H);
+                lds_read_tr16_b64(f2l[hh], ob + (uint32_t)MX_OFF_M2L);
             }
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fah[0]), "+v"(fah[1]), "+v"(fal[0]), "+v"(fal[1]), "+v"(f1[0]), "+v"(f1[1]), "+v"(f2h[0]), "+v"(f2h[1]),
                                                   "+v"(f2l[0]), "+v"(f2l[1]));

@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "../../include/p3hip.h"
+#include "gfx950_asm.h"          // LDS-DMA, waits, lds_barrier(), the transposing LDS read: all shared inline asm
 
 typedef uint16_t bf16_t;  // raw bfloat16 bits
 
@@ -38,9 +39,6 @@ __device__ __forceinline__ void split8(const float (&v)[8], u32x4_t& h, u32x4_t&
         l[k] = pack_bf2(v[2 * k] - __uint_as_float(hw << 16), v[2 * k + 1] - __uint_as_float(hw & 0xffff0000u));
     }
 }
-
-// workgroup barrier that waits for this wave's LDS traffic only: global loads (LDS-DMA included) stay in flight across it, unlike __syncthreads()
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 template <typename T> struct Cvt;
 template <> struct Cvt<float> {

@@ -39,16 +39,11 @@ __global__ __launch_bounds__(512, 2) void pair_bwd_mma_kernel(PfArgs g) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, hi = lane >> 5;
     const int wr = wave >> 2, wc = wave & 3;
     const uint32_t lds_addr = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)lds);
-    auto dma1 = [&](const void* base, uint32_t dst, uint32_t voff) __attribute__((always_inline)) {
-        uint32_t keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff), "s"(base), "s"(dst) : "memory");
-    };
     // ---- W2^T -> LDS once: 64 pieces of 4 rows x 256 B, 8 per wave; source chunk = slot ^ (row & 15)
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
         const int p = wave * 8 + q, row = p * 4 + (lane >> 4), slot = lane & 15;
-        dma1(g.W2t, lds_addr + (uint32_t)(p * 1024), (uint32_t)((row * 128 + ((slot ^ (row & 15)) * 8)) * 2));
+        lds_dma16(g.W2t, lds_addr + (uint32_t)(p * 1024), (uint32_t)((row * 128 + ((slot ^ (row & 15)) * 8)) * 2));
     }
     // ---- per-lane constants: the two 32-column blocks of this wave's 64 columns.  us = U_i * scale + shift, so that the ReLU decision of an element
     // is fma(V_j, scale, us) > 0; a row i beyond N gets us = -inf (never on).  The BatchNorm sums are rebuilt from the dU / dV partial sums at the end:
@@ -77,10 +72,10 @@ __global__ __launch_bounds__(512, 2) void pair_bwd_mma_kernel(PfArgs g) {
         for (int q = 0; q < 4; ++q) {
             const int p = wave * 4 + q, r = p * 4 + (lane >> 4), slot = lane & 15;      // tile row r = jj * 8 + ii
             const int ii = min(r & 7, N - 1 - i0), jj = min(j0 + (r >> 3), N - 1);      // clamped: masked in the epilogue
-            dma1(dHb, da + (uint32_t)(p * 1024), (uint32_t)((((int64_t)ii * N + jj) * 128 + ((slot ^ (r & 15)) * 8)) * 2));
+            lds_dma16(dHb, da + (uint32_t)(p * 1024), (uint32_t)((((int64_t)ii * N + jj) * 128 + ((slot ^ (r & 15)) * 8)) * 2));
         }
         const int jv = min(j0 + wave * 2 + (lane >> 5), N - 1);
-        dma1(Vb, dv + (uint32_t)(wave * 1024), (uint32_t)((jv * 256 + (lane & 31) * 8) * 2));
+        lds_dma16(Vb, dv + (uint32_t)(wave * 1024), (uint32_t)((jv * 256 + (lane & 31) * 8) * 2));
     };
     const int nsteps = (N + PF_JT - 1) / PF_JT;
     float du[2][4], a_v[2], dvp[2][2][4];         // du: RAW sums of dz over j (scaled at the end); a_v = sum_j V_j sum_i dz
@@ -109,7 +104,7 @@ __global__ __launch_bounds__(512, 2) void pair_bwd_mma_kernel(PfArgs g) {
     const uint32_t arow = (uint32_t)((wr * 64 + l31) * 256), brow = (uint32_t)((wc * 64 + l31) * 256);
     if (nsteps > 0) stage(0);
     for (int st = 0; st < nsteps; ++st) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // this wave's pieces of step st (and W2^T); the stores of step st - 2 are long done
+        wait_vm<0>();                                               // this wave's pieces of step st (and W2^T); the stores of step st - 2 are long done
         __builtin_amdgcn_s_barrier();                               // ... every wave's pieces; all reads of step st - 1 (whose buffers step st + 1 takes) are done
         if (st + 1 < nsteps) stage(st + 1);
         if (st > 0) store_dv(st - 1);
@@ -163,7 +158,7 @@ __global__ __launch_bounds__(512, 2) void pair_bwd_mma_kernel(PfArgs g) {
             }
     }
     if (nsteps > 0) store_dv(nsteps - 1);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    wait_lgkm0();
     __builtin_amdgcn_s_barrier();                                   // operand images are dead: their space takes the folds
     // ---- dU[b, i0 + ii, c] = sum over the two wave rows; BatchNorm sums over both half-waves and wave rows
     float* red = reinterpret_cast<float*>(lds);                     // [2][8][256] dU, then [2][2][256] sums

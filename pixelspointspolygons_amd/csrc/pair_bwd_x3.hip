@@ -50,11 +50,6 @@ __global__ __launch_bounds__(512, 2) void pair_bwd_x3_kernel(PxArgs g) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, hi = lane >> 5;
     const int c = wave * 32 + l31;                                   // this lane's output channel
     const uint32_t lds_addr = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)lds);
-    auto dma1 = [&](const void* base, uint32_t dst, uint32_t voff) __attribute__((always_inline)) {
-        uint32_t keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff), "s"(base), "s"(dst) : "memory");
-    };
     // ---- W2^T row c, k = 16 kk + 8 hi .. + 8: B fragments of the 8 k-blocks, hi and lo
     bf16x8_t wh[8], wl[8];
     {
@@ -90,13 +85,13 @@ __global__ __launch_bounds__(512, 2) void pair_bwd_x3_kernel(PxArgs g) {
             const int p = wave * 4 + q, r = p * 4 + (lane >> 4), ck = (lane & 15) ^ (r & 15);
             const int ii = min(r & 7, N - 1 - i0), jj = min(j0 + (r >> 3), N - 1);      // clamped: masked in the epilogue
             const uint32_t voff = (uint32_t)((((int64_t)ii * N + jj) * 128 + ck * 8) * 4);
-            dma1(dHb, dst + (uint32_t)(p * 2048), voff);
-            dma1(dHb, dst + (uint32_t)(p * 2048 + 1024), voff + 16u);
+            lds_dma16(dHb, dst + (uint32_t)(p * 2048), voff);
+            lds_dma16(dHb, dst + (uint32_t)(p * 2048 + 1024), voff + 16u);
         }
     };
     auto convert = [&](int st) __attribute__((always_inline)) {
-        __builtin_amdgcn_s_waitcnt(0x0F70);                          // vmcnt(0): this lane's own pieces and everything older (the builtin, not asm: the compiler's
-        asm volatile("" ::: "memory");                                // counter model then knows the V loads are complete too and inserts no waits of its own for them)
+        wait_vm0_tracked();                                           // vmcnt(0): this lane's own pieces and everything older, the V loads included
+        asm volatile("" ::: "memory");
         unsigned char* base = lds + (st & 1) * PX_TILE + wave * 4 * 2048 + lane * 16;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -192,7 +187,7 @@ __global__ __launch_bounds__(512, 2) void pair_bwd_x3_kernel(PxArgs g) {
                     }
                 }
         }
-        __builtin_amdgcn_s_waitcnt(0x0F70);                          // vmcnt(0) on every path (see convert)
+        wait_vm0_tracked();                                          // vmcnt(0) on every path (see convert)
         if (st + 1 < nsteps) convert(st + 1);
     }
     if (nsteps > 0) {

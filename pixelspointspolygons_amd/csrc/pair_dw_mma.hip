@@ -40,11 +40,6 @@ __global__ __launch_bounds__(512, 1) void pair_dw_mma_kernel(PdArgs g) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, hi = lane >> 5;
     const int wr = wave >> 2, wc = wave & 3;                  // output block: channels n of dH2 [64 wr, +64) x columns c [64 wc, +64)
     const uint32_t lds_addr = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)lds);
-    auto dma1 = [&](const void* base, uint32_t dst, uint32_t voff) __attribute__((always_inline)) {
-        uint32_t keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff), "s"(base), "s"(dst) : "memory");
-    };
     const int nsteps = N / PD_JT;
     const int my_units = (g.units - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
     const int total = my_units * nsteps;                       // steps of this workgroup, over all its units
@@ -58,9 +53,9 @@ __global__ __launch_bounds__(512, 1) void pair_dw_mma_kernel(PdArgs g) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int p = wave * 4 + q, r = p * 4 + (lane >> 4), slot = lane & 15;      // tile row r = jj * 8 + ii
-            dma1(dHb, da + (uint32_t)(p * 1024), (uint32_t)((((int64_t)(r & 7) * N + j0 + (r >> 3)) * 128 + ((slot ^ ((r & 3) << 2)) * 8)) * 2));
+            lds_dma16(dHb, da + (uint32_t)(p * 1024), (uint32_t)((((int64_t)(r & 7) * N + j0 + (r >> 3)) * 128 + ((slot ^ ((r & 3) << 2)) * 8)) * 2));
         }
-        dma1(Vb, dv + (uint32_t)(wave * 1024), (uint32_t)(((j0 + wave * 2 + (lane >> 5)) * 256 + (lane & 31) * 8) * 2));
+        lds_dma16(Vb, dv + (uint32_t)(wave * 1024), (uint32_t)(((j0 + wave * 2 + (lane >> 5)) * 256 + (lane & 31) * 8) * 2));
     };
     f32x16 acc[2][2];
 #pragma unroll
@@ -96,7 +91,7 @@ __global__ __launch_bounds__(512, 1) void pair_dw_mma_kernel(PdArgs g) {
                 for (int ii = 0; ii < 8; ++ii) us[jb][ii] = fmaf(bf2f(g.U[((int64_t)b * N + i0 + ii) * 256 + c]), s_[jb], hh);
             }
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this wave's pieces of step gs (the U loads above included)
+        wait_vm<0>();                                           // this wave's pieces of step gs (the U loads above included)
         __builtin_amdgcn_s_barrier();                           // every wave's pieces; all reads of step gs - 1 (whose buffers step gs + 1 takes) are done
         if (gs + 1 < total) stage(gs + 1);
         const uint32_t ab = lds_addr + (uint32_t)((gs & 1) * PD_A_BYTES);
@@ -107,7 +102,7 @@ __global__ __launch_bounds__(512, 1) void pair_dw_mma_kernel(PdArgs g) {
 #pragma unroll
             for (int ib = 0; ib < 2; ++ib)
 #pragma unroll
-                for (int hh = 0; hh < 2; ++hh) asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(fa[ib][hh]) : "v"(ab + (uint32_t)(kk * 16 * 256) + troff[ib][hh]));
+                for (int hh = 0; hh < 2; ++hh) lds_read_tr16_b64(fa[ib][hh], ab + (uint32_t)(kk * 16 * 256) + troff[ib][hh]);
             // generated operand: rows (j = 2 kk + hi, i = 0..7) of columns c
             bf16x8_t bfr[2];
 #pragma unroll

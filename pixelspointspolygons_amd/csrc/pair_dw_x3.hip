@@ -46,11 +46,6 @@ __global__ __launch_bounds__(512, 2) void pair_dw_x3_kernel(DxArgs g) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, hi = lane >> 5;
     const int c = wave * 32 + l31;                                // this lane's column of dW2
     const uint32_t lds_addr = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)lds);
-    auto dma1 = [&](const void* base, uint32_t dst, uint32_t voff) __attribute__((always_inline)) {
-        uint32_t keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff), "s"(base), "s"(dst) : "memory");
-    };
     const int nsteps = N / DX_JT;
     const int my_units = (g.units - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
     const int total = my_units * nsteps;                       // steps of this workgroup, over all its units
@@ -71,13 +66,13 @@ __global__ __launch_bounds__(512, 2) void pair_dw_x3_kernel(DxArgs g) {
         for (int q = 0; q < 4; ++q) {
             const int p = wave * 4 + q, r = p * 4 + (lane >> 4), ck = (lane & 15) ^ ((r & 3) << 2);
             const uint32_t voff = (uint32_t)((((int64_t)(r & 7) * N + j0 + (r >> 3)) * 128 + ck * 8) * 4);
-            dma1(dHb, dst + (uint32_t)(p * 2048), voff);
-            dma1(dHb, dst + (uint32_t)(p * 2048 + 1024), voff + 16u);
+            lds_dma16(dHb, dst + (uint32_t)(p * 2048), voff);
+            lds_dma16(dHb, dst + (uint32_t)(p * 2048 + 1024), voff + 16u);
         }
     };
     auto convert = [&](int gs) __attribute__((always_inline)) {
-        __builtin_amdgcn_s_waitcnt(0x0F70);                          // vmcnt(0): this lane's own pieces and everything older (the builtin, not asm: the compiler's
-        asm volatile("" ::: "memory");                                // counter model then knows the V loads are complete too and inserts no waits of its own for them)
+        wait_vm0_tracked();                                           // vmcnt(0): this lane's own pieces and everything older, the V loads included
+        asm volatile("" ::: "memory");
         unsigned char* base = lds + (gs & 1) * DX_TILE + wave * 4 * 2048 + lane * 16;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -171,8 +166,8 @@ __global__ __launch_bounds__(512, 2) void pair_dw_x3_kernel(DxArgs g) {
             if (kk + 2 < 8) rdset(kk + 2, f0);
             block(kk + 1, f1);
         }
-        __builtin_amdgcn_s_waitcnt(0x0F70);                      // vmcnt(0), unconditionally: on a path without it the compiler's counter model keeps the V loads
-        if (gs + 1 < total) convert(gs + 1);                    // pending and waits for them inside the next step's products - i.e. for the DMA pieces queued behind
+        wait_vm0_tracked();                                      // vmcnt(0) on every path (see convert)
+        if (gs + 1 < total) convert(gs + 1);
     };
     for (int gs = 0; gs < total; gs += 2) {
         step(gs, v, vn);

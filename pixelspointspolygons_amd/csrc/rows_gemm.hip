@@ -30,8 +30,6 @@ struct RGArgs {
     int64_t groups;         // R / 32
 };
 
-__device__ __forceinline__ void wave_lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
 template <int K, int N, int MODE>
 __global__ __launch_bounds__(256, 2) void rows_gemm_kernel(RGArgs g) {
     constexpr int KS = K / 16, NB = N / 32, P = N + 4, CH = N / 8;     // k-steps, 32-channel blocks, image pitch (floats), 8-channel chunks per row
@@ -113,7 +111,7 @@ __global__ __launch_bounds__(256, 2) void rows_gemm_kernel(RGArgs g) {
                 if constexpr (MODE == 0) { s1[nb] += v; s2[nb] += v * v; }
                 img[crow32(r, hi) * P + nb * 32 + l32] = v;
             }
-        wave_lds_fence();
+        wait_lgkm0();
 #pragma unroll
         for (int t = 0; t < TASKS; ++t) {
             const int row = rsel + RSTEP * t;
@@ -132,7 +130,7 @@ __global__ __launch_bounds__(256, 2) void rows_gemm_kernel(RGArgs g) {
             for (int q = 0; q < 4; ++q) o[q] = pack_bf2(v[2 * q], v[2 * q + 1]);
             *reinterpret_cast<u32x4_t*>(g.Y + (gi * 32 + row) * N + c8) = o;
         }
-        wave_lds_fence();       // the image is read before the next group overwrites it
+        wait_lgkm0();       // the image is read before the next group overwrites it
 #pragma unroll
         for (int s = 0; s < KS; ++s) xa[s] = xn[s];
     }

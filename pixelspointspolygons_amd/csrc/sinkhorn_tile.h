@@ -56,7 +56,7 @@ __device__ __forceinline__ void st_off(float* base, uint32_t byte_off, float v) 
     *reinterpret_cast<float*>(reinterpret_cast<char*>(base) + byte_off) = v;
 }
 
-// The loops synchronise with lds_barrier() (p3_common.h), which orders LDS traffic only.  __syncthreads() also waits for every outstanding GLOBAL access
+// The loops synchronise with lds_barrier() (gfx950_asm.h), which orders LDS traffic only.  __syncthreads() also waits for every outstanding GLOBAL access
 // (s_waitcnt vmcnt(0)): with the per-iteration dual / vector stores of these loops in flight that is a ~1 us store round trip per barrier (r04: 2.5 us
 // per iteration, two barriers each).  The stores are consumed by a later launch (or behind the final __syncthreads of the kernel), never inside the loop.
 
