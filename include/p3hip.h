@@ -694,6 +694,33 @@ int p3_hisup_val_loss(const float* jloc, const float* joff, const float* mask, c
 int64_t p3_hisup_val_loss_workspace_bytes(int B, int H, int W);
 
 /* ------------------------------------------------------------------------------------------
+ * HiSup training losses with their gradients: the five lines of `EncoderDecoder.forward_train` (models/hisup/model_hisup.py:302-306, sigmoid_l1_loss
+ * :27-37) weighted as `LossReducer` does (train/trainer_hisup.py:31-39), forward and backward in one call.  The five prediction maps are fp32, each
+ * given as base pointer + (batch, channel, pixel) strides in elements as in the block above (NCHW and token-major rows, in any mix): jloc 3 channels,
+ * joff / mask / afm / remask 2.  Targets as p3_hisup_val_loss reads them (contiguous): t_jloc int64 [B,1,H,W], t_joff fp32 [B,2,H,W], t_mask fp32
+ * [B,1,H,W], t_afm fp32 [B,2,H,W].  weights[5] (host) in the order loss_jloc, loss_joff, loss_mask, loss_afm, loss_remask.
+ * losses fp32 [6] (device) = the five un-weighted losses in that order, then total = sum w_k * loss_k.
+ * d_jloc .. d_remask: d total / d map, each written with the strides of its prediction from a base pointer of its own; only the map's valid
+ * channels of the B * H * W pixels are written (the padding of token-major rows keeps its contents).  All five or none: without them only the
+ * values are computed, bit for bit the same values.  With N = B * H * W, pixel p of image b:
+ *   jloc, mask, remask (cross-entropy; mask classes = (int64) t_mask):  w_k / N * (softmax(l)_c - [c == t])
+ *   afm (L1 over 2N elements):                                            w_afm / 2N * sign(afm - t_afm), sign(0) = 0
+ *   joff: on junction pixels (t_jloc in {1, 2})                            w_joff / 2N * (H * W / c_b) * sign(s - 0.5 - t_joff) * s * (1 - s),
+ *         s = sigmoid(joff), c_b = junction pixels of image b (the reference's t / w with w == 0 -> 1); zero elsewhere and in an image without junctions.
+ * Targets select by comparison only, so any target value is safe: a t_jloc outside {0, 1} is class 2 of the cross-entropy, a truncated t_mask other
+ * than 0 is class 1.  No host synchronisation, no floating-point atomics: workgroup partials are summed in one fixed order in float64 and every
+ * output repeats bit for bit.  Three launches with gradients (junction count, pixel pass, final sum), two without.  H * W <= 2^22, B <= 65535.
+ * workspace: p3_hisup_train_loss_workspace_bytes(B, H, W) bytes of device scratch, contents irrelevant on entry.
+ * ------------------------------------------------------------------------------------------ */
+int p3_hisup_train_loss(const float* jloc, int64_t jloc_sb, int64_t jloc_sc, int64_t jloc_sp, const float* joff, int64_t joff_sb, int64_t joff_sc,
+                        int64_t joff_sp, const float* mask, int64_t mask_sb, int64_t mask_sc, int64_t mask_sp, const float* afm, int64_t afm_sb,
+                        int64_t afm_sc, int64_t afm_sp, const float* remask, int64_t remask_sb, int64_t remask_sc, int64_t remask_sp,
+                        const int64_t* t_jloc, const float* t_joff, const float* t_mask, const float* t_afm, int B, int H, int W,
+                        const float* weights, float* losses, float* d_jloc, float* d_joff, float* d_mask, float* d_afm, float* d_remask,
+                        void* workspace, void* stream);
+int64_t p3_hisup_train_loss_workspace_bytes(int B, int H, int W);
+
+/* ------------------------------------------------------------------------------------------
  * FFL active-contour (ACM) polygon optimiser: predict/ffl/polygonize_acm.py:77-220 (`PolygonAlignLoss`, `TensorPolyOptimizer`), `steps` plain-SGD
  * iterations of every contour vertex in one call, with the analytic gradient of the reference's loss instead of an autograd graph.
  * pos fp32 [N,2] (row, col), updated in place.  poly_slice int32 [P,2] = [first vertex, one past the last) of each polygon, poly_batch int32 [P] its

@@ -7,6 +7,7 @@
 // Reproducibility: every selection runs on integers (64-bit keys, integer vector atomics whose result does not depend on their order, a
 // final sort on unique keys); the one float sum (a region's mean probability) is accumulated as 32.32 fixed point with integer atomics.
 #include "p3_common.h"
+#include "hisup_loss_pixel.h"
 
 namespace {
 
@@ -292,13 +293,9 @@ __global__ __launch_bounds__(256) void region_score_kernel(const int32_t* __rest
 }
 
 // ================================================================================================ validation losses
-constexpr int VL_PIX = 1024;           // pixels per workgroup
-constexpr int VL_N = 6;                // partials per workgroup: CE jloc | CE mask | CE remask | L1 afm | masked |sigmoid(joff) - 0.5 - t| | junction pixels
-
-__device__ __forceinline__ float ce2(float l0, float l1, int t) {
-    const float m = fmaxf(l0, l1);
-    return m + logf(expf(l0 - m) + expf(l1 - m)) - (t ? l1 : l0);
-}
+// the per-pixel arithmetic lives in hisup_loss_pixel.h, shared with p3_hisup_train_loss (hisup_loss.hip)
+constexpr int VL_PIX = hisup_px::PIX;
+constexpr int VL_N = hisup_px::NPART;
 
 // grid (ceil(HW / VL_PIX), B); parts [B, nblk, VL_N]
 __global__ __launch_bounds__(256) void val_loss_partial_kernel(const float* __restrict__ jloc, const float* __restrict__ joff,
@@ -315,16 +312,14 @@ __global__ __launch_bounds__(256) void val_loss_partial_kernel(const float* __re
         if (pix >= HW) break;
         const int64_t o1 = (int64_t)b * HW + pix, o2 = (int64_t)b * 2 * HW + pix, o3 = (int64_t)b * 3 * HW + pix;
         const int64_t tj = t_jloc[o1];
-        const float l0 = jloc[o3], l1 = jloc[o3 + HW], l2 = jloc[o3 + 2 * (int64_t)HW];
-        const float m = fmaxf(l0, fmaxf(l1, l2));
-        acc[0] += m + logf(expf(l0 - m) + expf(l1 - m) + expf(l2 - m)) - (tj == 0 ? l0 : (tj == 1 ? l1 : l2));
-        const int tm = (int)(int64_t)t_mask[o1];                        // targets['mask'].long()
-        acc[1] += ce2(mask[o2], mask[o2 + HW], tm);
-        acc[2] += ce2(remask[o2], remask[o2 + HW], tm);
+        acc[0] += hisup_px::ce3(jloc[o3], jloc[o3 + HW], jloc[o3 + 2 * (int64_t)HW], tj);
+        const int tm = hisup_px::mask_class(t_mask[o1]);
+        acc[1] += hisup_px::ce2(mask[o2], mask[o2 + HW], tm);
+        acc[2] += hisup_px::ce2(remask[o2], remask[o2 + HW], tm);
         acc[3] += fabsf(afm[o2] - t_afm[o2]) + fabsf(afm[o2 + HW] - t_afm[o2 + HW]);
-        if (tj == 1 || tj == 2) {
-            const float s0 = 1.f / (1.f + expf(-joff[o2])) - 0.5f, s1 = 1.f / (1.f + expf(-joff[o2 + HW])) - 0.5f;
-            acc[4] += fabsf(s0 - t_joff[o2]) + fabsf(s1 - t_joff[o2 + HW]);
+        if (hisup_px::is_junction(tj)) {
+            acc[4] += fabsf(hisup_px::joff_residual(hisup_px::sigmoidf(joff[o2]), t_joff[o2])) +
+                      fabsf(hisup_px::joff_residual(hisup_px::sigmoidf(joff[o2 + HW]), t_joff[o2 + HW]));
             acc[5] += 1.f;
         }
     }

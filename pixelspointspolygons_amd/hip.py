@@ -1085,7 +1085,66 @@ def hisup_val_loss(jloc, joff, mask, afm_pred, remask, t_jloc, t_joff, t_mask, t
     return losses
 
 
-HISUP_MAX_EDGE = 32766      # csrc/hisup_polygon.hip: ring coordinates are packed into 16 bits each
+def hisup_train_loss(jloc, joff, mask, afm_pred, remask, t_jloc, t_joff, t_mask, t_afm, weights, need_grad=True, shape=None, grads=None):
+    """p3_hisup_train_loss: the five HiSup training losses (model_hisup.py:302-306) and the gradients of their weighted total, in one call
+    -> (losses fp32 [6] = loss_jloc, loss_joff, loss_mask, loss_afm, loss_remask (un-weighted), total = sum weights[k] * loss_k,
+        [d total / d jloc, d joff, d mask, d afm, d remask] | None).
+    Each prediction is NCHW fp32 or token-major fp32 rows [B*H*W, >= n] with shape = (B, H, W) (`_logit_map`), in any mix; its gradient has the same
+    layout (for rows: an [R, n] view with the prediction's row stride).  grads: the five output tensors, given by the caller (same layouts and strides);
+    only their valid channels are written.  need_grad=False computes the values alone - the same values, bit for bit.  No host synchronisation."""
+    names = ("jloc", "joff", "mask", "afm", "remask")
+    preds = (jloc, joff, mask, afm_pred, remask)
+    bhw = [(t.shape[0], t.shape[2], t.shape[3]) if t.dim() == 4 else (tuple(int(v) for v in shape) if shape is not None else None) for t in preds]
+    B, H, W = bhw[0] if bhw[0] is not None and len(bhw[0]) == 3 else (0, 0, 0)
+    for k, v in zip(names, bhw):                         # shapes first, devices second: a shape error reads as one on any tensor
+        if v != (B, H, W) or B < 1:
+            raise P3Error(f"hisup_train_loss: the five maps must share one (B, H, W); jloc is {bhw[0]}, {k} is {v}")
+    want = ((t_jloc, 1), (t_joff, 2), (t_mask, 1), (t_afm, 2))
+    for i, (t, n) in enumerate(want):
+        if tuple(t.shape) != (B, n, H, W):
+            raise P3Error(f"hisup_train_loss: target {i} must be {(B, n, H, W)}, got {tuple(t.shape)}")
+    if H * W > HISUP_MAX_HW:
+        raise P3Error(f"hisup_train_loss: H * W = {H * W} is beyond the {HISUP_MAX_HW} pixels per map the kernel supports")
+    if len(weights) != 5:
+        raise P3Error(f"hisup_train_loss: five loss weights expected, got {len(weights)}")
+    maps = [_logit_map(t, n, shape, f"hisup_train_loss({k})") for t, n, k in zip(preds, (3, 2, 2, 2, 2), names)]
+    dev = maps[0][0].device
+    for t, _ in want:
+        _dev(t)
+    tj = t_jloc.contiguous().to(torch.int64)
+    tt = [t.contiguous().float() for t in (t_joff, t_mask, t_afm)]
+    out = None
+    if need_grad:
+        out = []
+        for i, (k, (t, _, _, _, st)) in enumerate(zip(names, maps)):
+            n = 3 if i == 0 else 2
+            if grads is None:
+                g = torch.empty_like(t) if t.dim() == 4 else torch.empty((t.shape[0], st[2]), dtype=torch.float32, device=dev)[:, :n]
+            else:
+                g = grads[i]
+                if g.dim() == 4 and not g.is_contiguous():
+                    raise P3Error(f"hisup_train_loss: the gradient of {k} must be contiguous")
+                gm = _logit_map(g, n, shape, f"hisup_train_loss(d {k})")
+                if g.dim() != t.dim() or gm[1:] != (B, H, W, st):
+                    raise P3Error(f"hisup_train_loss: the gradient of {k} needs the layout and strides of its prediction {st}, got {gm[4]}")
+                g = g if g.dim() == 4 else g[:, :n]
+            out.append(g)
+    elif grads is not None:
+        raise P3Error("hisup_train_loss: grads given with need_grad=False")
+    losses = torch.empty(6, dtype=torch.float32, device=dev)
+    ws = workspace(int(lib().p3_hisup_train_loss_workspace_bytes(B, H, W)), dev, "hisup_train_loss")
+    cw = (c_float * 5)(*[float(v) for v in weights])
+    s = [m[4] for m in maps]
+    gp = out if out is not None else [None] * 5
+    check(lib().p3_hisup_train_loss(ptr(maps[0][0]), s[0][0], s[0][1], s[0][2], ptr(maps[1][0]), s[1][0], s[1][1], s[1][2],
+                                    ptr(maps[2][0]), s[2][0], s[2][1], s[2][2], ptr(maps[3][0]), s[3][0], s[3][1], s[3][2],
+                                    ptr(maps[4][0]), s[4][0], s[4][1], s[4][2], ptr(tj), ptr(tt[0]), ptr(tt[1]), ptr(tt[2]), B, H, W, cw,
+                                    ptr(losses), ptr(gp[0]), ptr(gp[1]), ptr(gp[2]), ptr(gp[3]), ptr(gp[4]), ptr(ws), stream()),
+          "p3_hisup_train_loss")
+    return losses, out
+
+
+HISUP_MAX_EDGE = 32766     # csrc/hisup_polygon.hip: ring coordinates are packed into 16 bits each
 
 
 def hisup_polygons_capacity(B, H, W, max_regions):
