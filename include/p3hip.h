@@ -772,7 +772,7 @@ int64_t p3_acm_workspace_bytes(int64_t N);
  * Update (:380, 404-409): torch.optim.RMSprop(alpha = 0.9, eps = 1e-8, no momentum, not centred): sq = 0.9 sq + 0.1 g^2,
  * pos -= lr_i * g / (sqrt(sq) + eps).  A node with is_tip (degree 1) keeps its position; its sq is still updated.
  *
- * The work unit is a connected component of the skeleton graph, described by a plan the host builds once per skeleton (csrc/asm.hip explains it):
+ * The work unit is a connected component of the skeleton graph, described by a plan built once per skeleton, on the host or by p3_asm_plan below (csrc/asm.hip explains it):
  * comp_ptr int32 [C+1] delimits components inside cn_node int32 [CN] (node ids; an entry's index inside its component is its local index);
  * cn_occ int32 [CN+1] delimits each entry's occurrences, ascending in k, inside slot_nb int32 [S,2] = local index of the node at k-1 (-1 at a path
  * start) and at k+1 (-1 at a path end).  is_tip uint8 [N], node_batch int32 [N].  Every index is clamped on the device.
@@ -852,6 +852,46 @@ int p3_corner_split(const float* pos, int64_t N, const int64_t* index, int64_t K
                     int max_pieces, float* out_pos, int32_t* out_src, int64_t* piece_slice, int32_t* piece_poly, int32_t* piece_batch,
                     uint8_t* stage_flags, int32_t* counts, int32_t* status, void* workspace, void* stream);
 int64_t p3_corner_split_workspace_bytes(int64_t E, int P);
+
+/* ------------------------------------------------------------------------------------------
+ * FFL active-skeleton initialisation from marching squares: the conversion half of get_marching_squares_skeleton (predict/ffl/polygonize_asm.py:581-638)
+ * and tensorskeleton.py:87-159 on the device, behind p3_init_contours (csrc/skeleton_init.hip).
+ * Input, the contour container exactly as p3_init_contours leaves it: pos fp32 [N,2], poly_slice int64 [P,2], poly_batch int32 [P], is_endpoint uint8 [N]; a
+ * closed contour does not repeat its first point, an open one has is_endpoint = 1 on both ends; contours ordered by image.  Every slice and image is clamped.
+ * A contour of n stored points is CLOSED when its first point is no endpoint.  The reference tests max|c[0] - c[-1]| < 1e-6 on skimage's points instead; the
+ * two agree whenever no pixel equals the level (an open contour's two ends lie on different border edges, which can only share a point at a grid vertex whose
+ * value is the level).  filter != 0 keeps a contour when vertices >= 3 - a closed contour counts its repeated point: n + 1 - and
+ * min_area < |sum_i x_i y_(i+1) - y_i x_(i+1)| / 2 (cyclic over the n points, evaluated in double from the fp32 positions; the order of the sum is fixed per
+ * build but not that of numpy: a contour within rounding of min_area may be decided differently).  filter == 0 keeps every contour with a point (min_area=None).
+ * Output, kept contours in container order, nodes numbered in that order (the fields of skeletons_to_tensorskeleton([contours_to_skeleton(c_b, min_area)])):
+ * out_pos fp32 [max_nodes,2] (bit copies); degrees int64 [max_nodes] = 2, and 1 on the two ends of an open contour; path_index int64 [max_slots]: a path's
+ * node ids, a closed one's first id once more; path_delim int64 [max_paths+1], entry P' = M'; batch int64 [max_nodes]; batch_delim int64 [B+1] = kept paths
+ * in front of each image; counts int32 [4] = (N' nodes, M' slots, P' paths, nodes of the longest kept path); status int32 [1] bit 0 = a capacity was too
+ * small: counts hold the true totals and nothing is written past a capacity.  N nodes, N + P slots and P paths can never overflow.
+ * One writer per element, no atomics: two runs give the same bits and an image alone gives the rows it gives inside a batch.  Three launches and one memset
+ * whatever the data, no host synchronisation.  P == 0 or N == 0: zero counts and batch_delim, nothing else is touched.
+ * workspace: p3_skeleton_from_contours_workspace_bytes(P) bytes.
+ *
+ * p3_asm_plan: the plan of p3_asm_optimize (above) from path_index int64 [M] and path_delim int64 [D] (D = paths + 1, or 0) for N nodes, entry for entry
+ * what polygonize_asm.AsmPlan builds on the host.  Path boundaries are the INTERIOR entries path_delim[1 .. D-2] that lie in 1 .. M-1 (the first path starts
+ * at 0, the last ends at M, a repeated delimiter is an empty path and changes nothing); an edge is (k, k+1) for every k that is no path end; components are
+ * ordered by their smallest node id and list their nodes in ascending id; a node on no path is a component of its own.  Outputs, all int32: comp_ptr [N+1]
+ * (C + 1 entries used), cn_node [N], cn_occ [N+1], slot_nb [M,2] = local index of the node at k-1 and k+1, -1 at a path start / end, node_local [N],
+ * slot_k [M] (a node's slots ascending in k); counts [2] = (C, nodes of the largest component); status [1]: bit 1 = a node id outside [0, N) (it is
+ * clamped before any use as an index; the outputs are then no plan).  No float arithmetic; integer atomics only where their order cannot show (minimum,
+ * maximum, or); two runs give the same bits.  The component search (labels over PATHS, lowered along shared nodes until a round changes nothing) has no
+ * round cap: labels never rise and every round but the last lowers one (csrc/skeleton_init.hip).  It runs inside one launch, so the number of launches
+ * depends on N and M only; no host synchronisation.  N == 0: C = 0, comp_ptr[0] = cn_occ[0] = 0 (status bit 1 when M > 0).
+ * workspace: p3_asm_plan_workspace_bytes(N, M) bytes.
+ * ------------------------------------------------------------------------------------------ */
+int p3_skeleton_from_contours(const float* pos, int64_t N, const int64_t* poly_slice, const int32_t* poly_batch, const uint8_t* is_endpoint, int P, int B,
+                              int filter, double min_area, int max_nodes, int max_slots, int max_paths, float* out_pos, int64_t* degrees,
+                              int64_t* path_index, int64_t* path_delim, int64_t* batch, int64_t* batch_delim, int32_t* counts, int32_t* status,
+                              void* workspace, void* stream);
+int64_t p3_skeleton_from_contours_workspace_bytes(int P);
+int p3_asm_plan(const int64_t* path_index, int64_t M, const int64_t* path_delim, int64_t D, int64_t N, int32_t* comp_ptr, int32_t* cn_node, int32_t* cn_occ,
+                int32_t* slot_nb, int32_t* node_local, int32_t* slot_k, int32_t* counts, int32_t* status, void* workspace, void* stream);
+int64_t p3_asm_plan_workspace_bytes(int64_t N, int64_t M);
 
 /* ------------------------------------------------------------------------------------------
  * HiSup polygons: models/hisup/polygon.py:56-93,111-169 (`ext_c_to_poly_coco`, `diagonal_to_square`, `simple_polygon`, `get_poly_crowdai` with

@@ -1424,7 +1424,7 @@ def asm_optimize(pos, sq, plan, is_tip, batch, indicator, c0c2, knots, data_leve
                  losses=False, force_fallback=False):
     """p3_asm_optimize (predict/ffl/polygonize_asm.py:133-421): `steps` RMSprop iterations first_iter .. first_iter + steps - 1 on pos fp32 [N,2] (row, col),
     IN PLACE, with the state sq fp32 [N,2] (zeros on a first call) read and written.  plan: polygonize_asm.AsmPlan on the device (components, occurrence
-    lists and neighbour indices derived from path_index / path_delim, built once per skeleton on the host).  is_tip [N] (degrees == 1), batch [N].
+    lists and neighbour indices derived from path_index / path_delim, built once per skeleton on the host) or its device-built twin (asm_plan below).  is_tip [N] (degrees == 1), batch [N].
     indicator [B,H,W] or seg [B,C,H,W] (channel 0 is taken), c0c2 [B,4,H,W]; bf16 / strided maps are copied to contiguous fp32.
     knots: [step_thresholds, data, length, crossfield] of loss_params.coefs.  grad_out: None or contiguous fp32 [N,2], receives the gradient of the last
     executed step.  Reads nothing back.  -> pos, or (pos, losses fp32 [C,3] = (align, level, length) per component at the last step, before its update)."""
@@ -1455,6 +1455,100 @@ def asm_optimize(pos, sq, plan, is_tip, batch, indicator, c0c2, knots, data_leve
                                 int(steps), int(plan.max_comp), int(bool(force_fallback)), ptr(grad_out), ptr(out), ptr(ws), stream()),
           "p3_asm_optimize")
     return (pos, out) if losses else pos
+
+
+# ------------------------------------------------------------------------------------------ FFL active-skeleton initialisation (marching squares) and plan
+def skeleton_from_contours_device(pos, poly_slice, poly_batch, is_endpoint, batch_size, min_area=None, max_nodes=None, max_slots=None, max_paths=None,
+                                  _guard=0):
+    """p3_skeleton_from_contours (the conversion half of get_marching_squares_skeleton, predict/ffl/polygonize_asm.py:581-638, plus
+    skeletons_to_tensorskeleton) without any synchronisation.  The contour container as init_contours leaves it: pos fp32 [N,2], poly_slice [P,2],
+    poly_batch [P], is_endpoint [N].  min_area None keeps every contour, a number keeps those with at least 3 vertices and a larger shoelace area.
+    -> dict(pos f32 [max_nodes,2], degrees i64 [max_nodes], path_index i64 [max_slots], path_delim i64 [max_paths+1], batch i64 [max_nodes], batch_delim i64
+    [B+1], counts i32 [4] = (nodes, slots, paths, nodes of the longest kept path), status i32 [1] (bit 0: a capacity was too small; counts are the true totals
+    then and nothing is written past the capacities)).  The default capacities N, N + P and P cannot overflow.  _guard: test hook, as init_contours_device."""
+    for t in (pos, poly_slice, poly_batch, is_endpoint):
+        _dev(t)
+    if pos.dtype != torch.float32 or pos.dim() != 2 or pos.shape[1] != 2:
+        raise P3Error(f"skeleton_from_contours: pos must be float32 [N, 2], got {pos.dtype} {tuple(pos.shape)}")
+    N, P, B = pos.shape[0], poly_slice.shape[0], int(batch_size)
+    if poly_slice.dim() != 2 or poly_slice.shape[1] != 2 or poly_batch.shape[0] != P or is_endpoint.shape[0] != N or B < 1:
+        raise P3Error(f"skeleton_from_contours: poly_slice [P, 2], poly_batch [P], is_endpoint [N] and batch_size >= 1 expected, got {tuple(poly_slice.shape)}, "
+                      f"{tuple(poly_batch.shape)}, {tuple(is_endpoint.shape)}, {batch_size}")
+    nn = max(N, 1) if max_nodes is None else int(max_nodes)
+    ns = max(N + P, 1) if max_slots is None else int(max_slots)
+    npth = max(P, 1) if max_paths is None else int(max_paths)
+    if nn < 1 or ns < 1 or npth < 1:
+        raise P3Error(f"skeleton_from_contours: max_nodes = {max_nodes}, max_slots = {max_slots}, max_paths = {max_paths}")
+    dev, arenas, g = pos.device, [], int(_guard)
+    out = dict(pos=_ic_out((nn, 2), torch.float32, dev, g, arenas), degrees=_ic_out((nn,), torch.int64, dev, g, arenas),
+               path_index=_ic_out((ns,), torch.int64, dev, g, arenas), path_delim=_ic_out((npth + 1,), torch.int64, dev, g, arenas),
+               batch=_ic_out((nn,), torch.int64, dev, g, arenas), batch_delim=_ic_out((B + 1,), torch.int64, dev, g, arenas),
+               counts=_ic_out((4,), torch.int32, dev, g, arenas), status=_ic_out((1,), torch.int32, dev, g, arenas))
+    if g:
+        out["_arenas"] = arenas
+    # converted copies stay referenced until the launch is queued
+    p32, sl = pos.contiguous(), poly_slice.to(torch.int64).contiguous()
+    pb, ep = poly_batch.to(torch.int32).contiguous(), is_endpoint.to(torch.uint8).contiguous()
+    ws = workspace(int(lib().p3_skeleton_from_contours_workspace_bytes(P)), dev, "skeleton_from_contours") if P else None
+    check(lib().p3_skeleton_from_contours(ptr(p32), N, ptr(sl), ptr(pb), ptr(ep), P, B, int(min_area is not None),
+                                          0.0 if min_area is None else float(min_area), nn, ns, npth, ptr(out["pos"]), ptr(out["degrees"]),
+                                          ptr(out["path_index"]), ptr(out["path_delim"]), ptr(out["batch"]), ptr(out["batch_delim"]), ptr(out["counts"]),
+                                          ptr(out["status"]), ptr(ws), stream()), "p3_skeleton_from_contours")
+    return out
+
+
+def skeleton_from_contours(pos, poly_slice, poly_batch, is_endpoint, batch_size, min_area=None, max_nodes=None, max_slots=None, max_paths=None):
+    """the checking form of skeleton_from_contours_device: reads counts and status once (the only read-back), raises when a capacity was too small and
+    narrows the arrays: pos [N',2], degrees [N'], path_index [M'], path_delim [P'+1] ([0] without a path), batch [N']; counts = (N', M', P', longest)."""
+    out = skeleton_from_contours_device(pos, poly_slice, poly_batch, is_endpoint, batch_size, min_area, max_nodes, max_slots, max_paths)
+    N, M, P, longest, status = torch.cat([out["counts"], out["status"]]).tolist()
+    if status & 1:
+        raise P3Error(f"skeleton_from_contours: {N} nodes, {M} slots and {P} paths do not fit max_nodes = {out['pos'].shape[0]}, max_slots = "
+                      f"{out['path_index'].shape[0]}, max_paths = {out['path_delim'].shape[0] - 1}")
+    for k in ("pos", "degrees", "batch"):
+        out[k] = out[k][:N]
+    out["path_index"] = out["path_index"][:M]
+    out["path_delim"] = out["path_delim"][:P + 1] if P else torch.zeros(1, dtype=torch.int64, device=pos.device)          # nothing was written without a path
+    out["counts"] = (N, M, P, longest)
+    return out
+
+
+ASM_PLAN_FIELDS = ("comp_ptr", "cn_node", "cn_occ", "slot_nb", "node_local", "slot_k")
+
+
+def asm_plan_device(path_index, path_delim, num_nodes, _guard=0):
+    """p3_asm_plan without any synchronisation: path_index [M], path_delim [paths + 1] and the node count -> dict of the six int32 arrays of
+    polygonize_asm.AsmPlan at their largest sizes (comp_ptr [N+1] with C + 1 entries used, cn_node [N], cn_occ [N+1], slot_nb [M,2], node_local [N], slot_k
+    [M]), counts i32 [2] = (C, nodes of the largest component) and status i32 [1] (bit 1: a node id outside [0, N); the arrays are no plan then)."""
+    for t in (path_index, path_delim):
+        _dev(t)
+    if path_index.dim() != 1 or path_delim.dim() != 1 or int(num_nodes) < 0:
+        raise P3Error(f"asm_plan: path_index [M], path_delim [P+1] and num_nodes >= 0 expected, got {tuple(path_index.shape)}, {tuple(path_delim.shape)}, {num_nodes}")
+    N, M, D = int(num_nodes), path_index.shape[0], path_delim.shape[0]
+    dev, arenas, g = path_index.device, [], int(_guard)
+    out = dict(comp_ptr=_ic_out((N + 1,), torch.int32, dev, g, arenas), cn_node=_ic_out((N,), torch.int32, dev, g, arenas),
+               cn_occ=_ic_out((N + 1,), torch.int32, dev, g, arenas), slot_nb=_ic_out((M, 2), torch.int32, dev, g, arenas),
+               node_local=_ic_out((N,), torch.int32, dev, g, arenas), slot_k=_ic_out((M,), torch.int32, dev, g, arenas),
+               counts=_ic_out((2,), torch.int32, dev, g, arenas), status=_ic_out((1,), torch.int32, dev, g, arenas))
+    if g:
+        out["_arenas"] = arenas
+    idx, delim = path_index.to(torch.int64).contiguous(), path_delim.to(torch.int64).contiguous()
+    ws = workspace(int(lib().p3_asm_plan_workspace_bytes(N, M)), dev, "asm_plan") if N else None
+    check(lib().p3_asm_plan(ptr(idx), M, ptr(delim), D, N, ptr(out["comp_ptr"]), ptr(out["cn_node"]), ptr(out["cn_occ"]), ptr(out["slot_nb"]),
+                            ptr(out["node_local"]), ptr(out["slot_k"]), ptr(out["counts"]), ptr(out["status"]), ptr(ws), stream()), "p3_asm_plan")
+    return out
+
+
+def asm_plan(path_index, path_delim, num_nodes):
+    """the checking form of asm_plan_device: reads counts and status once (the only read-back), raises on a node id outside [0, N), narrows comp_ptr to
+    [C+1]; counts = (C, max_comp) as Python ints."""
+    out = asm_plan_device(path_index, path_delim, num_nodes)
+    C, max_comp, status = torch.cat([out["counts"], out["status"]]).tolist()
+    if status & 2:
+        raise P3Error(f"asm_plan: path_index holds node ids outside [0, {int(num_nodes)})")
+    out["comp_ptr"] = out["comp_ptr"][:C + 1]
+    out["counts"] = (C, max_comp)
+    return out
 
 
 def cast(a, dtype):

@@ -4,8 +4,13 @@
 The reference differentiates `data_coef * level_loss + length_coef * total_length_loss + crossfield_coef * total_align_loss` (:353): its curvature, corner
 and junction terms are computed and reported but never reach the positions.  They are not built here, and `step()` does not report them.
 
-What stays host code of the caller: skeleton initialisation (`skimage` skeletonize plus `skan`, or marching squares; `contours_to_skeleton` below is the
-conversion half of the latter) in front, and the shapely half of `post_process` behind (its corner split is polygonize_post.corner_split_skeleton).
+The marching-squares initialisation in front (`init_method: marching_squares`, get_marching_squares_skeleton :581-638) runs on the device too:
+`init_skeletons` chains p3_init_contours, p3_skeleton_from_contours and p3_asm_plan (csrc/skeleton_init.hip), and `polygonize_device` is seg and crossfield
+on the device -> optimised skeleton on the device, with one read-back of a few counts per stage and no host contour.
+`contours_to_skeleton`, `skeletons_to_tensorskeleton` and the host `AsmPlan` stay for callers that already hold host contours or skeletons.
+
+What stays host code of the caller: the `skimage` skeletonize plus `skan` initialisation (`init_method: skeleton`) in front, and the shapely half of
+`post_process` behind (its corner split is polygonize_post.corner_split_skeleton).
 
 `Skeleton`, `Paths`, `TensorSkeleton`, `skeletons_to_tensorskeleton` and `tensorskeleton_to_skeletons` keep the fields of
 torch_lydorn/torchvision/transforms/tensorskeleton.py: pos [N,2] (row, col), degrees [N], path_index [M], path_delim [P+1], batch [N], batch_delim [B+1],
@@ -145,6 +150,33 @@ class AsmPlan:
         return self
 
 
+class AsmDevicePlan:
+    """The plan of p3_asm_optimize built on the device by p3_asm_plan (hip.asm_plan): the six arrays of AsmPlan.FIELDS, equal to the host class entry for
+    entry, and the same four counts; the host has seen the component count and the largest component only."""
+
+    FIELDS = AsmPlan.FIELDS
+
+    def __init__(self, arrays, num_nodes, num_slots):
+        for k in self.FIELDS:
+            setattr(self, k, arrays[k])
+        self.num_nodes, self.num_slots = int(num_nodes), int(num_slots)
+        self.num_comps, self.max_comp = arrays["counts"]
+
+    def to(self, device):
+        for k in self.FIELDS:
+            setattr(self, k, getattr(self, k).to(device))
+        return self
+
+
+def asm_plan_device(tensorskeleton):
+    """The plan of any container with pos / path_index / path_delim on the device (the reference's own TensorSkeleton included), built there: one read-back
+    of (components, largest component, status).  Raises P3Error on a node id outside [0, N).  TensorSkeletonOptimizer takes it as `tensorskeleton.plan`."""
+    if not tensorskeleton.path_index.is_cuda or not tensorskeleton.path_delim.is_cuda:
+        raise hip.P3Error("asm_plan_device: the tensorskeleton must be on the device; AsmPlan builds the plan on the host")
+    N = tensorskeleton.pos.shape[0]
+    return AsmDevicePlan(hip.asm_plan(tensorskeleton.path_index, tensorskeleton.path_delim, N), N, tensorskeleton.path_index.shape[0])
+
+
 def skeletons_to_tensorskeleton(skeletons_batch, device=None):
     """tensorskeleton.py:87-159: B skeletons -> one TensorSkeleton (node ids, path positions and path numbers offset image by image).  The skeletons are
     not modified.  The result carries its AsmPlan."""
@@ -249,7 +281,8 @@ def asm_schedule(iter_num, config=ASM_DEFAULTS):
 
 class TensorSkeletonOptimizer:
     """The reference's class of the same name with the same constructor; `tensorskeleton` is anything with pos / degrees / path_index / path_delim / batch on
-    the device (the reference's own TensorSkeleton included: its plan is then built here, with one read-back of path_index and path_delim).  optimize() runs
+    the device (the reference's own TensorSkeleton included: its plan is then built here on the host, with one read-back of path_index and path_delim, unless
+    its `plan` attribute holds the result of asm_plan_device).  optimize() runs
     step_thresholds[-1] iterations in one kernel launch, reads nothing back and returns the tensorskeleton, whose pos is updated in place.  step(iter_num)
     runs one iteration and returns (loss, losses_dict) - one launch and one read-back per call, meant for inspection, not for speed.  losses_dict holds
     "align", "level" and "length"; the reference's "curvature", "corner" and "junction" entries, which never enter its total_loss, are not produced.
@@ -270,7 +303,9 @@ class TensorSkeletonOptimizer:
         self.batch = tensorskeleton.batch.to(torch.int32).contiguous()
         self.indicator = indicator.contiguous().float()
         self.c0c2 = c0c2.contiguous().float()
-        plan = tensorskeleton.plan if isinstance(tensorskeleton, TensorSkeleton) else None          # only a container built here is trusted to carry its plan
+        plan = getattr(tensorskeleton, "plan", None)
+        if not isinstance(tensorskeleton, TensorSkeleton) and not isinstance(plan, AsmDevicePlan):          # only a container or a plan built here is trusted
+            plan = None
         if plan is None:
             plan = AsmPlan(tensorskeleton.path_index.cpu().numpy(), tensorskeleton.path_delim.cpu().numpy(), N).to(pos.device)
         self.plan = plan
@@ -305,3 +340,37 @@ def optimize_skeletons(seg_batch, crossfield_batch, skeletons_batch, config=ASM_
     tensorskeleton.to(seg_batch.device)
     optimizer = TensorSkeletonOptimizer(config, tensorskeleton, seg_batch[:, 0, :, :], crossfield_batch)
     return [skeleton_to_polylines(sk) for sk in tensorskeleton_to_skeletons(optimizer.optimize())]
+
+
+def init_skeletons(seg_or_indicator, level=0.5, min_area=10):
+    """get_marching_squares_skeleton per image + skeletons_to_tensorskeleton on the device: seg [B, C, H, W] (channel 0 is the indicator, read in place) or
+    indicator [B, H, W] -> a device TensorSkeleton that carries its device-built plan, None when no path is kept.  min_area None keeps every contour.
+    Three stages (contours, skeleton, plan), each with one read-back of its counts; no contour, node or path index reaches the host."""
+    if not seg_or_indicator.is_cuda:
+        raise hip.P3Error("init_skeletons: the map must be a device tensor (there is no CPU path)")
+    B = seg_or_indicator.shape[0]
+    c = hip.init_contours(seg_or_indicator, level)
+    if c["counts"][1] == 0:
+        return None
+    sk = hip.skeleton_from_contours(c["pos"], c["poly_slice"], c["poly_batch"], c["is_endpoint"], B, min_area)
+    if sk["counts"][2] == 0:
+        return None
+    tensorskeleton = TensorSkeleton(pos=sk["pos"], degrees=sk["degrees"], path_index=sk["path_index"], path_delim=sk["path_delim"], batch=sk["batch"],
+                                    batch_delim=sk["batch_delim"], batch_size=B)
+    tensorskeleton.plan = asm_plan_device(tensorskeleton)
+    return tensorskeleton
+
+
+def polygonize_device(seg_batch, crossfield_batch, config=ASM_DEFAULTS):
+    """PolygonizerASM.__call__ (:715-752) with init_method "marching_squares" and without a host skeleton: initial skeletons at config["data_level"] /
+    config["min_area"], the plan and the optimiser, all on the device.  -> the optimised device TensorSkeleton (polygonize_post.corner_split_skeleton or
+    tensorskeleton_to_skeletons take it from there), None when no path is kept.  ASM_DEFAULTS keeps the reference's init_method "skeleton", which is not
+    built: pass {**ASM_DEFAULTS, "init_method": "marching_squares"}."""
+    if config["init_method"] != "marching_squares":
+        raise NotImplementedError(f"init_method = {config['init_method']!r}: only \"marching_squares\" is built on the device; the skimage skeletonize / skan "
+                                  "initialisation (\"skeleton\") is host code of the caller, whose skeletons optimize_skeletons takes")
+    _check_maps("polygonize_device", seg_batch, crossfield_batch)
+    tensorskeleton = init_skeletons(seg_batch, config["data_level"], config["min_area"])
+    if tensorskeleton is None:
+        return None
+    return TensorSkeletonOptimizer(config, tensorskeleton, seg_batch[:, 0, :, :], crossfield_batch).optimize()

@@ -11,7 +11,7 @@ A tolerance list gives a dict keyed "tol_{}", as the reference's shapely_postpro
 import numpy as np
 import torch
 
-from . import hip, polygonize_acm
+from . import hip, polygonize_acm, polygonize_asm
 
 
 def _is_list(tolerance):
@@ -75,15 +75,29 @@ def pieces_to_host(result):
     return out
 
 
+def _empty_pieces(seg_batch, tolerance):
+    dev = seg_batch.device
+    empty = lambda: {"out_pos": torch.zeros((0, 2), dtype=torch.float32, device=dev), "out_src": torch.zeros(0, dtype=torch.int32, device=dev),
+                     "piece_slice": torch.zeros((0, 2), dtype=torch.int64, device=dev), "piece_poly": torch.zeros(0, dtype=torch.int32, device=dev),
+                     "piece_batch": torch.zeros(0, dtype=torch.int32, device=dev), "counts": (0, 0, 0), "batch_size": seg_batch.shape[0]}
+    return {"tol_{}".format(t): empty() for t in tolerance} if _is_list(tolerance) else empty()
+
+
 def polygonize_acm_pieces(seg_batch, crossfield_batch, config=polygonize_acm.ACM_DEFAULTS, tolerance=None):
     """polygonize_acm.polygonize_device followed by the ACM form at config["tolerance"] (or `tolerance`): seg and crossfield on the device -> the pieces on the
     device.  Without any contour: an empty result (None per tolerance is never returned)."""
     tolerance = config["tolerance"] if tolerance is None else tolerance
     tensorpoly = polygonize_acm.polygonize_device(seg_batch, crossfield_batch, config)
     if tensorpoly is None:
-        dev = seg_batch.device
-        empty = lambda: {"out_pos": torch.zeros((0, 2), dtype=torch.float32, device=dev), "out_src": torch.zeros(0, dtype=torch.int32, device=dev),
-                         "piece_slice": torch.zeros((0, 2), dtype=torch.int64, device=dev), "piece_poly": torch.zeros(0, dtype=torch.int32, device=dev),
-                         "piece_batch": torch.zeros(0, dtype=torch.int32, device=dev), "counts": (0, 0, 0), "batch_size": seg_batch.shape[0]}
-        return {"tol_{}".format(t): empty() for t in tolerance} if _is_list(tolerance) else empty()
+        return _empty_pieces(seg_batch, tolerance)
     return corner_split_tensorpoly(tensorpoly, crossfield_batch, tolerance)
+
+
+def polygonize_asm_pieces(seg_batch, crossfield_batch, config, tolerance=None):
+    """The ASM twin: polygonize_asm.polygonize_device (config["init_method"] must be "marching_squares") followed by the ASM form at config["tolerance"] (or
+    `tolerance`).  Without any kept path: the same empty result as polygonize_acm_pieces."""
+    tolerance = config["tolerance"] if tolerance is None else tolerance
+    tensorskeleton = polygonize_asm.polygonize_device(seg_batch, crossfield_batch, config)
+    if tensorskeleton is None:
+        return _empty_pieces(seg_batch, tolerance)
+    return corner_split_skeleton(tensorskeleton, crossfield_batch, tolerance)
