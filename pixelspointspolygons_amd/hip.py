@@ -1031,28 +1031,52 @@ def hisup_junctions(jloc, joff, scale_x=1.0, scale_y=1.0, shape=None):
     return juncs, scores, index, counts
 
 
-def hisup_regions_device(remask, max_regions=1024, shape=None, _guard=0):
+def _outputs(stage, dev, spec, out=None):
+    """the output tensors of a *_device binding -> dict.  spec: (name, shape, dtype) per output, in the order of the C arguments.  out: None, or a dict with
+    the caller's own tensors for any of the names (buffers kept across batches or a graph capture, guard-band views in the tests); the rest is allocated.
+    A given tensor must lie on dev, be contiguous, have exactly that dtype and exactly prod(shape) elements; it is viewed to shape, so [n, 1] stands for [n]."""
+    given, res = dict(out or {}), {}
+    for name, shape, dtype in spec:
+        t = given.pop(name, None)
+        if t is None:
+            res[name] = torch.empty(shape, dtype=dtype, device=dev)
+            continue
+        if t.device != torch.device(dev) or t.dtype != dtype or t.numel() != math.prod(shape) or not t.is_contiguous():
+            raise P3Error(f"{stage}: out['{name}'] must be a contiguous {dtype} tensor of {math.prod(shape)} elements on {dev}, got {t.dtype} "
+                          f"{tuple(t.shape)} with strides {t.stride()} on {t.device}")
+        res[name] = t.view(shape)
+    if given:
+        raise P3Error(f"{stage}: out has no {sorted(given)}; its outputs are {[name for name, _, _ in spec]}")
+    return res
+
+
+def _read_back(out, who, errors, narrow):
+    """the one device-to-host copy of a checking form: counts and status together.  errors: (status bits, message or function of the counts -> message) in the
+    order they are looked at, the first set one raises; narrow: output name -> the index of the count it is cut to.  counts becomes the tuple of ints."""
+    *counts, status = torch.cat([out["counts"], out["status"]]).tolist()
+    for bits, msg in errors:
+        if status & bits:
+            raise P3Error(f"{who}: {msg(*counts) if callable(msg) else msg}")
+    for k, i in narrow.items():
+        out[k] = out[k][:counts[i]]
+    out["counts"] = tuple(counts)
+    return out
+
+
+def hisup_regions_device(remask, max_regions=1024, shape=None, out=None):
     """p3_hisup_regions without any synchronisation: -> dict(mask f32 [B,H,W], labels i32 [B,H,W], n_regions i32 [B], area i32 [B,R],
-    bbox i32 [B,R,4] = (min_row, min_col, max_row + 1, max_col + 1), score f32 [B,R], status i32 [B] = 1 where n_regions > R = max_regions)."""
+    bbox i32 [B,R,4] = (min_row, min_col, max_row + 1, max_col + 1), score f32 [B,R], status i32 [B] = 1 where n_regions > R = max_regions).
+    out: the caller's own tensors for any of these (`_outputs`)."""
     rm, B, H, W, st = _logit_map(remask, 2, shape, "hisup_regions(remask)")
     R = int(max_regions)
     if R < 1:
         raise P3Error(f"hisup_regions: max_regions = {max_regions}")
-    dev = rm.device
-    g = int(_guard)                 # test hook: the three statistics arrays are carved out of one buffer with g guard words around each
-    arena = torch.full((B * R * 6 + 4 * g,), -559038737, dtype=torch.int32, device=dev) if g else torch.empty(B * R * 6, dtype=torch.int32, device=dev)
-    area = arena[g:g + B * R].view(B, R)
-    bbox = arena[2 * g + B * R:2 * g + B * R * 5].view(B, R, 4)
-    score = arena[3 * g + B * R * 5:3 * g + B * R * 6].view(torch.float32).view(B, R)
-    out = dict(mask=torch.empty((B, H, W), dtype=torch.float32, device=dev), labels=torch.empty((B, H, W), dtype=torch.int32, device=dev),
-               n_regions=torch.empty(B, dtype=torch.int32, device=dev), area=area, bbox=bbox, score=score,
-               status=torch.empty(B, dtype=torch.int32, device=dev))
-    if g:
-        out["_arena"] = arena
+    dev, f32, i32 = rm.device, torch.float32, torch.int32
+    out = _outputs("hisup_regions", dev, (("mask", (B, H, W), f32), ("labels", (B, H, W), i32), ("n_regions", (B,), i32), ("area", (B, R), i32),
+                                          ("bbox", (B, R, 4), i32), ("score", (B, R), f32), ("status", (B,), i32)), out)
     ws = workspace(int(lib().p3_hisup_regions_workspace_bytes(B, H, W, R)), dev, "hisup_regions")
-    check(lib().p3_hisup_regions(ptr(rm), st[0], st[1], st[2], B, H, W, R, ptr(out["mask"]),
-                                 ptr(out["labels"]), ptr(out["n_regions"]), ptr(area), ptr(bbox), ptr(score), ptr(out["status"]), ptr(ws), stream()),
-          "p3_hisup_regions")
+    check(lib().p3_hisup_regions(ptr(rm), st[0], st[1], st[2], B, H, W, R, ptr(out["mask"]), ptr(out["labels"]), ptr(out["n_regions"]), ptr(out["area"]),
+                                 ptr(out["bbox"]), ptr(out["score"]), ptr(out["status"]), ptr(ws), stream()), "p3_hisup_regions")
     return out
 
 
@@ -1152,7 +1176,7 @@ def hisup_polygons_capacity(B, H, W, max_regions):
     return B * (2 * (H * (W + 1) + W * (H + 1)) + 9 * min(max_regions, ((H + 1) // 2) * ((W + 1) // 2)))
 
 
-def hisup_polygons_device(labels, n_regions, bbox, juncs, junc_counts, max_vertices=None, force_fallback=False, _guard=0):
+def hisup_polygons_device(labels, n_regions, bbox, juncs, junc_counts, max_vertices=None, force_fallback=False, out=None):
     """p3_hisup_polygons (models/hisup/polygon.py `get_poly_crowdai`, outer polygons only) without any synchronisation.
     labels i32 [B,H,W], n_regions i32 [B], bbox i32 [B,R,4] as hisup_regions_device returns them, juncs f32 [B,600,2], junc_counts i32 [B,2] as
     hisup_junctions returns them.  -> dict(pos f32 [max_vertices,2] (x, y), src i32 [max_vertices] (ring or junction index), poly_slice i64 [B,R,2],
@@ -1160,7 +1184,7 @@ def hisup_polygons_device(labels, n_regions, bbox, juncs, junc_counts, max_verti
     n_vertices i32 [B], counts i32 [2] = (vertices, longest polygon), status i32 [1] (bit 0: max_vertices was too small; the counts are the true totals
     then, pos / src are not written)).  The default max_vertices cannot overflow but is large: 12 bytes of output and 12 of workspace per vertex, about
     2 x 41 MB at B = 16, 224 x 224, where real outputs have a few thousand vertices; a caller that holds many batches passes its own max_vertices and
-    checks status.  _guard: test hook, guard bytes around every output (out["_arenas"])."""
+    checks status.  out: the caller's own tensors for any of the outputs (`_outputs`); they have to fit max_vertices, they do not define it."""
     if labels.dim() != 3 or labels.dtype != torch.int32 or min(labels.shape) < 1:
         raise P3Error(f"hisup_polygons: labels int32 [B, H, W] expected, got {labels.dtype} {tuple(labels.shape)}")
     B, H, W = labels.shape
@@ -1178,13 +1202,9 @@ def hisup_polygons_device(labels, n_regions, bbox, juncs, junc_counts, max_verti
         raise P3Error(f"hisup_polygons: max_vertices = {nv}")
     for t in (labels, n_regions, bbox, juncs, junc_counts):
         _dev(t)
-    dev, arenas, g = labels.device, [], int(_guard)
-    out = dict(pos=_ic_out((nv, 2), torch.float32, dev, g, arenas), src=_ic_out((nv,), torch.int32, dev, g, arenas),
-               poly_slice=_ic_out((B, R, 2), torch.int64, dev, g, arenas), poly_flags=_ic_out((B, R), torch.int32, dev, g, arenas),
-               hole_pixels=_ic_out((B, R), torch.int32, dev, g, arenas), n_vertices=_ic_out((B,), torch.int32, dev, g, arenas),
-               counts=_ic_out((2,), torch.int32, dev, g, arenas), status=_ic_out((1,), torch.int32, dev, g, arenas))
-    if g:
-        out["_arenas"] = arenas
+    dev, i32 = labels.device, torch.int32
+    out = _outputs("hisup_polygons", dev, (("pos", (nv, 2), torch.float32), ("src", (nv,), i32), ("poly_slice", (B, R, 2), torch.int64), ("poly_flags", (B, R), i32),
+                                           ("hole_pixels", (B, R), i32), ("n_vertices", (B,), i32), ("counts", (2,), i32), ("status", (1,), i32)), out)
     lab, nr, bb, jc, cn = labels.contiguous(), n_regions.contiguous(), bbox.contiguous(), juncs.contiguous(), junc_counts.contiguous()
     ws = workspace(int(lib().p3_hisup_polygons_workspace_bytes(B, H, W, R, nv)), dev, "hisup_polygons")
     check(lib().p3_hisup_polygons(ptr(lab), ptr(nr), ptr(bb), ptr(jc), ptr(cn), B, H, W, R, nv, int(bool(force_fallback)),
@@ -1201,15 +1221,9 @@ def hisup_polygons(labels, n_regions, bbox, juncs, junc_counts, max_vertices=Non
 
 def hisup_polygons_checked(out, who="hisup_polygons"):
     """the one read-back of counts and status of a hisup_polygons_device result: raises on any status bit, narrows pos / src, counts as Python ints"""
-    V, longest, status = torch.cat([out["counts"], out["status"]]).tolist()
-    if status & 1:
-        raise P3Error(f"{who}: {V} vertices do not fit max_vertices = {out['pos'].shape[0]}")
-    if status & 4:
-        raise P3Error(f"{who}: P3_HISUP_POLY_STOP is set: the run was cut short for a measurement and has no result")
-    if status & 2:
-        raise P3Error(f"{who}: a region's ring is longer than the bound the workspace is sized for (include/p3hip.h)")
-    out["pos"], out["src"], out["counts"] = out["pos"][:V], out["src"][:V], (V, longest)
-    return out
+    return _read_back(out, who, ((1, lambda V, _: f"{V} vertices do not fit max_vertices = {out['pos'].shape[0]}"),
+                                 (4, "P3_HISUP_POLY_STOP is set: the run was cut short for a measurement and has no result"),
+                                 (2, "a region's ring is longer than the bound the workspace is sized for (include/p3hip.h)")), dict(pos=0, src=0))
 
 
 # ------------------------------------------------------------------------------------------ FFL active-contour polygon optimiser
@@ -1260,29 +1274,13 @@ def acm_optimize(pos, poly_slice, batch, is_endpoint, indicator, c0c2, data_coef
 
 
 # ------------------------------------------------------------------------------------------ FFL initial contours (marching squares)
-_IC_GUARD_BYTE = 0xA5
-
-
-def _ic_out(shape, dtype, dev, g, arenas):
-    """an output of init_contours_device; with g > 0 it sits between two runs of 16 * g guard bytes inside an arena of its own (kept in `arenas`)"""
-    if not g:
-        return torch.empty(shape, dtype=dtype, device=dev)
-    n = 1
-    for s in shape:
-        n *= s
-    nbytes = n * torch.empty((), dtype=dtype).element_size()
-    arena = torch.full((nbytes + 32 * g,), _IC_GUARD_BYTE, dtype=torch.uint8, device=dev)
-    arenas.append((arena, 16 * g, nbytes))
-    return arena[16 * g:16 * g + nbytes].view(dtype).view(shape)
-
-
-def init_contours_device(indicator, level=0.5, max_vertices=None, max_contours=None, _guard=0):
+def init_contours_device(indicator, level=0.5, max_vertices=None, max_contours=None, out=None):
     """p3_init_contours (predict/ffl/polygonize_utils.py:15-44: find_contours(indicator, level, fully_connected='low', positive_orientation='high') per image)
     without any synchronisation.  indicator fp32 [B,H,W] with any strides (seg[:, 0] is not copied), or [B,C,H,W] (channel 0 is taken).
     -> dict(pos f32 [max_vertices,2] (row, col), poly_slice i64 [max_contours,2], poly_batch i32 [max_contours], batch i64 [max_vertices], is_endpoint u8
     [max_vertices], counts i32 [3] = (N, P, longest contour), n_contours i32 [B], n_vertices i32 [B], status i32 [1] = 1 when N > max_vertices or P > max_contours;
     counts are the true totals then, and nothing is written past the capacities).  The default capacities B (H (W-1) + (H-1) W) and half of that cannot overflow.
-    _guard: test hook, guard bytes around every output (out["_arenas"] = [(arena, guard bytes, payload bytes)])."""
+    out: the caller's own tensors for any of the outputs (`_outputs`); they have to fit the capacities, they do not define them."""
     _dev(indicator)
     if indicator.dim() == 4:
         indicator = indicator[:, 0]
@@ -1296,14 +1294,10 @@ def init_contours_device(indicator, level=0.5, max_vertices=None, max_contours=N
     nc = max(bound // 2, 1) if max_contours is None else int(max_contours)
     if nv < 1 or nc < 1:
         raise P3Error(f"init_contours: max_vertices = {max_vertices}, max_contours = {max_contours}")
-    dev, arenas, g = indicator.device, [], int(_guard)
-    out = dict(pos=_ic_out((nv, 2), torch.float32, dev, g, arenas), poly_slice=_ic_out((nc, 2), torch.int64, dev, g, arenas),
-               poly_batch=_ic_out((nc,), torch.int32, dev, g, arenas), batch=_ic_out((nv,), torch.int64, dev, g, arenas),
-               is_endpoint=_ic_out((nv,), torch.uint8, dev, g, arenas), counts=_ic_out((3,), torch.int32, dev, g, arenas),
-               n_contours=_ic_out((B,), torch.int32, dev, g, arenas), n_vertices=_ic_out((B,), torch.int32, dev, g, arenas),
-               status=_ic_out((1,), torch.int32, dev, g, arenas))
-    if g:
-        out["_arenas"] = arenas
+    dev, i32, i64 = indicator.device, torch.int32, torch.int64
+    out = _outputs("init_contours", dev, (("pos", (nv, 2), torch.float32), ("poly_slice", (nc, 2), i64), ("poly_batch", (nc,), i32), ("batch", (nv,), i64),
+                                          ("is_endpoint", (nv,), torch.uint8), ("counts", (3,), i32), ("n_contours", (B,), i32), ("n_vertices", (B,), i32),
+                                          ("status", (1,), i32)), out)
     ws = workspace(int(lib().p3_init_contours_workspace_bytes(B, H, W)), dev, "init_contours")
     sb, sr, sc = indicator.stride()
     check(lib().p3_init_contours(ptr(indicator), sb, sr, sc, B, H, W, float(level), nv,
@@ -1316,15 +1310,8 @@ def init_contours(indicator, level=0.5, max_vertices=None, max_contours=None):
     """the checking form of init_contours_device: reads counts and status once (the only read-back), raises when a capacity was too small and narrows every
     array to what was found: pos [N,2], poly_slice [P,2], poly_batch [P], batch [N], is_endpoint [N]; counts = (N, P, longest) as Python ints."""
     out = init_contours_device(indicator, level, max_vertices, max_contours)
-    N, P, longest, status = torch.cat([out["counts"], out["status"]]).tolist()
-    if status:
-        raise P3Error(f"init_contours: {N} vertices in {P} contours do not fit max_vertices = {out['pos'].shape[0]}, max_contours = {out['poly_slice'].shape[0]}")
-    for k in ("pos", "batch", "is_endpoint"):
-        out[k] = out[k][:N]
-    for k in ("poly_slice", "poly_batch"):
-        out[k] = out[k][:P]
-    out["counts"] = (N, P, longest)
-    return out
+    fit = lambda N, P, _: f"{N} vertices in {P} contours do not fit max_vertices = {out['pos'].shape[0]}, max_contours = {out['poly_slice'].shape[0]}"
+    return _read_back(out, "init_contours", ((-1, fit),), dict(pos=0, batch=0, is_endpoint=0, poly_slice=1, poly_batch=1))          # -1: any status bit
 
 
 # ------------------------------------------------------------------------------------------ FFL corner-aware contour simplification
@@ -1332,7 +1319,7 @@ CS_LDS_CAP = 4096          # csrc/corner_split.hip: explicit points of one polyl
 
 
 def corner_split_device(pos, index, poly_slice, closed, poly_batch, c0c2, tol_pre, tol, max_len=None, force_fallback=False, max_vertices=None,
-                        max_pieces=None, stage_flags=False, _guard=0):
+                        max_pieces=None, stage_flags=False, out=None):
     """p3_corner_split (the array half of FFL's post_process: approximate_polygon, detect_corners, split_polylines_corner, simplify per piece; DESIGN.md
     section 14) without any synchronisation.  pos fp32 [N,2] (row, col); index int64 [K] or None; poly_slice [P,2] into index (into pos without index);
     closed [P] (the first point is appended once more); poly_batch [P] the image of each polyline; c0c2 [B,4,H,W].  tol_pre: stage A (ACM: min(1,
@@ -1340,7 +1327,7 @@ def corner_split_device(pos, index, poly_slice, closed, poly_batch, c0c2, tol_pr
     -> dict(out_pos f32 [max_vertices,2], out_src i32 [max_vertices], piece_slice i64 [max_pieces,2], piece_poly i32 [max_pieces], piece_batch i32
     [max_pieces], counts i32 [3] = (vertices, pieces, longest piece), status i32 [1] (bit 0: a capacity was too small; counts are the true totals then and
     nothing is written past the capacities), stage_flags u8 [(K or N) + P] with stage_flags=True).  The default capacities 2 E and E for E = (K or N) + P
-    explicit points cannot overflow.  _guard: test hook, guard bytes around every output (out["_arenas"])."""
+    explicit points cannot overflow.  out: the caller's own tensors for any of the outputs (`_outputs`); they have to fit the capacities."""
     for t in (pos, poly_slice, closed, poly_batch, c0c2) + (() if index is None else (index,)):
         _dev(t)
     if pos.dtype != torch.float32 or pos.dim() != 2 or pos.shape[1] != 2:
@@ -1358,15 +1345,10 @@ def corner_split_device(pos, index, poly_slice, closed, poly_batch, c0c2, tol_pr
     nq = max(E, 1) if max_pieces is None else int(max_pieces)
     if nv < 1 or nq < 1:
         raise P3Error(f"corner_split: max_vertices = {max_vertices}, max_pieces = {max_pieces}")
-    dev, arenas, g = pos.device, [], int(_guard)
-    out = dict(out_pos=_ic_out((nv, 2), torch.float32, dev, g, arenas), out_src=_ic_out((nv,), torch.int32, dev, g, arenas),
-               piece_slice=_ic_out((nq, 2), torch.int64, dev, g, arenas), piece_poly=_ic_out((nq,), torch.int32, dev, g, arenas),
-               piece_batch=_ic_out((nq,), torch.int32, dev, g, arenas), counts=_ic_out((3,), torch.int32, dev, g, arenas),
-               status=_ic_out((1,), torch.int32, dev, g, arenas))
-    if stage_flags:
-        out["stage_flags"] = _ic_out((max(E, 1),), torch.uint8, dev, g, arenas)
-    if g:
-        out["_arenas"] = arenas
+    dev, i32 = pos.device, torch.int32
+    flags = (("stage_flags", (max(E, 1),), torch.uint8),) if stage_flags else ()
+    out = _outputs("corner_split", dev, (("out_pos", (nv, 2), torch.float32), ("out_src", (nv,), i32), ("piece_slice", (nq, 2), torch.int64), ("piece_poly", (nq,), i32),
+                                         ("piece_batch", (nq,), i32)) + flags + (("counts", (3,), i32), ("status", (1,), i32)), out)
     # converted copies stay referenced until the launch is queued
     p32, cf = pos.contiguous(), c0c2.contiguous().float()
     idx = None if index is None else index.to(torch.int64).contiguous()
@@ -1385,17 +1367,9 @@ def corner_split(pos, index, poly_slice, closed, poly_batch, c0c2, tol_pre, tol,
     """the checking form of corner_split_device: reads counts and status once (the only read-back), raises when a capacity was too small and narrows the
     outputs to what was found: out_pos [V,2], out_src [V], piece_slice [Q,2], piece_poly [Q], piece_batch [Q]; counts = (V, Q, longest piece) as ints."""
     out = corner_split_device(pos, index, poly_slice, closed, poly_batch, c0c2, tol_pre, tol, max_len, force_fallback, max_vertices, max_pieces, stage_flags)
-    V, Q, longest, status = torch.cat([out["counts"], out["status"]]).tolist()
-    if status & 1:
-        raise P3Error(f"corner_split: {V} vertices in {Q} pieces do not fit max_vertices = {out['out_pos'].shape[0]}, max_pieces = {out['piece_slice'].shape[0]}")
-    if status & 2:
-        raise P3Error("corner_split: the rows of poly_slice overlap: they hold more explicit points than index / pos has entries")
-    for k in ("out_pos", "out_src"):
-        out[k] = out[k][:V]
-    for k in ("piece_slice", "piece_poly", "piece_batch"):
-        out[k] = out[k][:Q]
-    out["counts"] = (V, Q, longest)
-    return out
+    fit = lambda V, Q, _: f"{V} vertices in {Q} pieces do not fit max_vertices = {out['out_pos'].shape[0]}, max_pieces = {out['piece_slice'].shape[0]}"
+    return _read_back(out, "corner_split", ((1, fit), (2, "the rows of poly_slice overlap: they hold more explicit points than index / pos has entries")),
+                      dict(out_pos=0, out_src=0, piece_slice=1, piece_poly=1, piece_batch=1))
 
 
 # ------------------------------------------------------------------------------------------ FFL active-skeleton optimiser
@@ -1459,13 +1433,13 @@ def asm_optimize(pos, sq, plan, is_tip, batch, indicator, c0c2, knots, data_leve
 
 # ------------------------------------------------------------------------------------------ FFL active-skeleton initialisation (marching squares) and plan
 def skeleton_from_contours_device(pos, poly_slice, poly_batch, is_endpoint, batch_size, min_area=None, max_nodes=None, max_slots=None, max_paths=None,
-                                  _guard=0):
+                                  out=None):
     """p3_skeleton_from_contours (the conversion half of get_marching_squares_skeleton, predict/ffl/polygonize_asm.py:581-638, plus
     skeletons_to_tensorskeleton) without any synchronisation.  The contour container as init_contours leaves it: pos fp32 [N,2], poly_slice [P,2],
     poly_batch [P], is_endpoint [N].  min_area None keeps every contour, a number keeps those with at least 3 vertices and a larger shoelace area.
     -> dict(pos f32 [max_nodes,2], degrees i64 [max_nodes], path_index i64 [max_slots], path_delim i64 [max_paths+1], batch i64 [max_nodes], batch_delim i64
     [B+1], counts i32 [4] = (nodes, slots, paths, nodes of the longest kept path), status i32 [1] (bit 0: a capacity was too small; counts are the true totals
-    then and nothing is written past the capacities)).  The default capacities N, N + P and P cannot overflow.  _guard: test hook, as init_contours_device."""
+    then and nothing is written past the capacities)).  The default capacities N, N + P and P cannot overflow.  out: the caller's own tensors for any of the outputs (`_outputs`)."""
     for t in (pos, poly_slice, poly_batch, is_endpoint):
         _dev(t)
     if pos.dtype != torch.float32 or pos.dim() != 2 or pos.shape[1] != 2:
@@ -1479,13 +1453,9 @@ def skeleton_from_contours_device(pos, poly_slice, poly_batch, is_endpoint, batc
     npth = max(P, 1) if max_paths is None else int(max_paths)
     if nn < 1 or ns < 1 or npth < 1:
         raise P3Error(f"skeleton_from_contours: max_nodes = {max_nodes}, max_slots = {max_slots}, max_paths = {max_paths}")
-    dev, arenas, g = pos.device, [], int(_guard)
-    out = dict(pos=_ic_out((nn, 2), torch.float32, dev, g, arenas), degrees=_ic_out((nn,), torch.int64, dev, g, arenas),
-               path_index=_ic_out((ns,), torch.int64, dev, g, arenas), path_delim=_ic_out((npth + 1,), torch.int64, dev, g, arenas),
-               batch=_ic_out((nn,), torch.int64, dev, g, arenas), batch_delim=_ic_out((B + 1,), torch.int64, dev, g, arenas),
-               counts=_ic_out((4,), torch.int32, dev, g, arenas), status=_ic_out((1,), torch.int32, dev, g, arenas))
-    if g:
-        out["_arenas"] = arenas
+    dev, i32, i64 = pos.device, torch.int32, torch.int64
+    out = _outputs("skeleton_from_contours", dev, (("pos", (nn, 2), torch.float32), ("degrees", (nn,), i64), ("path_index", (ns,), i64), ("path_delim", (npth + 1,), i64),
+                                                   ("batch", (nn,), i64), ("batch_delim", (B + 1,), i64), ("counts", (4,), i32), ("status", (1,), i32)), out)
     # converted copies stay referenced until the launch is queued
     p32, sl = pos.contiguous(), poly_slice.to(torch.int64).contiguous()
     pb, ep = poly_batch.to(torch.int32).contiguous(), is_endpoint.to(torch.uint8).contiguous()
@@ -1501,37 +1471,26 @@ def skeleton_from_contours(pos, poly_slice, poly_batch, is_endpoint, batch_size,
     """the checking form of skeleton_from_contours_device: reads counts and status once (the only read-back), raises when a capacity was too small and
     narrows the arrays: pos [N',2], degrees [N'], path_index [M'], path_delim [P'+1] ([0] without a path), batch [N']; counts = (N', M', P', longest)."""
     out = skeleton_from_contours_device(pos, poly_slice, poly_batch, is_endpoint, batch_size, min_area, max_nodes, max_slots, max_paths)
-    N, M, P, longest, status = torch.cat([out["counts"], out["status"]]).tolist()
-    if status & 1:
-        raise P3Error(f"skeleton_from_contours: {N} nodes, {M} slots and {P} paths do not fit max_nodes = {out['pos'].shape[0]}, max_slots = "
-                      f"{out['path_index'].shape[0]}, max_paths = {out['path_delim'].shape[0] - 1}")
-    for k in ("pos", "degrees", "batch"):
-        out[k] = out[k][:N]
-    out["path_index"] = out["path_index"][:M]
+    fit = lambda N, M, P, _: (f"{N} nodes, {M} slots and {P} paths do not fit max_nodes = {out['pos'].shape[0]}, max_slots = {out['path_index'].shape[0]}, "
+                              f"max_paths = {out['path_delim'].shape[0] - 1}")
+    P = _read_back(out, "skeleton_from_contours", ((1, fit),), dict(pos=0, degrees=0, batch=0, path_index=1))["counts"][2]
     out["path_delim"] = out["path_delim"][:P + 1] if P else torch.zeros(1, dtype=torch.int64, device=pos.device)          # nothing was written without a path
-    out["counts"] = (N, M, P, longest)
     return out
 
 
-ASM_PLAN_FIELDS = ("comp_ptr", "cn_node", "cn_occ", "slot_nb", "node_local", "slot_k")
-
-
-def asm_plan_device(path_index, path_delim, num_nodes, _guard=0):
+def asm_plan_device(path_index, path_delim, num_nodes, out=None):
     """p3_asm_plan without any synchronisation: path_index [M], path_delim [paths + 1] and the node count -> dict of the six int32 arrays of
     polygonize_asm.AsmPlan at their largest sizes (comp_ptr [N+1] with C + 1 entries used, cn_node [N], cn_occ [N+1], slot_nb [M,2], node_local [N], slot_k
-    [M]), counts i32 [2] = (C, nodes of the largest component) and status i32 [1] (bit 1: a node id outside [0, N); the arrays are no plan then)."""
+    [M]), counts i32 [2] = (C, nodes of the largest component) and status i32 [1] (bit 1: a node id outside [0, N); the arrays are no plan then).
+    out: the caller's own tensors for any of the outputs (`_outputs`)."""
     for t in (path_index, path_delim):
         _dev(t)
     if path_index.dim() != 1 or path_delim.dim() != 1 or int(num_nodes) < 0:
         raise P3Error(f"asm_plan: path_index [M], path_delim [P+1] and num_nodes >= 0 expected, got {tuple(path_index.shape)}, {tuple(path_delim.shape)}, {num_nodes}")
     N, M, D = int(num_nodes), path_index.shape[0], path_delim.shape[0]
-    dev, arenas, g = path_index.device, [], int(_guard)
-    out = dict(comp_ptr=_ic_out((N + 1,), torch.int32, dev, g, arenas), cn_node=_ic_out((N,), torch.int32, dev, g, arenas),
-               cn_occ=_ic_out((N + 1,), torch.int32, dev, g, arenas), slot_nb=_ic_out((M, 2), torch.int32, dev, g, arenas),
-               node_local=_ic_out((N,), torch.int32, dev, g, arenas), slot_k=_ic_out((M,), torch.int32, dev, g, arenas),
-               counts=_ic_out((2,), torch.int32, dev, g, arenas), status=_ic_out((1,), torch.int32, dev, g, arenas))
-    if g:
-        out["_arenas"] = arenas
+    dev, i32 = path_index.device, torch.int32
+    out = _outputs("asm_plan", dev, (("comp_ptr", (N + 1,), i32), ("cn_node", (N,), i32), ("cn_occ", (N + 1,), i32), ("slot_nb", (M, 2), i32), ("node_local", (N,), i32),
+                                     ("slot_k", (M,), i32), ("counts", (2,), i32), ("status", (1,), i32)), out)
     idx, delim = path_index.to(torch.int64).contiguous(), path_delim.to(torch.int64).contiguous()
     ws = workspace(int(lib().p3_asm_plan_workspace_bytes(N, M)), dev, "asm_plan") if N else None
     check(lib().p3_asm_plan(ptr(idx), M, ptr(delim), D, N, ptr(out["comp_ptr"]), ptr(out["cn_node"]), ptr(out["cn_occ"]), ptr(out["slot_nb"]),
@@ -1543,11 +1502,8 @@ def asm_plan(path_index, path_delim, num_nodes):
     """the checking form of asm_plan_device: reads counts and status once (the only read-back), raises on a node id outside [0, N), narrows comp_ptr to
     [C+1]; counts = (C, max_comp) as Python ints."""
     out = asm_plan_device(path_index, path_delim, num_nodes)
-    C, max_comp, status = torch.cat([out["counts"], out["status"]]).tolist()
-    if status & 2:
-        raise P3Error(f"asm_plan: path_index holds node ids outside [0, {int(num_nodes)})")
+    C = _read_back(out, "asm_plan", ((2, f"path_index holds node ids outside [0, {int(num_nodes)})"),), {})["counts"][0]
     out["comp_ptr"] = out["comp_ptr"][:C + 1]
-    out["counts"] = (C, max_comp)
     return out
 
 

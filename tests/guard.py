@@ -11,9 +11,10 @@ import torch
 
 BAND_ROWS = 128                      # a stray store of a whole 128-row tile still lands inside the allocation
 ALIGN = 16                           # bytes: the view's base address
-SENTINEL = {2: 0x7FE5, 4: 0x7FE5C3A7, 8: 0x7FE5C3A75AD2B4E1}          # by element size; 2 / 4: quiet NaNs of bfloat16 / float32
+SENTINEL = {1: 0xA5, 2: 0x7FE5, 4: 0x7FE5C3A7, 8: 0x7FE5C3A75AD2B4E1}          # by element size; 2 / 4: quiet NaNs of bfloat16 / float32
+#                                      1: the uint8 outputs hold 0 or 1 (is_endpoint) or flag bits 0..2 (stage_flags), never 0xA5
 POISON = {2: 0x7FD3, 4: 0x7FD3A1B7}           # inputs: quiet NaNs too, but not the sentinel's bits (nor its bf16 rounding)
-_INT = {2: torch.int16, 4: torch.int32, 8: torch.int64}
+_INT = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
 
 
 def _backing(n_elems, es, device, pattern=SENTINEL):
@@ -84,6 +85,25 @@ def guarded(rows, cols, dtype, ld=None, device="cpu", fill=None):
         else:
             view.fill_(fill)
     return view, Guard(bits, view, off, rows, cols, ld, is_output=fill is None)
+
+
+def guarded_set(spec, device):
+    """spec: name -> (rows, cols, dtype).  -> (name -> view, name -> Guard): the out= dict of a binding that takes the caller's outputs, and its guards"""
+    pairs = {k: guarded(rows, cols, dtype, device=device) for k, (rows, cols, dtype) in spec.items()}
+    return {k: p[0] for k, p in pairs.items()}, {k: p[1] for k, p in pairs.items()}
+
+
+def guarded_run(fn, unwritten=(), untouched=()):
+    """fn(out=None) -> dict of output tensors, a *_device binding.  One run for the shapes, a second one with every output a guarded view of that dtype and
+    size, then every guard is checked: written, but for the names in `unwritten` (may keep sentinels; True / False: all / none of them) and `untouched` (must keep them all).
+    -> the second dict"""
+    first = fn()
+    views, guards = guarded_set({k: (t.shape[0], t[0].numel(), t.dtype) for k, t in first.items()}, next(iter(first.values())).device)
+    out = fn(out=views)
+    assert sorted(out) == sorted(views) and all(out[k].data_ptr() == views[k].data_ptr() for k in views)
+    for k, g in guards.items():
+        g.check(valid=torch.zeros(g.rows, g.cols, dtype=torch.bool) if k in untouched else None, written=k not in unwritten if isinstance(unwritten, tuple) else not unwritten)
+    return out
 
 
 def poisoned(t, ld=None, extra_rows=0, front_rows=0, device=None):

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from tests import corner_split_ref as R
+from tests import guard as G
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -176,22 +177,15 @@ def test_overflow_reports_the_true_totals_and_writes_nothing_past_the_capacities
     want = expected("acm", 1.0, 1.0)
     V, Q, longest = want["counts"]
     nv, nq = V // 2, Q // 3
-    out = hip.corner_split_device(dev(pos, torch.float32), None, dev(slices), dev(closed), dev(poly_batch), dev(c0c2), 1.0, 1.0, max_vertices=nv, max_pieces=nq,
-                                  stage_flags=True, _guard=4)
-    assert out["status"].tolist() == [1] and out["counts"].tolist() == [V, Q, longest]
-    for arena, g, nbytes in out["_arenas"]:
-        a = arena.cpu().numpy()
-        assert (a[:g] == hip._IC_GUARD_BYTE).all() and (a[g + nbytes:] == hip._IC_GUARD_BYTE).all()
+    args = (dev(pos, torch.float32), None, dev(slices), dev(closed), dev(poly_batch), dev(c0c2), 1.0, 1.0)
+    # every output between guard bands and written up to its capacity; stage_flags (uint8) only up to the explicit points that exist
+    out = G.guarded_run(lambda **kw: hip.corner_split_device(*args, max_vertices=nv, max_pieces=nq, stage_flags=True, **kw), unwritten=("stage_flags",))
+    assert out["status"].tolist() == [1] and out["counts"].tolist() == [V, Q, longest] and out["stage_flags"].dtype == torch.uint8
     assert out["out_pos"].cpu().numpy().tobytes() == want["out_pos"][:nv].tobytes() and np.array_equal(out["out_src"].cpu().numpy(), want["out_src"][:nv])
     assert np.array_equal(out["piece_slice"].cpu().numpy(), want["piece_slice"][:nq]) and np.array_equal(out["piece_poly"].cpu().numpy(), want["piece_poly"][:nq])
     with pytest.raises(hip.P3Error):
         hip.corner_split(dev(pos, torch.float32), None, dev(slices), dev(closed), dev(poly_batch), dev(c0c2), 1.0, 1.0, max_vertices=nv)
-    full = hip.corner_split_device(dev(pos, torch.float32), None, dev(slices), dev(closed), dev(poly_batch), dev(c0c2), 1.0, 1.0, max_vertices=V, max_pieces=Q,
-                                   _guard=4)
-    assert full["status"].tolist() == [0]
-    for arena, g, nbytes in full["_arenas"]:
-        a = arena.cpu().numpy()
-        assert (a[:g] == hip._IC_GUARD_BYTE).all() and (a[g + nbytes:] == hip._IC_GUARD_BYTE).all()
+    assert G.guarded_run(lambda **kw: hip.corner_split_device(*args, max_vertices=V, max_pieces=Q, **kw))["status"].tolist() == [0]
 
 
 def test_the_containers_the_list_of_tolerances_and_the_host_pieces():

@@ -5,7 +5,7 @@ import torch
 
 from tests.guard import ALIGN, BAND_ROWS, POISON, SENTINEL, guarded, poisoned
 
-DTYPES = [torch.float32, torch.bfloat16, torch.int32, torch.int64]
+DTYPES = [torch.float32, torch.bfloat16, torch.int32, torch.int64, torch.uint8]
 
 
 def _flat(g):

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import guard as G
 from tests import hisup_polygon_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -27,9 +28,7 @@ def inputs(fg, juncs):
 def run(inp, sel=slice(None), **kw):
     t = [torch.from_numpy(np.ascontiguousarray(inp[k][sel])).to(DEV) for k in ("labels", "n_regions", "bbox", "juncs", "counts")]
     out = _hip().hisup_polygons_device(*t, **kw)
-    res = {k: out[k].cpu().numpy() for k in KEYS}
-    res["_arenas"] = out.get("_arenas")
-    return res
+    return {k: out[k].cpu().numpy() for k in KEYS}
 
 
 def expected(inp, sel=slice(None)):
@@ -170,19 +169,15 @@ def test_capacity_one_short_sets_the_status_and_writes_nothing_outside():
     inp = inputs(*R.junction_cases())
     want = expected(inp)
     V, longest = want["counts"]
+    t = [torch.from_numpy(inp[k]).to(DEV) for k in ("labels", "n_regions", "bbox", "juncs", "counts")]
     for nv, status in ((V - 1, 1), (V, 0)):
-        got = run(inp, max_vertices=nv, _guard=4)
-        assert got["status"].tolist() == [status] and got["counts"].tolist() == [V, longest]                  # the true counts either way
+        out = G.guarded_run(lambda **kw: hip.hisup_polygons_device(*t, max_vertices=nv, **kw), untouched=("pos", "src") if status else ())      # documented: pos / src stay untouched
+        got = {k: out[k].cpu().numpy() for k in KEYS}
+        assert len(out) == 8 and got["status"].tolist() == [status] and got["counts"].tolist() == [V, longest]                  # the true counts either way
         assert np.array_equal(got["poly_slice"], want["poly_slice"]) and np.array_equal(got["n_vertices"], want["n_vertices"])
         assert np.array_equal(got["poly_flags"], want["poly_flags"]) and np.array_equal(got["hole_pixels"], want["hole_pixels"])
-        for arena, g, nbytes in got["_arenas"]:
-            a = arena.cpu().numpy()
-            assert (a[:g] == hip._IC_GUARD_BYTE).all() and (a[g + nbytes:] == hip._IC_GUARD_BYTE).all()
         if status == 0:
             same(got, want)
-        else:
-            assert (got["pos"].view(np.uint8) == hip._IC_GUARD_BYTE).all()                                    # documented: pos / src stay untouched
-    t = [torch.from_numpy(inp[k]).to(DEV) for k in ("labels", "n_regions", "bbox", "juncs", "counts")]
     with pytest.raises(hip.P3Error, match="max_vertices"):
         hip.hisup_polygons(*t, max_vertices=V - 1)
     full = hip.hisup_polygons(*t)

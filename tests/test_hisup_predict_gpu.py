@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import guard as G
 from tests import hisup_predict_ref as R
 from tests.helpers import load_golden
 
@@ -221,13 +222,13 @@ def test_regions_more_than_max_regions():
     assert _check_regions(out, 0, logits[0], 4096) == 3094
     with pytest.raises(hip.P3Error, match="max_regions"):
         hip.hisup_regions(x)                                                  # the default 1024
-    dev = hip.hisup_regions_device(x, max_regions=1024, _guard=64)          # the device-only path hands the status back; guard words around the arrays
+    v, guards = G.guarded_set(dict(area=(1, 1024, torch.int32), bbox=(1024, 4, torch.int32), score=(1, 1024, torch.float32)), DEV)
+    dev = hip.hisup_regions_device(x, max_regions=1024, out=v)          # the device-only path hands the status back; guard bands around the statistics
     assert dev["status"].tolist() == [1] and int(dev["n_regions"][0]) == 3094
     assert _check_regions(dev, 0, logits[0], 1024) == 3094                    # labels complete, statistics of the first 1024 regions
-    arena, R_ = dev["_arena"].cpu(), 1024
-    g = 64
-    guards = torch.cat([arena[:g], arena[g + R_:2 * g + R_], arena[2 * g + 5 * R_:3 * g + 5 * R_], arena[3 * g + 6 * R_:]])
-    assert len(guards) == 4 * g and bool((guards == -559038737).all())
+    for k, guard in guards.items():
+        assert dev[k].data_ptr() == v[k].data_ptr()
+        guard.check(written=True)
     two = hip.hisup_regions_device(torch.cat([x, -x.abs() * 0 + torch.tensor([3.0, -3.0], device=DEV).view(1, 2, 1, 1)]), max_regions=1024)
     assert two["status"].tolist() == [1, 0] and two["n_regions"].tolist() == [3094, 0]
 

@@ -379,3 +379,20 @@ def test_weight_planes_rules_of_the_host_side():
         ops.unregister([w])
     with hip.gemm_split(True):
         assert ops.wpl_T_registered(w) is None
+
+
+def test_outputs_helper_allocates_takes_the_callers_tensors_and_refuses_what_does_not_fit():
+    """hip._outputs, the one place where a *_device binding makes its outputs or takes them from out= (no GPU: dev = "cpu")"""
+    from pixelspointspolygons_amd import hip
+    i32 = torch.int32
+    spec = (("pos", (5, 2), torch.float32), ("src", (5,), i32), ("status", (1,), i32))
+    got = hip._outputs("stage", "cpu", spec)
+    assert list(got) == ["pos", "src", "status"] and all(got[n].shape == s and got[n].dtype == d and got[n].device.type == "cpu" for n, s, d in spec)
+    src = torch.zeros(5, 1, dtype=i32)
+    part = hip._outputs("stage", "cpu", spec, dict(src=src))                             # a [n, 1] view stands for [n]; the rest is allocated
+    assert part["src"].data_ptr() == src.data_ptr() and part["src"].shape == (5,) and part["pos"].shape == (5, 2) and part["status"].shape == (1,)
+    for bad in (torch.zeros(5, dtype=torch.int64), torch.zeros(6, dtype=i32), torch.zeros(5, 2, dtype=i32)[:, 0], torch.zeros(5, dtype=i32, device="meta")):
+        with pytest.raises(hip.P3Error, match=r"stage: out\['src'\]"):                   # dtype, element count, strides, device
+            hip._outputs("stage", "cpu", spec, dict(src=bad))
+    with pytest.raises(hip.P3Error, match="stage: out has no .*'scr'"):
+        hip._outputs("stage", "cpu", spec, dict(scr=src))

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import guard as G
 from tests import marching_ref as M
 
 pytestmark = pytest.mark.gpu
@@ -163,20 +164,23 @@ def test_overflow_sets_status_keeps_the_totals_and_writes_nothing_outside(short)
     N, P, longest = full["counts"]
     assert N > 1 and P > 1
     caps = {"max_vertices": N, "max_contours": P}
-    exact = hip.init_contours_device(x, _guard=4, **caps)          # the exact capacities fit
+    run = lambda: G.guarded_run(lambda **kw: hip.init_contours_device(x, **caps, **kw))          # all nine outputs between guard bands, each written up to its capacity
+    exact = run()          # the exact capacities fit
     assert exact["status"].tolist() == [0] and torch.equal(exact["pos"], full["pos"]) and torch.equal(exact["poly_slice"], full["poly_slice"])
     caps[short] -= 1
-    out = hip.init_contours_device(x, _guard=4, **caps)
+    out = run()
     assert out["status"].tolist() == [1] and out["counts"].tolist() == [N, P, longest]
     assert out["n_contours"].tolist() == [P] and out["n_vertices"].tolist() == [N]
-    assert out["pos"].shape[0] == caps["max_vertices"] and out["poly_slice"].shape[0] == caps["max_contours"]
-    for o in (exact, out):
-        assert len(o["_arenas"]) == 9
-        for arena, g, nbytes in o["_arenas"]:
-            assert g == 64 and arena.numel() == nbytes + 2 * g
-            assert bool((arena[:g] == 0xA5).all()) and bool((arena[g + nbytes:] == 0xA5).all())
+    assert out["pos"].shape[0] == caps["max_vertices"] and out["poly_slice"].shape[0] == caps["max_contours"] and len(exact) == len(out) == 9
     with pytest.raises(hip.P3Error):
         hip.init_contours(x, **caps)
+
+
+def test_an_output_of_the_wrong_dtype_is_refused():
+    from pixelspointspolygons_amd import hip
+    x = torch.tensor(M.level_valued()[None]).to(DEV)
+    with pytest.raises(hip.P3Error, match="init_contours.*pos"):          # the default capacity of the 8 x 8 map, 2 * 8 * 7 vertices, in float64
+        hip.init_contours_device(x, out=dict(pos=torch.empty((112, 2), dtype=torch.float64, device=DEV)))
 
 
 def test_two_runs_give_the_same_bits():

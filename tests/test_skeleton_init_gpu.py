@@ -103,29 +103,6 @@ def test_larger_maps_equal_the_oracle_and_two_runs_give_the_same_bits():
         assert torch.equal(getattr(a.plan, k), getattr(b.plan, k)), k
 
 
-def _guarded(spec):
-    views, guards = {}, {}
-    for k, (rows, cols, dtype) in spec.items():
-        views[k], guards[k] = G.guarded(rows, cols, dtype, device=DEV)
-    return views, guards
-
-
-def _skeleton_guarded(c, B, min_area, nn, ns, npth):
-    """the C entry itself, every output a view between guard bands -> (views, guards)"""
-    from pixelspointspolygons_amd import hip
-    from pixelspointspolygons_amd._lib import check, lib
-    i64, i32 = torch.int64, torch.int32
-    v, g = _guarded(dict(pos=(nn, 2, torch.float32), degrees=(nn, 1, i64), path_index=(ns, 1, i64), path_delim=(npth + 1, 1, i64), batch=(nn, 1, i64),
-                         batch_delim=(B + 1, 1, i64), counts=(4, 1, i32), status=(1, 1, i32)))
-    N, P = c["pos"].shape[0], c["poly_slice"].shape[0]
-    ws = hip.workspace(int(lib().p3_skeleton_from_contours_workspace_bytes(P)), c["pos"].device, "skeleton_from_contours")
-    check(lib().p3_skeleton_from_contours(hip.ptr(c["pos"]), N, hip.ptr(c["poly_slice"]), hip.ptr(c["poly_batch"]), hip.ptr(c["is_endpoint"]), P, B, 1, float(min_area),
-                                          nn, ns, npth, *(hip.ptr(v[k]) for k in ("pos", "degrees", "path_index", "path_delim", "batch", "batch_delim", "counts",
-                                                                                   "status")), hip.ptr(ws), hip.stream()), "p3_skeleton_from_contours")
-    torch.cuda.synchronize()
-    return v, g
-
-
 @pytest.mark.parametrize("short", ["exact", "nodes", "slots", "paths"])
 def test_a_capacity_one_short_sets_status_keeps_the_counts_and_the_guards(short):
     from pixelspointspolygons_amd import hip
@@ -137,17 +114,16 @@ def test_a_capacity_one_short_sets_status_keeps_the_counts_and_the_guards(short)
     caps = dict(nodes=N, slots=M, paths=P)
     if short != "exact":
         caps[short] -= 1
-    v, g = _skeleton_guarded(c, 2, S.MIN_AREA, caps["nodes"], caps["slots"], caps["paths"])
-    assert v["counts"][:, 0].tolist() == [N, M, P, longest]
-    assert v["status"].item() == (0 if short == "exact" else 1)
-    for k, guard in g.items():
-        guard.check(written=short == "exact")          # nothing outside the views; with the exact capacities every element was written
+    v = G.guarded_run(lambda **kw: hip.skeleton_from_contours_device(c["pos"], c["poly_slice"], c["poly_batch"], c["is_endpoint"], 2, S.MIN_AREA, caps["nodes"],
+                                                                     caps["slots"], caps["paths"], **kw), unwritten=short != "exact")
+    # nothing outside the views; with the exact capacities every element was written
+    assert len(v) == 8 and v["counts"].tolist() == [N, M, P, longest] and v["status"].item() == (0 if short == "exact" else 1)
     if short == "exact":
         for k in ("degrees", "path_index", "path_delim", "batch", "batch_delim"):
-            assert torch.equal(v[k][:, 0].cpu(), getattr(ref, k)), k
+            assert torch.equal(v[k].cpu(), getattr(ref, k)), k
         assert torch.equal(v["pos"].cpu().view(torch.int32), ref.pos.view(torch.int32))
     else:
-        assert torch.equal(v["batch_delim"][:, 0].cpu(), ref.batch_delim)
+        assert torch.equal(v["batch_delim"].cpu(), ref.batch_delim)
         with pytest.raises(hip.P3Error):
             hip.skeleton_from_contours(c["pos"], c["poly_slice"], c["poly_batch"], c["is_endpoint"], 2, S.MIN_AREA, max_nodes=caps["nodes"], max_slots=caps["slots"],
                                        max_paths=caps["paths"])
@@ -191,20 +167,11 @@ def test_plan_of_degenerate_sizes():
 
 def test_a_node_id_equal_to_n_raises_and_writes_nothing_outside_the_outputs():
     from pixelspointspolygons_amd import hip
-    from pixelspointspolygons_amd._lib import check, lib
     N = 12
     idx = torch.tensor([0, 1, 2, 3, 0, 4, 5, N, 7, 8], dtype=torch.int64, device=DEV)
     delim = torch.tensor([0, 5, 10], dtype=torch.int64, device=DEV)
-    M, i32 = idx.shape[0], torch.int32
-    v, g = _guarded(dict(comp_ptr=(N + 1, 1, i32), cn_node=(N, 1, i32), cn_occ=(N + 1, 1, i32), slot_nb=(M, 2, i32), node_local=(N, 1, i32), slot_k=(M, 1, i32),
-                         counts=(2, 1, i32), status=(1, 1, i32)))
-    ws = hip.workspace(int(lib().p3_asm_plan_workspace_bytes(N, M)), idx.device, "asm_plan")
-    check(lib().p3_asm_plan(hip.ptr(idx), M, hip.ptr(delim), 3, N, *(hip.ptr(v[k]) for k in ("comp_ptr", "cn_node", "cn_occ", "slot_nb", "node_local", "slot_k", "counts",
-                                                                                             "status")), hip.ptr(ws), hip.stream()), "p3_asm_plan")
-    torch.cuda.synchronize()
-    assert v["status"].item() & 2
-    for guard in g.values():
-        guard.check(written=False)
+    v = G.guarded_run(lambda **kw: hip.asm_plan_device(idx, delim, N, **kw), unwritten=True)
+    assert len(v) == 8 and v["status"].item() & 2
     with pytest.raises(hip.P3Error, match="outside"):
         hip.asm_plan(idx, delim, N)
     with pytest.raises(hip.P3Error, match="outside"):
