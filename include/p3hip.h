@@ -209,6 +209,13 @@ typedef struct {
     int tile;             /* 0: the library picks the kernel (measured rule); 1: the 128 x 128 tile kernel, 2: the 128 x 384 tile kernel, 3: the A-stationary kernel -
                            * for THIS call (the host splits a launch with a ragged last round of 128 x 384 tiles into a head on tile 2 and a remainder on tile 1);
                            * the process-wide p3_gemm_x3_tile hook is for measurement tools only and loses against this field */
+    /* 3 x 3 convolution as a GEMM over a zero-bordered planes image (conv_ci > 0; the two tile kernels only, P3_EUNSUP on the A-stationary one and with a fused
+     * LayerNorm): A is the image [conv_B, conv_H + 2, conv_W + 2, lda] (p3_pad_nhwc_planes), K = 9 * conv_ci, W is laid out [N, (ky, kx, ci)].  Output row m is
+     * interior pixel (b, y, x) = unravel(conv_row0 + m) of the UNPADDED [conv_B, conv_H, conv_W] grid, its A row b P_h P_w + (y + 1) P_w + (x + 1) with
+     * P_h = conv_H + 2, P_w = conv_W + 2; the 32-deep slice kt belongs to tap t = kt * 32 / conv_ci and reads A at row + (ky - 1) P_w + (kx - 1), column
+     * kt * 32 - t * conv_ci: an interior row +- one pixel never leaves its own padded image.  conv_ci % 32 == 0.  conv_row0: first output pixel of this launch
+     * (c, residual, ... address ITS row 0) - the second half of a launch the host splits over the two tile kernels. */
+    int conv_B, conv_H, conv_W, conv_ci, conv_row0;
 } p3_gemm_x3_desc;
 int p3_gemm_x3(const p3_gemm_x3_desc* d, void* stream);
 /* measurement hook (tools/mb_x3.py, tools/mb_as.py): 0 = the library's rule, 1 = every product on the 128 x 128 tile, 2 = on the 128 x 384 tile, 3 = on the
@@ -221,6 +228,24 @@ int p3_gemm_x3_as_debug(void* buf);
  * tiles + a fixed-order reduce like p3_gemm_tn_ex); colsum (optional, [N]) += column sums of A (the bias gradient).  M % 64 == 0, N % 128 == 0, K % 128 == 0. */
 int p3_gemm_tn_x3(const void* a_hi, const void* a_lo, int lda, const void* b_hi, const void* b_lo, int ldb, float* C, int ldc, int M, int N, int K,
                   float* colsum, float* slabs, int max_slabs, void* stream);
+/* weight gradient of a 3 x 3 convolution from planes in ONE launch:  C[N, 9 * Ci] (+)= sum_m (a_hi + a_lo)[m, n] (b_hi + b_lo)[m + s_t, c]  for column
+ * t * Ci + c, s_t = (t / 3 - 1) * Pw + (t % 3 - 1).  A: the output gradient in the zero-bordered row space [M, N] (rows outside the interior are zero), B: the
+ * zero-bordered input image [M, Ci] in the same row space; b_hi / b_lo address ITS row 0 and the buffer holds Pw + 1 readable (zero) guard rows in front of it
+ * and behind row M - 1: the shifted rows of the first and last padded image rows are READ (and multiplied by zero).  M % 64 == 0, N % 128 == 0, Ci % 128 == 0;
+ * column tiles never straddle a tap (the 128 x 384 tile needs Ci % 384 == 0).  Splits, slabs, parking and the fixed-order reduce as in p3_gemm_tn_x3. */
+int p3_gemm_tn_x3_conv(const void* a_hi, const void* a_lo, int lda, const void* b_hi, const void* b_lo, int ldb, float* C, int ldc, int M, int N, int Ci, int Pw,
+                       float* slabs, int max_slabs, void* stream);
+/* fp32 [B*H*W, C] (ld_src) -> zero-bordered PLANES image [B, H+2, W+2, C] (hi, lo address padded row 0; ld_dst) for the convolution forms of p3_gemm_x3 /
+ * p3_gemm_tn_x3_conv: border pixels, the `guard` rows in front of row 0 and the rows B (H+2) (W+2) .. rows_total + guard - 1 behind the image are written as
+ * zeros in the same pass.  pre != NULL: the value split is src + a[c] + b[c] * pre[m, c] (ld_pre) - p3_affine_fix_ld's arithmetic, the BatchNorm statistics term
+ * of a gradient, without writing the fp32 gradient back.  The image has Cp >= C columns, columns C .. Cp - 1 zero (a 64-channel gradient as the 128-column operand
+ * of the weight-gradient kernel).  C % 8 == 0, Cp % 8 == 0. */
+int p3_pad_nhwc_planes(const float* src, int ld_src, const float* pre, int ld_pre, const float* a, const float* b, void* hi, void* lo, int ld_dst, int B, int H,
+                       int W, int C, int Cp, int guard, int64_t rows_total, void* stream);
+/* sums[0 .. N) = column sums, sums[N .. 2N) = column sums of squares of fp32 x [M, N] (ld): workgroup partials in `scratch` (scratch_floats >= 2 N; as many
+ * workgroups as fit, at most 1024) added in workgroup order in float64 - the same bits on every run (the BatchNorm batch statistics of a planes GEMM's output).
+ * N % 4 == 0, N <= 1024. */
+int p3_col_stats(const float* x, int ld, int64_t M, int N, float* sums, float* scratch, int64_t scratch_floats, void* stream);
 /* measurement hook: 0 keeps every weight gradient on the 128 x 128 tile (the 128 x 384 tile is the default where K % 384 == 0 and it has >= 8 tiles); returns the previous setting */
 int p3_gemm_tn_x3_wide(int on);
 /* fp32 [rows, cols] (ld_src) -> planes (hi, lo; ld_dst), and back (x = hi + lo): the seams of the planes region (attention outputs, tests) */

@@ -25,7 +25,17 @@ struct TdArgs {
     float* slabs;       // optional [splits][N][K]: partial tiles stored instead of atomics (deterministic mode)
     float* colsum;      // optional [N]: += column sums of A (bias gradient) from the tk == 0 tiles
     float* cs_slab;     // deterministic mode: [splits][N]
+    int conv_ci, conv_pw;   // p3_gemm_tn_x3_conv (conv_ci > 0): column tile -> tap t = column / conv_ci, B rows shifted by (t / 3 - 1) * conv_pw + (t % 3 - 1)
 };
+
+// B side of a column tile that starts at output column c0: plain product - column c0 of B; 3 x 3 convolution - the tile lies inside ONE tap (the host checks
+// conv_ci % tile width == 0): the tap's constant row shift goes onto the scalar base pointer, the column is the channel inside the tap
+__device__ __forceinline__ int td_conv_b(const TdArgs& g, int c0, const bf16_t*& src) {
+    if (g.conv_ci == 0) return c0;
+    const int t = c0 / g.conv_ci;
+    src += (int64_t)((t / 3 - 1) * g.conv_pw + (t % 3 - 1)) * g.ldb;
+    return c0 - t * g.conv_ci;
+}
 
 template <int NBUF>
 __global__ __launch_bounds__(512, 2) void gemm_tn_x3_kernel(TdArgs g) {
@@ -47,7 +57,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_x3_kernel(TdArgs g) {
     const uint32_t lds_addr = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)lds_raw);
     const int img = wave >> 1;
     const bf16_t* src = img == 0 ? g.A : (img == 1 ? g.Al : (img == 2 ? g.B : g.Bl));
-    const int sld = img < 2 ? g.lda : g.ldb, scol = img < 2 ? tn * 128 : tk * 128;
+    const int sld = img < 2 ? g.lda : g.ldb, scol = img < 2 ? tn * 128 : td_conv_b(g, tk * 128, src);
     uint32_t voff[4];
     {
         const int prow = lane >> 4, slot = lane & 15, chunk = slot ^ (prow << 2);
@@ -227,7 +237,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_x3_wide_kernel(TdArgs g) {
     // lane -> (row = lane / 16, slot = lane % 16) of a piece, source chunk = slot ^ ((row & 3) << 2)
     const uint32_t lds_addr = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)lds_raw);
     const bf16_t* src = wave == 0 ? g.A : (wave == 1 ? g.Al : ((wave & 1) ? g.Bl : g.B));
-    const int sld = wave < 2 ? g.lda : g.ldb, scol = wave < 2 ? tn * 128 : tk * 384 + ((wave - 2) >> 1) * 128;
+    const int sld = wave < 2 ? g.lda : g.ldb, scol = wave < 2 ? tn * 128 : td_conv_b(g, tk * 384, src) + ((wave - 2) >> 1) * 128;
     uint32_t voff[4];
     {
         const int prow = lane >> 4, slot = lane & 15, chunk = slot ^ (prow << 2);
@@ -372,8 +382,8 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_x3_wide_kernel(TdArgs g) {
 static int g_tn_wide = 1;
 extern "C" int p3_gemm_tn_x3_wide(int on) { const int was = g_tn_wide; g_tn_wide = on; return was; }
 
-extern "C" int p3_gemm_tn_x3(const void* a_hi, const void* a_lo, int lda, const void* b_hi, const void* b_lo, int ldb, float* C, int ldc, int M, int N, int K,
-                             float* colsum, float* slabs, int max_slabs, void* stream) {
+static int tn_x3_launch(const void* a_hi, const void* a_lo, int lda, const void* b_hi, const void* b_lo, int ldb, float* C, int ldc, int M, int N, int K,
+                        float* colsum, float* slabs, int max_slabs, int conv_ci, int conv_pw, void* stream) {
     P3_CHECK(a_hi && a_lo && b_hi && b_lo && C && M > 0 && N > 0 && K > 0, P3_EINVAL, "p3_gemm_tn_x3: bad arguments");
     P3_CHECK(M % TD_BM == 0 && N % 128 == 0 && K % 128 == 0, P3_ESHAPE, "p3_gemm_tn_x3: M % 32 == 0, N % 128 == 0, K % 128 == 0");
     P3_CHECK(lda % 8 == 0 && ldb % 8 == 0 && ((uintptr_t)a_hi | (uintptr_t)a_lo | (uintptr_t)b_hi | (uintptr_t)b_lo) % 16 == 0, P3_EALIGN, "p3_gemm_tn_x3: 16-byte rows");
@@ -382,12 +392,13 @@ extern "C" int p3_gemm_tn_x3(const void* a_hi, const void* a_lo, int lda, const 
     TdArgs g;
     g.A = (const bf16_t*)a_hi; g.Al = (const bf16_t*)a_lo; g.B = (const bf16_t*)b_hi; g.Bl = (const bf16_t*)b_lo; g.C = C;
     g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.colsum = colsum;
+    g.conv_ci = conv_ci; g.conv_pw = conv_pw;
     const int tiles_n = N / 128;
     // the wide tile (128 x 384, every wave on all rows) where K is a multiple of 384 and there are enough tiles for its split count to stay moderate
     // (p3_gemm_tn_x3_wide(0) switches it off: same-box A/B, tools/mb_x3.py)
     static int env_wide = -1;                        // P3_TN_WIDE=0: same-box A/B of the step (bench.py --lean)
     if (env_wide < 0) { const char* e = getenv("P3_TN_WIDE"); env_wide = (e && atoi(e) == 0) ? 0 : 1; }
-    const bool wide = g_tn_wide && env_wide && K % 384 == 0 && tiles_n * (K / 384) >= 8;
+    const bool wide = g_tn_wide && env_wide && K % 384 == 0 && tiles_n * (K / 384) >= 8 && conv_ci % 384 == 0;       // conv: a column tile lies inside one tap
     g.tiles_k = wide ? K / 384 : K / 128;
     const int step_rows = wide ? TW_BM : TD_BM;
     const int tiles = tiles_n * g.tiles_k;
@@ -416,4 +427,18 @@ extern "C" int p3_gemm_tn_x3(const void* a_hi, const void* a_lo, int lda, const 
     P3_LAUNCH_CHECK();
     if (g.cs_slab && !cs_parked) return p3_det_reduce(g.cs_slab, splits, N, colsum, N, 1, s);
     return P3_OK;
+}
+
+extern "C" int p3_gemm_tn_x3(const void* a_hi, const void* a_lo, int lda, const void* b_hi, const void* b_lo, int ldb, float* C, int ldc, int M, int N, int K,
+                             float* colsum, float* slabs, int max_slabs, void* stream) {
+    return tn_x3_launch(a_hi, a_lo, lda, b_hi, b_lo, ldb, C, ldc, M, N, K, colsum, slabs, max_slabs, 0, 0, stream);
+}
+
+// the nine taps of a 3 x 3 convolution's weight gradient as column tiles of ONE launch (include/p3hip.h): K = 9 * Ci output columns, the B rows of a tile shifted by
+// its tap's constant row offset in the zero-bordered row space.  The caller owns the Pw + 1 zero guard rows in front of and behind B.
+extern "C" int p3_gemm_tn_x3_conv(const void* a_hi, const void* a_lo, int lda, const void* b_hi, const void* b_lo, int ldb, float* C, int ldc, int M, int N, int Ci,
+                                  int Pw, float* slabs, int max_slabs, void* stream) {
+    P3_CHECK(Ci > 0 && Ci % 128 == 0 && Pw >= 3, P3_ESHAPE, "p3_gemm_tn_x3_conv: Ci % 128 == 0, Pw >= 3");
+    P3_CHECK(M % 64 == 0, P3_ESHAPE, "p3_gemm_tn_x3_conv: M % 64 == 0");
+    return tn_x3_launch(a_hi, a_lo, lda, b_hi, b_lo, ldb, C, ldc, M, N, 9 * Ci, nullptr, slabs, max_slabs, Ci, Pw, stream);
 }

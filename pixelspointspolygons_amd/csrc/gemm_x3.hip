@@ -27,6 +27,23 @@ struct X3Args {
     int tiles_m, tiles_n;
 };
 
+// ---- 3 x 3 convolution addressing (p3_gemm_x3_desc.conv_*; CONV = true instantiations of the two tile kernels) ---------------------------------
+// A is a zero-bordered planes image [B, H + 2, W + 2, lda]; output row m is interior pixel (b, y, x) of the unpadded grid.  voffA is computed ONCE from the pixel's
+// own row of the image; a 32-deep slice belongs to one tap (conv_ci % 32 == 0) and moves the scalar A base by the tap's constant row shift
+// ((ky - 1) P_w + (kx - 1)) lda plus the channel inside the tap - an interior pixel +- one pixel stays inside its own padded image, so no row is guarded and no
+// border row is computed.  The W side, the LDS images, the MFMA order and the epilogue are those of the plain product.
+__device__ __forceinline__ int x3_conv_row(const p3_gemm_x3_desc& d, int m) {
+    const int p = m + d.conv_row0, hw = d.conv_H * d.conv_W;
+    const int b = p / hw, r = p - b * hw, y = r / d.conv_W, x = r - y * d.conv_W;
+    return (b * (d.conv_H + 2) + y + 1) * (d.conv_W + 2) + x + 1;
+}
+// tap and channel of the next slice to stage: uniform values, advanced once per slice (no division in the loop)
+struct X3ConvK {
+    int tap = 0, kc = 0;
+    __device__ __forceinline__ int64_t off(const p3_gemm_x3_desc& d) const { return (int64_t)((tap / 3 - 1) * (d.conv_W + 2) + (tap % 3 - 1)) * d.lda + kc; }
+    __device__ __forceinline__ void next(const p3_gemm_x3_desc& d) { kc += 32; if (kc == d.conv_ci) { kc = 0; ++tap; } }
+};
+
 // ---- 128 x 128 tile, 4 waves, 64 KB of LDS -> TWO workgroups per CU ---------------------------------------------------------------------------
 // Same software-pipelined loop as the 128 x 384 kernel below (fragments double-buffered per 16-deep block, the next slice's DMA pieces and the next block's
 // fragment reads issued in the gaps between the MFMAs, one barrier in the middle of the iteration).  What the smaller tile buys: two INDEPENDENT workgroups
@@ -35,7 +52,7 @@ struct X3Args {
 // N / 384 (N = 384: 1179 tiles = 4.6 rounds against 393 = 1.54 rounds of the big tile).  What it costs: 98 MFMA-flop per staged byte against 147.
 struct X3Frag2 { uint4 ah[2], al[2], bh[2], bl[2]; };
 
-template <bool PLANES>
+template <bool PLANES, bool CONV>
 __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(X3Args g) {
     constexpr int CPR = 4, TILE_U4 = 128 * CPR, STAGE_U4 = 4 * TILE_U4;      // a_hi | a_lo | w_hi | w_lo
     constexpr int OPER_U4 = 2 * STAGE_U4, EPI_U4 = 4 * 32 * 72 * 4 / 16;
@@ -58,16 +75,18 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(X3Args g) {
     for (int q = 0; q < 2; ++q) {
         const int rr = (wave * 2 + q) * 16 + (lane >> 2), slot = lane & 3;
         const int c = slot ^ ((rr >> 2) & 3);
-        const int ra = min(tm * 128 + rr, d.M - 1), rb = min(tn * 128 + rr, d.N - 1);
+        const int rm = min(tm * 128 + rr, d.M - 1), rb = min(tn * 128 + rr, d.N - 1);
+        const int ra = CONV ? x3_conv_row(d, rm) : rm;
         voffA[q] = (uint32_t)(((int64_t)ra * d.lda + c * 8) * 2);
         voffB[q] = (uint32_t)(((int64_t)rb * d.ldb + c * 8) * 2);
     }
     const uint32_t lds_addr = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(&lds[0]));
-    auto dma_part = [&](int kt, int n) __attribute__((always_inline)) {      // n = 0 a_hi, 1 a_lo, 2 w_hi, 3 w_lo: two pieces each
+    X3ConvK ck;
+    auto dma_part = [&](int kt, int n, int64_t koa) __attribute__((always_inline)) {      // n = 0 a_hi, 1 a_lo, 2 w_hi, 3 w_lo: two pieces each; koa: A offset of the slice
         const uint32_t base = lds_addr + (uint32_t)(((kt & 1) * STAGE_U4 + n * TILE_U4 + wave * 2 * 64) * 16);
         const int64_t ko = (int64_t)kt * 32;
-        if (n == 0) lds_dma16x2(Ah + ko, base, voffA[0], voffA[1]);
-        else if (n == 1) lds_dma16x2(Al + ko, base, voffA[0], voffA[1]);
+        if (n == 0) lds_dma16x2(Ah + koa, base, voffA[0], voffA[1]);
+        else if (n == 1) lds_dma16x2(Al + koa, base, voffA[0], voffA[1]);
         else if (n == 2) lds_dma16x2(Wh + ko, base, voffB[0], voffB[1]);
         else lds_dma16x2(Wl + ko, base, voffB[0], voffB[1]);
     };
@@ -96,11 +115,21 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(X3Args g) {
         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, av), __builtin_bit_cast(bf16x8_t, bv), acc[i][j], 0, 0, 0);
     };
     X3Frag2 F0, F1;
+    auto koa_of = [&](int kt) __attribute__((always_inline)) -> int64_t {      // slices are staged in order: the conv state steps with each call
+        if constexpr (!CONV) return (int64_t)kt * 32;
+        const int64_t o = ck.off(d);
+        ck.next(d);
+        return o;
+    };
+    {
+        const int64_t koa = koa_of(0);
 #pragma unroll
-    for (int n = 0; n < 4; ++n) dma_part(0, n);
+        for (int n = 0; n < 4; ++n) dma_part(0, n, koa);
+    }
     if (nk > 1) {
+        const int64_t koa = koa_of(1);
 #pragma unroll
-        for (int n = 0; n < 4; ++n) dma_part(1, n);
+        for (int n = 0; n < 4; ++n) dma_part(1, n, koa);
         wait_vm<8>();      // slice 0 landed (this wave's pieces); slice 1 stays in flight
     } else {
         wait_vm<0>();
@@ -112,6 +141,7 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(X3Args g) {
         const uint4* sb = lds + (kt & 1) * STAGE_U4;
         const uint4* sn = lds + ((kt + 1) & 1) * STAGE_U4;
         const bool more = kt + 1 < nk, more2 = kt + 2 < nk;
+        const int64_t koa2 = more2 ? koa_of(kt + 2) : 0;
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int n = 0; n < 12; ++n) {                       // block (kt, 0) on F0; the reads of block (kt, 1) fill F1 in the gaps
@@ -133,7 +163,7 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(X3Args g) {
             if (n % 3 == 2 && n < 11) {
                 __builtin_amdgcn_sched_barrier(0);
                 const int sl = n / 3;                      // 0 .. 2
-                if (more2) { dma_part(kt + 2, sl); if (sl == 2) dma_part(kt + 2, 3); }
+                if (more2) { dma_part(kt + 2, sl, koa2); if (sl == 2) dma_part(kt + 2, 3, koa2); }
                 if (more) { frag_read(F0, sn, 0, sl * 3); frag_read(F0, sn, 0, sl * 3 + 1); if (sl * 3 + 2 < 8) frag_read(F0, sn, 0, sl * 3 + 2); }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -184,7 +214,7 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(X3Args g) {
 // output row in one workgroup (LN = true: LayerNorm of that row in the epilogue), N = 1152 / 1536 as 3 / 4 column tiles (consecutive workgroups = one A panel).
 struct X3Frag { uint4 ah[2], al[2], bh[3], bl[3]; };
 
-template <bool LN>
+template <bool LN, bool CONV>
 __global__ __launch_bounds__(512, 2) void gemm_x3_n384_kernel(X3Args g) {
     constexpr int CPR = 4, A_U4 = 128 * CPR, B_U4 = 384 * CPR, STAGE_U4 = 2 * A_U4 + 2 * B_U4;      // a_hi | a_lo | w_hi | w_lo = 64 KB
     extern __shared__ __attribute__((aligned(1024))) uint4 lds[];
@@ -202,7 +232,8 @@ __global__ __launch_bounds__(512, 2) void gemm_x3_n384_kernel(X3Args g) {
     {
         const int slot = lane & 3;
         const int ra_l = wave * 16 + (lane >> 2);
-        voffA = (uint32_t)(((int64_t)min(tm * 128 + ra_l, d.M - 1) * d.lda + (slot ^ ((ra_l >> 2) & 3)) * 8) * 2);
+        const int rm = min(tm * 128 + ra_l, d.M - 1);
+        voffA = (uint32_t)(((int64_t)(CONV ? x3_conv_row(d, rm) : rm) * d.lda + (slot ^ ((ra_l >> 2) & 3)) * 8) * 2);
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
             const int rb_l = (wave * 3 + q) * 16 + (lane >> 2);
@@ -211,13 +242,14 @@ __global__ __launch_bounds__(512, 2) void gemm_x3_n384_kernel(X3Args g) {
     }
     const uint32_t lds_addr = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(&lds[0]));
     // the 8 DMA pieces of a slice, individually placeable: n = 0 a_hi, 1 a_lo, 2 w_hi (two pieces), 3 w_hi (third), 4 w_lo (two), 5 w_lo (third)
-    auto dma_part = [&](int kt, int n) __attribute__((always_inline)) {
+    X3ConvK ck;
+    auto dma_part = [&](int kt, int n, int64_t koa) __attribute__((always_inline)) {      // koa: A offset of the slice (kt * 32, or the conv tap's)
         const uint32_t sbase = lds_addr + (uint32_t)((kt & 1) * STAGE_U4 * 16);
         const int64_t ko = (int64_t)kt * 32;
         const uint32_t da = sbase + (uint32_t)(wave * 64 * 16);
         const uint32_t db = sbase + (uint32_t)((2 * A_U4 + wave * 3 * 64) * 16);
-        if (n == 0) lds_dma16(Ah + ko, da, voffA);
-        else if (n == 1) lds_dma16(Al + ko, da + A_U4 * 16, voffA);
+        if (n == 0) lds_dma16(Ah + koa, da, voffA);
+        else if (n == 1) lds_dma16(Al + koa, da + A_U4 * 16, voffA);
         else if (n == 2) lds_dma16x2(Wh + ko, db, voffB[0], voffB[1]);
         else if (n == 3) lds_dma16(Wh + ko, db + 0x800, voffB[2]);
         else if (n == 4) lds_dma16x2(Wl + ko, db + B_U4 * 16, voffB[0], voffB[1]);
@@ -248,11 +280,21 @@ __global__ __launch_bounds__(512, 2) void gemm_x3_n384_kernel(X3Args g) {
         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, av), __builtin_bit_cast(bf16x8_t, bv), acc[i][j], 0, 0, 0);
     };
     X3Frag F0, F1;
+    auto koa_of = [&](int kt) __attribute__((always_inline)) -> int64_t {      // slices are staged in order: the conv state steps with each call
+        if constexpr (!CONV) return (int64_t)kt * 32;
+        const int64_t o = ck.off(d);
+        ck.next(d);
+        return o;
+    };
+    {
+        const int64_t koa = koa_of(0);
 #pragma unroll
-    for (int n = 0; n < 6; ++n) dma_part(0, n);
+        for (int n = 0; n < 6; ++n) dma_part(0, n, koa);
+    }
     if (nk > 1) {
+        const int64_t koa = koa_of(1);
 #pragma unroll
-        for (int n = 0; n < 6; ++n) dma_part(1, n);
+        for (int n = 0; n < 6; ++n) dma_part(1, n, koa);
         wait_vm<8>();      // slice 0 landed (this wave's pieces); slice 1 stays in flight
     } else {
         wait_vm<0>();
@@ -264,6 +306,7 @@ __global__ __launch_bounds__(512, 2) void gemm_x3_n384_kernel(X3Args g) {
         const uint4* sb = lds + (kt & 1) * STAGE_U4;
         const uint4* sn = lds + ((kt + 1) & 1) * STAGE_U4;
         const bool more = kt + 1 < nk, more2 = kt + 2 < nk;
+        const int64_t koa2 = more2 ? koa_of(kt + 2) : 0;
         // ---- block (kt, 0) on F0; the reads of block (kt, 1) fill F1 in the gaps
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -289,7 +332,7 @@ __global__ __launch_bounds__(512, 2) void gemm_x3_n384_kernel(X3Args g) {
             if (n % 3 == 2 && n < 15) {
                 __builtin_amdgcn_sched_barrier(0);
                 const int sl = n / 3;                      // 0 .. 4
-                if (more2) { dma_part(kt + 2, sl == 0 ? 0 : sl + 1); if (sl == 0) dma_part(kt + 2, 1); }
+                if (more2) { dma_part(kt + 2, sl == 0 ? 0 : sl + 1, koa2); if (sl == 0) dma_part(kt + 2, 1, koa2); }
                 if (more) { frag_read(F0, sn, 0, sl * 2); frag_read(F0, sn, 0, sl * 2 + 1); }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -466,7 +509,9 @@ __global__ __launch_bounds__(256) void from_planes_kernel(const bf16_t* __restri
 static int g_x3_tile = 0;
 extern "C" int p3_gemm_x3_tile(int mode) { const int was = g_x3_tile; g_x3_tile = mode; return was; }
 // the 128 x 384 tile (one workgroup per CU, 147 MFMA-flop per staged byte) pays where its quantisation over the CUs is not worse than the small tile's and
-// the epilogue is short against the main loop; see the table in DESIGN.md section 5
+// the epilogue is short against the main loop; see the table in DESIGN.md section 5.  The 3 x 3 convolution (conv_ci > 0; DESIGN section 0s, tools/mb_conv_planes.py,
+// bench batch 64 on the 28 x 28 grid) follows the same rule: forward N = 384, K = 6912 - 746 us here, 768 us on the small tile, 830 us as head + remainder;
+// input gradient N = 768, K = 3456 - 737 us here whole, 741 us on the small tile, 688 us with the host's split (384 row tiles here, 8 on the small tile)
 static bool x3_big_tile(const p3_gemm_x3_desc* d) {
     if (d->N <= 256) return false;
     return d->K >= 1024;
@@ -485,8 +530,16 @@ extern "C" int p3_gemm_x3(const p3_gemm_x3_desc* d, void* stream) {
     P3_CHECK(!d->aux || (d->ldaux % 4 == 0 && (uintptr_t)d->aux % 16 == 0), P3_EALIGN, "p3_gemm_x3: aux alignment");
     P3_CHECK(!d->mul || (d->ldmul % 4 == 0 && (uintptr_t)d->mul % 16 == 0), P3_EALIGN, "p3_gemm_x3: mul alignment");
     P3_CHECK(d->act == P3_ACT_NONE || d->act == P3_ACT_GELU, P3_EUNSUP, "p3_gemm_x3: act NONE or GELU");
-    P3_CHECK((int64_t)d->M * d->lda * 2 < (1ll << 31) && (int64_t)d->N * d->ldb * 2 < (1ll << 31), P3_EUNSUP, "p3_gemm_x3: operand larger than the 32-bit DMA offsets");
+    P3_CHECK((d->conv_ci != 0 || (int64_t)d->M * d->lda * 2 < (1ll << 31)) && (int64_t)d->N * d->ldb * 2 < (1ll << 31), P3_EUNSUP, "p3_gemm_x3: operand larger than the 32-bit DMA offsets");
     const bool ln = d->ln_gamma != nullptr;
+    const bool conv = d->conv_ci != 0;
+    if (conv) {
+        P3_CHECK(d->conv_ci > 0 && d->conv_ci % 32 == 0 && d->K == 9 * d->conv_ci, P3_ESHAPE, "p3_gemm_x3: conv needs conv_ci % 32 == 0 and K == 9 * conv_ci");
+        P3_CHECK(d->conv_B > 0 && d->conv_H > 0 && d->conv_W > 0 && d->conv_row0 >= 0 && d->lda >= d->conv_ci, P3_EINVAL, "p3_gemm_x3: conv_B / conv_H / conv_W / conv_row0");
+        P3_CHECK((int64_t)d->conv_row0 + d->M <= (int64_t)d->conv_B * d->conv_H * d->conv_W, P3_ESHAPE, "p3_gemm_x3: conv_row0 + M beyond the conv_B * conv_H * conv_W output pixels");
+        P3_CHECK((int64_t)d->conv_B * (d->conv_H + 2) * (d->conv_W + 2) * d->lda * 2 < (1ll << 31), P3_EUNSUP, "p3_gemm_x3: padded image larger than the 32-bit DMA offsets");
+        P3_CHECK(!ln && d->tile != 3, P3_EUNSUP, "p3_gemm_x3: the conv addressing is built into the two tile kernels only (no fused LayerNorm, no A-stationary kernel)");
+    }
     if (ln) {
         P3_CHECK(d->N == 384 && !planes && d->act == P3_ACT_NONE && !d->mul, P3_EUNSUP, "p3_gemm_x3: fused LayerNorm needs N == 384, fp32 C, no activation");
         P3_CHECK(d->ln_beta && d->ln_hi && d->ln_lo && d->ldln % 8 == 0 && ((uintptr_t)d->ln_hi | (uintptr_t)d->ln_lo) % 16 == 0, P3_EINVAL, "p3_gemm_x3: ln_* arguments");
@@ -513,15 +566,18 @@ extern "C" int p3_gemm_x3(const p3_gemm_x3_desc* d, void* stream) {
         g.tiles_n = p3_ceil_div(d->N, 384);
         constexpr size_t LDS = 2 * (2 * 128 * 4 + 2 * 384 * 4) * 16;          // 2 slices x 64 KB
         const dim3 grid(g.tiles_m * g.tiles_n), block(512);
-        return !ln ? p3_launch<gemm_x3_n384_kernel<false>>("gemm_x3_n384_kernel<false>", grid, block, LDS, s, g)
-                   : p3_launch<gemm_x3_n384_kernel<true>>("gemm_x3_n384_kernel<true>", grid, block, LDS, s, g);
+        if (conv) return p3_launch<gemm_x3_n384_kernel<false, true>>("gemm_x3_n384_conv_kernel", grid, block, LDS, s, g);
+        return !ln ? p3_launch<gemm_x3_n384_kernel<false, false>>("gemm_x3_n384_kernel<false>", grid, block, LDS, s, g)
+                   : p3_launch<gemm_x3_n384_kernel<true, false>>("gemm_x3_n384_kernel<true>", grid, block, LDS, s, g);
     }
     P3_CHECK(!ln, P3_EUNSUP, "p3_gemm_x3: fused LayerNorm needs N == 384");
     g.tiles_n = p3_ceil_div(d->N, 128);
-    if (p3_tracing()) p3_note_kernel(planes ? "gemm_x3_kernel<true>" : "gemm_x3_kernel<false>");
+    if (p3_tracing()) p3_note_kernel(conv ? (planes ? "gemm_x3_conv_kernel<true>" : "gemm_x3_conv_kernel<false>") : (planes ? "gemm_x3_kernel<true>" : "gemm_x3_kernel<false>"));
     dim3 grid(g.tiles_m * g.tiles_n), block(256);
-    if (planes) hipLaunchKernelGGL(gemm_x3_kernel<true>, grid, block, 0, s, g);
-    else hipLaunchKernelGGL(gemm_x3_kernel<false>, grid, block, 0, s, g);
+    if (conv && planes) hipLaunchKernelGGL((gemm_x3_kernel<true, true>), grid, block, 0, s, g);
+    else if (conv) hipLaunchKernelGGL((gemm_x3_kernel<false, true>), grid, block, 0, s, g);
+    else if (planes) hipLaunchKernelGGL((gemm_x3_kernel<true, false>), grid, block, 0, s, g);
+    else hipLaunchKernelGGL((gemm_x3_kernel<false, false>), grid, block, 0, s, g);
     P3_LAUNCH_CHECK();
     return P3_OK;
 }

@@ -492,7 +492,7 @@ int as_dispatch(const AsArgs& g, int epi, int var, int nwg, hipStream_t s) {
 bool p3_gemm_x3_as_default(const p3_gemm_x3_desc* d) { return d->N >= 1024 && !(d->mul && d->c_lo); }
 
 bool p3_gemm_x3_as_ok(const p3_gemm_x3_desc* d) {
-    return (d->K == 384 || d->K == 256) && d->N % 32 == 0 && d->N <= 4096 && !d->ln_gamma && as_epi_built(as_epi_of(d)) &&
+    return d->conv_ci == 0 && (d->K == 384 || d->K == 256) && d->N % 32 == 0 && d->N <= 4096 && !d->ln_gamma && as_epi_built(as_epi_of(d)) &&
            (int64_t)d->N * d->ldb * 2 < (1ll << 31) && (!d->bias || (uintptr_t)d->bias % 16 == 0) &&
            (int64_t)d->M * d->ldc * 4 < (1ll << 32) && (!d->aux || (int64_t)d->M * d->ldaux * 4 < (1ll << 32)) &&
            (!d->mul || (int64_t)d->M * d->ldmul * 4 < (1ll << 32)) && (!d->residual || (int64_t)d->M * d->ldr * 4 < (1ll << 32));

@@ -5,6 +5,8 @@
 // launches, with no fault and no message.  The rules for everything below:
 //   * m0 is the LDS-DMA destination base.  It is compiler-reserved and not preserved around a statement: it is saved, written and restored inside the SAME
 //     statement that reads it (`keep`), never across two.
+//   * a statement that steps m0 with s_add_u32 overwrites SCC and says so ("scc" in its clobber list): hipcc keeps a scalar compare alive across an asm
+//     statement that does not (the conv-tap state of gemm_x3.hip - a compare, the DMA statements, then the s_cselect - read the s_add's carry instead).
 //   * `s_nop 0` stands between every write of m0 and the DMA instruction that reads it; hipcc pads nothing inside the string, so wait states belong in it.
 //   * "s" operands (the base pointer, the LDS destination) must be provably wave-uniform: a kernel argument, a blockIdx expression, or a
 //     __builtin_amdgcn_readfirstlane.  The per-lane part of the source address is the "v" byte offset.
@@ -42,7 +44,7 @@ __device__ __forceinline__ void lds_dma16x2(const void* base, uint32_t lds_dst, 
         "s_mov_b32 m0, %4\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\t"
         "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\t"
         "s_mov_b32 m0, %0"
-        : "=&s"(keep) : "v"(v0), "v"(v1), "s"(base), "s"(lds_dst) : "memory");
+        : "=&s"(keep) : "v"(v0), "v"(v1), "s"(base), "s"(lds_dst) : "memory", "scc");
 }
 // one piece from base_a to dst_a, then three consecutive pieces from base_b starting at dst_b (the 128 x 384 tile of gemm_dma.hip: A panel | W panel)
 __device__ __forceinline__ void lds_dma16x1p3(const void* base_a, uint32_t dst_a, uint32_t va, const void* base_b, uint32_t dst_b, uint32_t v0, uint32_t v1,
@@ -55,7 +57,7 @@ __device__ __forceinline__ void lds_dma16x1p3(const void* base_a, uint32_t dst_a
         "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, %6\n\t"
         "s_add_u32 m0, m0, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, %6\n\t"
         "s_mov_b32 m0, %0"
-        : "=&s"(keep) : "v"(va), "v"(v0), "v"(v1), "v"(v2), "s"(base_a), "s"(base_b), "s"(dst_a), "s"(dst_b) : "memory");
+        : "=&s"(keep) : "v"(va), "v"(v0), "v"(v1), "v"(v2), "s"(base_a), "s"(base_b), "s"(dst_a), "s"(dst_b) : "memory", "scc");
 }
 
 // ---- waits ---------------------------------------------------------------------------------------------------------------------------------------

@@ -6,6 +6,8 @@ HIP data flow: both stems write straight into one token-major (NHWC) canvas [B, 
 conv is an implicit-GEMM gather over that canvas with the BN batch statistics accumulated in the GEMM epilogue, and
 BN + ReLU + CLS + pos_embed are applied by one assemble kernel that produces the fp32 residual stream.
 """
+import os
+
 import torch
 import torch.nn as nn
 
@@ -63,6 +65,11 @@ class EarlyFusionViT(nn.Module):
         return pool(y, self.cfg.experiment.encoder.out_feature_dim)
 
 
+# A/B switch: the fp32x3 fusion convolution (forward, dX, dW) on the planes GEMM kernels - conv-tap addressing over one zero-bordered planes image per operand
+# (DESIGN section 0s); 0 keeps the register-staged implicit GEMM and the nine shifted fp32 weight-gradient products
+CONV_PLANES = [os.environ.get("P3_CONV_PLANES", "1") != "0"]
+
+
 def _zero_lidar(canvas, D):
     canvas = canvas.clone()
     canvas[..., D:] = 0
@@ -79,17 +86,30 @@ class _FusionConvBN(torch.autograd.Function):
         bn = mod.fusion_layer[1]
         training = mod.training
         # [Co, Ci, 3, 3] -> [Co, (ky, kx, ci)] to match the NHWC gather order
-        w2 = ops.shadow(w, cd, key="khwc", fn=lambda t: t.permute(0, 2, 3, 1).reshape(t.shape[0], -1))
+        khwc = lambda t: t.permute(0, 2, 3, 1).reshape(t.shape[0], -1)
+        w2 = ops.shadow(w, cd, key="khwc", fn=khwc)
         sums = torch.zeros(2 * D, dtype=torch.float32, device=canvas.device) if training else None
-        pre = hip.gemm(canvas.view(B * g * g, 2 * D), w2, bias=b.detach(), a_mode=hip.A_CONV3X3, conv=(B, g, g, 2 * D), lda=2 * D,
-                       out_dtype=cd, colsum=sums[:D] if training else None, colsumsq=sums[D:] if training else None, w_planes=ops.wpl(w2))
+        # fp32x3 only; 2 D channels per tap: whole 128-column weight-gradient tiles
+        wp = ops.derived_planes(w, "khwc", khwc) if CONV_PLANES[0] and hip.split_now() and cd == torch.float32 and canvas.dtype == torch.float32 and D % 64 == 0 else None
+        cpl = None
+        if wp is not None:
+            # fp32x3: the canvas becomes ONE zero-bordered planes image (kept for the weight gradient instead of the fp32 canvas), the convolution a planes GEMM
+            # whose A base moves by the tap's row shift; the batch statistics come from one fixed-order pass over pre (the planes epilogue has no column sums)
+            cpl = hip.pad_nhwc_planes(canvas.view(B * g * g, 2 * D), B, g, g)
+            pre = hip.gemm_x3(cpl, wp, bias=b.detach(), conv=(B, g, g, 2 * D))
+            if training:
+                hip.col_stats(pre, sums)
+        else:
+            pre = hip.gemm(canvas.view(B * g * g, 2 * D), w2, bias=b.detach(), a_mode=hip.A_CONV3X3, conv=(B, g, g, 2 * D), lda=2 * D,
+                           out_dtype=cd, colsum=sums[:D] if training else None, colsumsq=sums[D:] if training else None, w_planes=ops.wpl(w2))
         world = ops.sync_stats(sums) if training else 1
         scale, shift, mean, rstd = hip.bn_finalize(sums, float(B * g * g * world), gamma.detach(), beta.detach(), bn.running_mean, bn.running_var,
                                                    bn.eps, bn.momentum, training, save=True)
         if training:
             ops.bump_batches_tracked(bn)
-        ctx.save_for_backward(canvas, pre, w, gamma, mean, rstd)
-        ctx.mod, ctx.B = mod, B
+        # planes path: the guarded buffer of the canvas image (its Planes view is rebuilt in backward) takes the fp32 canvas's place
+        ctx.save_for_backward(canvas if cpl is None else cpl.buf._base, pre, w, gamma, mean, rstd)
+        ctx.mod, ctx.B, ctx.planes = mod, B, cpl is not None
         ctx.mark_non_differentiable(mean)
         return pre, scale, shift, mean
 
@@ -104,6 +124,8 @@ class _FusionConvBN(torch.autograd.Function):
         M = B * g * g
         dpre = dpre.contiguous()
         dg, dbt, a, b = ops.bn_backward_coeffs(dscC, dshift, gamma.detach(), mean, rstd, float(M), mod.training, params=(bn.weight, bn.bias))
+        if ctx.planes:
+            return _FusionConvBN._backward_planes(ctx, canvas, dpre, pre, w, a, b, dg, dbt)
         if mod.training:
             hip.affine_fix(dpre, pre, a, b)
         db = ops.bias_grad_before_bn(dpre, mod.training, mod.fusion_layer[0].bias)
@@ -127,4 +149,30 @@ class _FusionConvBN(torch.autograd.Function):
         # input gradient: correlation with the flipped kernel, [Ci, (ky', kx', co)]
         wf = ops.shadow(w, cd, key="flipT", fn=lambda t_: t_.flip(2, 3).permute(1, 2, 3, 0).reshape(t_.shape[1], -1))
         dcanvas = hip.gemm(dpre, wf, a_mode=hip.A_CONV3X3, conv=(B, g, g, D), lda=D, out_dtype=cd, w_planes=ops.wpl(wf)).view(B, g * g, 2 * D)
+        return dcanvas, dw, db, dg, dbt, None, None
+
+    @staticmethod
+    def _backward_planes(ctx, cbuf, dpre, pre, w, a, b, dg, dbt):
+        """fp32x3 on planes: dpre (+ the statistics term a + b pre, fused: in training the fixed fp32 gradient has no other reader) becomes one zero-bordered
+        planes image that is the A operand of BOTH products - the weight gradient (nine taps = column tiles of one launch, the canvas image's rows shifted per
+        tile) and the input gradient (the forward's addressing with the flipped / transposed kernel)."""
+        mod, B = ctx.mod, ctx.B
+        cd, g, D = mod.cd, mod.g, mod.D
+        M, P = B * g * g, g + 2
+        R = B * P * P
+        guard = P + 1
+        cp = hip.Planes(cbuf[guard:cbuf.shape[0] - guard], R, 2 * D)
+        db = ops.bias_grad_before_bn(dpre, mod.training, mod.fusion_layer[0].bias)          # eval: the real column sum of the (unfixed) gradient
+        Dp = (D + 127) // 128 * 128                  # the weight-gradient kernel's 128-row output tiles: a narrower gradient gets zero columns
+        fix = dict(pre=pre, a=a, b=b) if mod.training else {}
+        dp = hip.pad_nhwc_planes(dpre.view(M, D), B, g, g, guard=0, cols=Dp, **fix)
+        dW2 = torch.zeros((Dp, 9 * 2 * D), dtype=torch.float32, device=dpre.device)
+        with hip.tn_parking(hip.CONV_PARK) as parking:
+            hip.gemm_tn_x3_conv(dp, cp, P, out=dW2)
+        if parking.on and hip.reduce_pending():
+            hip.reduce_flush()
+        dw = dW2[:D].view(D, 3, 3, 2 * D).permute(0, 3, 1, 2).contiguous()
+        dp = dp.narrow(D)
+        wfp = ops.derived_planes(w, "flipT", lambda t_: t_.flip(2, 3).permute(1, 2, 3, 0).reshape(t_.shape[1], -1))
+        dcanvas = hip.gemm_x3(dp, wfp, conv=(B, g, g, D)).view(B, g * g, 2 * D)
         return dcanvas, dw, db, dg, dbt, None, None

@@ -1918,6 +1918,13 @@ class Planes:
             buf[rows:].zero_()
         return Planes(buf, rows, cols)
 
+    def narrow(self, cols):
+        """the first `cols` columns as Planes over the same buffer (same rows and row stride)"""
+        p = Planes.__new__(Planes)
+        p.buf, p.rows, p.cols = self.buf, self.rows, cols
+        p.hi, p.lo = self.hi[:, :cols], self.lo[:, :cols]
+        return p
+
     @property
     def ld(self):
         return self.buf.stride(0)
@@ -1958,7 +1965,8 @@ class GemmX3Desc(Structure):
                 ("bias", c_void_p), ("residual", c_void_p), ("ldr", c_int), ("act", c_int),
                 ("aux", c_void_p), ("ldaux", c_int), ("mul", c_void_p), ("ldmul", c_int),
                 ("ln_gamma", c_void_p), ("ln_beta", c_void_p), ("ln_eps", c_float),
-                ("ln_hi", c_void_p), ("ln_lo", c_void_p), ("ldln", c_int), ("ln_mean", c_void_p), ("ln_rstd", c_void_p), ("tile", c_int)]
+                ("ln_hi", c_void_p), ("ln_lo", c_void_p), ("ldln", c_int), ("ln_mean", c_void_p), ("ln_rstd", c_void_p), ("tile", c_int),
+                ("conv_B", c_int), ("conv_H", c_int), ("conv_W", c_int), ("conv_ci", c_int), ("conv_row0", c_int)]
 
 
 _x3_cus = {}
@@ -1976,10 +1984,28 @@ def x3_cus(device):
 X3_RAGGED_SPLIT = [os.environ.get("P3_X3_RAGGED", "1") != "0"]               # A/B switch of the ragged-round rule below
 
 
-def gemm_x3(a, w, *, bias=None, act=ACT_NONE, residual=None, aux=None, mul=None, out=None, out_planes=False, ln=None):
+def x3_conv_row(m, H, W):
+    """row of the zero-bordered image [B, H+2, W+2] that output pixel m of the unpadded [B, H, W] grid reads its centre tap from (csrc/gemm_x3.hip x3_conv_row)"""
+    b, r = divmod(m, H * W)
+    y, x = divmod(r, W)
+    return (b * (H + 2) + y + 1) * (W + 2) + x + 1
+
+
+def gemm_x3(a, w, *, bias=None, act=ACT_NONE, residual=None, aux=None, mul=None, out=None, out_planes=False, ln=None, conv=None, conv_rows=None, tile=0,
+            ragged=None):
     """C = epilogue((a_hi + a_lo) (w_hi + w_lo)^T).  a: Planes [M, K]; w: (hi, lo) bf16 [N, K] tensors (or Planes); out: fp32 [M, N] tensor or Planes
-    (out_planes=True allocates one).  ln = (gamma, beta, eps, Planes out, mean, rstd): LayerNorm of the output row fused into the epilogue (N == 384)."""
+    (out_planes=True allocates one).  ln = (gamma, beta, eps, Planes out, mean, rstd): LayerNorm of the output row fused into the epilogue (N == 384).
+    conv = (B, H, W, Ci): 3 x 3 convolution - a is the zero-bordered planes image [B (H+2) (W+2), Ci] (pad_nhwc_planes), w is [N, (ky, kx, ci)], the output rows
+    are the B H W interior pixels (conv_rows = (first, count): only these output pixels; out, residual, ... start at pixel `first`).  tile: 0 the library's rule, 1 / 2 force a tile kernel for this call; ragged: False keeps the launch whole (measurement)."""
     M, K = a.rows, a.cols
+    if conv is not None:
+        cB, cH, cW, cCi = conv
+        if a.rows != cB * (cH + 2) * (cW + 2) or a.cols != cCi:
+            raise P3Error("gemm_x3: conv needs the zero-bordered image [B (H+2) (W+2), Ci] as a")
+        row0, M = (0, cB * cH * cW) if conv_rows is None else conv_rows
+        K = 9 * cCi
+        if row0 < 0 or M <= 0 or row0 + M > cB * cH * cW:
+            raise P3Error("gemm_x3: conv_rows outside the B H W output pixels")
     w_hi, w_lo = (w.hi, w.lo) if isinstance(w, Planes) else w
     N = w_hi.shape[0]
     if w_hi.shape[1] != K or w_hi.stride(0) != w_lo.stride(0):
@@ -2000,6 +2026,9 @@ def gemm_x3(a, w, *, bias=None, act=ACT_NONE, residual=None, aux=None, mul=None,
     if residual is not None:
         d.residual, d.ldr = residual.data_ptr(), residual.stride(-2)
     d.act = act
+    d.tile = tile
+    if conv is not None:
+        d.conv_B, d.conv_H, d.conv_W, d.conv_ci, d.conv_row0 = cB, cH, cW, cCi, row0
     if aux is not None:
         d.aux, d.ldaux = aux.data_ptr(), aux.stride(-2)
     if mul is not None:
@@ -2013,22 +2042,34 @@ def gemm_x3(a, w, *, bias=None, act=ACT_NONE, residual=None, aux=None, mul=None,
         ev = KTIMER.begin()
         check(lib().p3_gemm_x3(byref(dd), stream()), "p3_gemm_x3")
         if ev is not None:
-            nbytes = 4.0 * (rows * K + N * K + rows * N) + (4.0 * rows * N if residual is not None else 0) + (4.0 * rows * N if aux is not None else 0) \
+            a_rows = rows if conv is None else a.rows * rows / M          # conv: the image is read once (nine taps of it from L2), not K / Ci times
+            nbytes = 4.0 * (a_rows * a.cols + N * K + rows * N) + (4.0 * rows * N if residual is not None else 0) + (4.0 * rows * N if aux is not None else 0) \
                 + (4.0 * rows * N if mul is not None else 0) + (4.0 * rows * N if ln is not None else 0)
             KTIMER.end(ev, lib().p3_last_kernel().decode() or "gemm_x3_kernel", 2.0 * rows * N * K, nbytes)
 
     # A ragged last round of the 128 x 384 tile (csrc/gemm_x3.hip picks it for N > 256, K >= 1024; one workgroup per CU): M = 50 240 is 393 row tiles = a full round
     # of 256 and a round of 137 with 119 CUs idle - two round times for 1.5 rounds of work.  Whole rounds go to the big tile, the remainder to the 128 x 128 tile
     # (two workgroups per CU: 137 x 3 = 411 small tiles are ONE round of 512 slots at a third of the work each), back to back on the same stream.
+    # conv: the forward of the fusion convolution (N = 384, K = 6912) stays WHOLE on the 128 x 384 tile - 746 us against 830 us split (its 136 x 3 remainder
+    # tiles walk 216 slices each, longer than the half round they save) and 768 us on the small tile; its input gradient (N = 768, K = 3456: two column tiles, a
+    # round is cus // 2 row tiles, 392 = 3 rounds + 8) takes the split - 688 us against 737 whole / 741 on the small tile (tools/mb_conv_planes.py,
+    # profiles/fusion_conv_planes_mb.txt)
     tm = (M + 127) // 128
     cus = x3_cus(a.buf.device)
+    if conv is not None and 384 < N <= 768:
+        cus //= 2
     rem = tm % cus
-    if X3_RAGGED_SPLIT[0] and ln is None and 256 < N <= 384 and K >= 1024 and tm > cus and 0 < rem <= (3 * cus) // 4:
+    split_ok = X3_RAGGED_SPLIT[0] if ragged is None else ragged
+    if split_ok and tile == 0 and ln is None and ((conv is None and 256 < N <= 384) or (conv is not None and 384 < N <= 768)) and K >= 1024 and tm > cus \
+            and 0 < rem <= (3 * cus) // 4:
         head = (tm - rem) * 128
         d2 = GemmX3Desc()
         ctypes.memmove(byref(d2), byref(d), ctypes.sizeof(d))
         d.M, d2.M = head, M - head
-        d2.a_hi, d2.a_lo = d.a_hi + head * d.lda * 2, d.a_lo + head * d.lda * 2
+        if conv is not None:
+            d2.conv_row0 = row0 + head           # the image stays where it is: the kernel maps its output rows from pixel `head` on
+        else:
+            d2.a_hi, d2.a_lo = d.a_hi + head * d.lda * 2, d.a_lo + head * d.lda * 2
         esz = 2 if isinstance(out, Planes) else 4
         d2.c = d.c + head * d.ldc * esz
         if isinstance(out, Planes):
@@ -2061,6 +2102,67 @@ def gemm_tn_x3(a, b, out=None, colsum_out=None):
     if ev is not None:
         KTIMER.end(ev, lib().p3_last_kernel().decode() or "gemm_tn_x3_kernel<4>", 2.0 * a.rows * N * K, float(4 * a.rows * (N + K) + N * K * 4))
     return out
+
+
+def pad_nhwc_planes(src, B, H, W, pre=None, a=None, b=None, guard=None, cols=None):
+    """fp32 token-major map [B*H*W, C] (row stride free) -> Planes of the zero-bordered image [B (H+2) (W+2), C]: a view into a buffer that also holds `guard`
+    zero rows (default W + 3: one padded row + 1, what the shifted rows of gemm_tn_x3_conv reach) in front of and behind the 64-padded rows - written in the same
+    pass.  pre, a, b: the value split is src + a + b * pre (affine_fix's arithmetic; src itself is not written).  cols >= C: zero columns up to
+    that width (Planes.narrow gives the C-column view back)."""
+    _dev(src)
+    M, C = src.shape
+    if M != B * H * W:
+        raise P3Error("pad_nhwc_planes: src must be [B*H*W, C]")
+    guard = W + 3 if guard is None else guard
+    R = B * (H + 2) * (W + 2)
+    Ra = (R + 63) // 64 * 64
+    Cp = C if cols is None else cols
+    full = torch.empty((Ra + 2 * guard, 2 * Cp), dtype=torch.bfloat16, device=src.device)
+    out = Planes(full[guard:guard + Ra], R, Cp)
+    ev = KTIMER.begin()
+    check(lib().p3_pad_nhwc_planes(ptr(src), src.stride(0), ptr(pre), pre.stride(0) if pre is not None else 0, ptr(a), ptr(b), ptr(out.hi), ptr(out.lo), out.ld,
+                                   B, H, W, C, Cp, guard, Ra, stream()), "p3_pad_nhwc_planes")
+    if ev is not None:
+        KTIMER.end(ev, "pad_nhwc_planes_kernel<fix>" if pre is not None else "pad_nhwc_planes_kernel", (2.0 if pre is not None else 0.0) * M * C,
+                   4.0 * M * C * (2 if pre is not None else 1) + 4.0 * (Ra + 2 * guard) * Cp)
+    return out
+
+
+def gemm_tn_x3_conv(a, b, Pw, out=None):
+    """weight gradient of a 3 x 3 convolution in one launch: out[N, 9 Ci] (+)= sum over the nine taps of a^T (b shifted by the tap's row offset).  a: Planes of the
+    zero-bordered output gradient [R, N]; b: Planes of the zero-bordered input image [R, Ci] from pad_nhwc_planes with its default guard rows (the kernel reads
+    Pw + 1 rows in front of and behind b); Pw = W + 2.  fp32 out, zero-filled when not given."""
+    if a.rows_alloc != b.rows_alloc:
+        raise P3Error("gemm_tn_x3_conv: operands must share the padded row count")
+    base = b.buf._base if b.buf._base is not None else b.buf
+    lead = (b.buf.data_ptr() - base.data_ptr()) // (base.stride(0) * 2)
+    if base.stride(0) != b.ld or lead < Pw + 1 or base.shape[0] - lead - b.rows_alloc < Pw + 1:
+        raise P3Error("gemm_tn_x3_conv: b needs Pw + 1 guard rows in front of and behind it (pad_nhwc_planes)")
+    M, N, Ci = a.rows_alloc, a.cols, b.cols
+    if out is None:
+        out = torch.zeros((N, 9 * Ci), dtype=torch.float32, device=a.buf.device)
+    slabs, ns = _tn_slabs(N, 9 * Ci, out)
+    ev = KTIMER.begin()
+    check(lib().p3_gemm_tn_x3_conv(ptr(a.hi), ptr(a.lo), a.ld, ptr(b.hi), ptr(b.lo), b.ld, ptr(out), out.stride(0), M, N, Ci, Pw, ptr(slabs), ns, stream()),
+          "p3_gemm_tn_x3_conv")
+    if ev is not None:
+        KTIMER.end(ev, (lib().p3_last_kernel().decode() or "gemm_tn_x3_wide_kernel<4>") + "/conv", 2.0 * a.rows * N * 9 * Ci, float(4 * a.rows * (N + Ci) + N * 9 * Ci * 4))
+    return out
+
+
+def col_stats(x, sums=None):
+    """[column sums | column sums of squares] of fp32 x [M, N] -> fp32 [2 N]; fixed summation order (the same bits on every run)"""
+    _dev(x)
+    M, N = x.shape
+    if sums is None:
+        sums = torch.empty(2 * N, dtype=torch.float32, device=x.device)
+    nfl = 1024 * 2 * N
+    ws = workspace(nfl * 4, x.device, "col_stats")
+    ev = KTIMER.begin()
+    check(lib().p3_col_stats(ptr(x), x.stride(0), M, N, ptr(sums), ptr(ws), nfl, stream()), "p3_col_stats")
+    if ev is not None:
+        KTIMER.end(ev, "col_stats_kernel", 3.0 * M * N, 4.0 * M * N)
+    return sums
 
 
 def layernorm_planes(x, gamma, beta, eps, out=None, save_stats=True):

@@ -348,6 +348,26 @@ def weight_planes(p, transpose=False):
     return pl.hi, pl.lo
 
 
+_derived_planes = {}       # (id(param), key) -> (param, re-laid-out fp32 source, its version, Planes): one buffer per layout, rewritten in place
+
+
+def derived_planes(p, key, fn):
+    """(hi, lo) planes of the re-laid-out fp32 copy shadow(p, float32, key, fn) of parameter p - the weight operand of a planes GEMM whose layout is not the
+    parameter's own (the 3 x 3 fusion convolution: [Co, (ky, kx, ci)] and the flipped transpose).  The split follows the copy: rebuilt when shadow() hands out a
+    new or rewritten copy (once per optimizer step: FlatAdamW.apply() invalidates the derived copies; optimizer-less: the parameter's version), never per
+    call, and always into the SAME buffer - a captured graph keeps its address, and the re-derivation it captured runs on every replay."""
+    src = shadow(p, torch.float32, key=key, fn=fn)
+    k = (id(p), key)
+    ver = (src._version, _epoch[0])
+    ent = _derived_planes.get(k)
+    if ent is not None and ent[0] is p and ent[1] is src and ent[2] == ver:
+        return ent[3].hi, ent[3].lo
+    keep = ent[3] if ent is not None and ent[0] is p and (ent[3].rows, ent[3].cols) == tuple(src.shape) else None
+    pl = hip.to_planes(src, out=keep, pad=1)
+    _derived_planes[k] = (p, src, ver, pl)
+    return pl.hi, pl.lo
+
+
 def wpl(p, transpose=False):
     """(hi, lo) of weight / derived weight tensor `p` for hip.gemm(w_planes=...) - the register-staged fp32x3 GEMM then copies the weight's planes instead of
     splitting the fp32 weight in every tile - or None outside an fp32x3 scope / for a non-fp32 or non-2-D tensor.  Callers slice the pair the way they slice the
@@ -383,6 +403,8 @@ def unregister(params):
         _registered.pop(i, None)
         _registered_T.pop(i, None)
         _registered_planes.pop(i, None)
+    for k in [k for k in _derived_planes if k[0] in ids]:
+        del _derived_planes[k]
     for k in [k for k in _planes_cache if k[0] in ids]:
         del _planes_cache[k]
     for k in [k for k in _shadow_cache if k[0] in ids]:
@@ -407,6 +429,7 @@ def reset_process_state():
     _registered_T.clear()
     _registered_planes.clear()
     _planes_cache.clear()
+    _derived_planes.clear()
     _shadow_cache.clear()
     _twins.clear()
     _stream.clear()
