@@ -937,7 +937,8 @@ int64_t p3_asm_plan_workspace_bytes(int64_t N, int64_t M);
  *   F  of the sequence q_0 .. q_{k-1}: e_i = q_{(i+1) mod k} - q_i, a_i = atan2(e.y, e.x) 180 / pi in float64, t_i = |a_i - a_{(i+1) mod k}|; vertex
  *      (i+1) mod k is kept when 10 < t_i < 350; output = the kept vertices in ascending index, then the first kept one once more.  Nothing kept: the
  *      region gives no polygon (flag bit 2; the reference raises there).
- * Inner rings are NOT built: a region with holes gets its outer polygon, flag bit 1 and hole_pixels, and is left to the host for its courtyards.
+ * p3_hisup_polygons: inner rings are NOT built: a region with holes gets its outer polygon, flag bit 1 and hole_pixels; p3_hisup_polygons_rings (below)
+ * builds them in the same call.
  * Outputs, polygons packed in the order (image, label): pos fp32 [max_vertices,2] (x, y; ring corners are integers, junctions bit copies of juncs); src
  * int32 [max_vertices] the ring index or junction index of each vertex; poly_slice int64 [B,max_regions,2] = [first, one past the last) in pos (empty
  * for a region without polygon and for labels past n_regions); poly_flags int32 [B,max_regions] bit 0 junction polygon, bit 1 hole_pixels > 0, bit 2 no
@@ -960,6 +961,54 @@ int p3_hisup_polygons(const int32_t* labels, const int32_t* n_regions, const int
                       int32_t* poly_flags, int32_t* hole_pixels, int32_t* n_vertices, int32_t* counts, int32_t* status, void* workspace,
                       void* stream);
 int64_t p3_hisup_polygons_workspace_bytes(int B, int H, int W, int max_regions, int max_vertices);
+
+/* ------------------------------------------------------------------------------------------
+ * HiSup polygons with their inner rings: the hole branch of `get_poly_crowdai` (models/hisup/polygon.py:95-109,152-154, `inn_c_to_poly_coco`) next to
+ * the outer polygons.  p3_hisup_polygons_rings takes the inputs of p3_hisup_polygons, writes its eight outputs with the same bits, and in the same call
+ * the ring of every hole of every region whose border encloses an area of at least 50.  Steps A to F are those above; for region (b, l) with pixel set M
+ * (everything else, other labels included, is background):
+ *   G  a hole is a 4-connected component of the background that step A leaves unfilled.  The holes of a region are numbered in raster order of their
+ *      first cell (x_h, y_h).  OpenCV's own order of sibling contours is NOT reproduced: this is the one deviation from the reference's output.
+ *   H  the hole border: the follower of step C on M (not on T) from p0 = (x_h - 1, y_h), a region pixel, with the start direction s = 0 in place of 4
+ *      (s = (s - 1) mod 8 until the neighbour p1 is set); the loop and the stop condition are unchanged.  This is Suzuki and Abe's hole border for
+ *      8-connected foreground, it cuts corners diagonally.  a2 = |sum (x_i y_{i+1} - x_{i+1} y_i)| over the cyclic border; the hole gives a ring iff
+ *      a2 >= 100 (area >= 50), decided in integers.  A 6 x 7 rectangular hole has area 54, 6 x 6 has 47, 3 x 3 has 14.
+ *   I  K = the border's cells and every cell that no 4-connected path avoiding them joins to the outside of the box (the flood of step A; it stands for
+ *      drawContours(thickness = -1)).  K' = K without the cells of its lowest row index and of its lowest column index.  K' holds the whole hole and
+ *      otherwise border pixels 8-adjacent to it, so it is one 8-connected component.  The ring: the outer border of K' by step C as it stands (first set
+ *      cell, s = 4), the point sequence REVERSED, then step D on the reversed cyclic sequence.  No corner grid: the coordinates are K''s pixel coordinates.
+ *   E and F as above on that ring.  A ring in which nothing is kept gets ring flag bit 2 and no vertices.
+ * Further arguments: max_rings, max_ring_vertices.  Further outputs, rings in (image, label, hole) order: ring_pos fp32 [max_ring_vertices,2] and ring_src
+ * int32 [max_ring_vertices], closed rings as pos / src; ring_slice int64 [max_rings,2] = [first, one past the last) in ring_pos; ring_region int32
+ * [max_rings] = b max_regions + l - 1; ring_flags int32 [max_rings] bit 0 junction ring, bit 2 nothing kept; ring_area2 int32 [max_rings] the a2 of step
+ * H; region_rings int32 [B,max_regions,2] = [first, one past the last) ring of the region; n_holes int32 [B,max_regions] all holes, kept or not;
+ * ring_counts int32 [3] = (rings, ring vertices, vertices of the longest ring).  status, further bits: bit 3 = more rings than max_rings: region_rings,
+ * n_holes and ring_counts hold the true values, no other ring output is written; bit 4 = more ring vertices than max_ring_vertices: all of them hold the
+ * true values, ring_pos and ring_src are left untouched.  Nothing is written past a capacity.  Bit 1 covers an inner ring past the bound as well.
+ * Ring bound: the kept rings of an image number at most floor(H W / 50), because the border polygons of distinct holes have disjoint interiors of area
+ * >= 50 each.  A ring has m <= 2 c(K') points as above, c = the sides of K' that face the outside.  Cutting the first row (column) takes away the upper
+ * (left) sides of its cells and lays open at most as many below (right of) them: c(K') <= c(K).  K is the hole grown by its 4-neighbours and filled, and
+ * its outline is the hole's outer outline moved outwards by one pixel: every side of the hole has one parallel side of K, a convex corner adds two sides,
+ * a concave one takes two away, and a rectilinear outline has four more convex corners than concave ones; where the moved outline meets itself sides
+ * only drop out.  So c(K) <= p + 8 with p the sides between the hole and M, and m <= 2 p + 16.  A pixel side lies between one region and one hole, and
+ * no side on the image border faces a hole, so the p of an image add up to at most H (W-1) + W (H-1), and one ring stays below the single-region bound
+ * 2 (H (W+1) + W (H+1)) + 8 the workspace slabs are sized for.  A ring has at most m + 1 vertices:
+ * max_rings = max(1, B floor(H W / 50)) and max_ring_vertices = B (2 (H (W-1) + W (H-1)) + 17 floor(H W / 50)), at least 1, can never overflow.
+ * Execution: as above, one workgroup per region in either form; after the outer polygon is staged the holes are taken one after another (seed by an
+ * integer atomicMin over the cells still unfilled, flood, border walk of one lane) with K / K' in the bitmap of T and the ring in the ring buffer, so the
+ * first form keeps its static LDS.  A region one of whose rings does not fit the 5120 LDS ring points goes on in the second form from that hole.  Six
+ * launches whatever the data; no host synchronisation; two runs, either form, an image alone or inside a batch give the same bits.  B == 0 or
+ * max_regions == 0: returns 0 without a launch.  workspace: p3_hisup_polygons_rings_workspace_bytes(B, H, W, max_regions, max_vertices, max_rings,
+ * max_ring_vertices) bytes.  Hand values (no junctions, (x, y)): a 15 x 14 block at rows 2..15, cols 3..17 with a hole at rows 4..9, cols 5..11: area 54,
+ * ring [[12,4],[12,10],[5,10],[5,4],[12,4]] from 26 ring points; two 8-row holes at cols 4..11 and 13..21 with the one-pixel wall at col 12 between them:
+ * areas 79 and 88, rings [[12,4],[12,12],[4,12],[4,4],[12,4]] and [[22,4],[22,12],[13,12],[13,4],[22,4]].
+ * ------------------------------------------------------------------------------------------ */
+int p3_hisup_polygons_rings(const int32_t* labels, const int32_t* n_regions, const int32_t* bbox, const float* juncs, const int32_t* junc_counts, int B,
+                            int H, int W, int max_regions, int max_vertices, int max_rings, int max_ring_vertices, int force_fallback, float* pos,
+                            int32_t* src, int64_t* poly_slice, int32_t* poly_flags, int32_t* hole_pixels, int32_t* n_vertices, int32_t* counts,
+                            float* ring_pos, int32_t* ring_src, int64_t* ring_slice, int32_t* ring_region, int32_t* ring_flags, int32_t* ring_area2,
+                            int32_t* region_rings, int32_t* n_holes, int32_t* ring_counts, int32_t* status, void* workspace, void* stream);
+int64_t p3_hisup_polygons_rings_workspace_bytes(int B, int H, int W, int max_regions, int max_vertices, int max_rings, int max_ring_vertices);
 
 #ifdef __cplusplus
 }

@@ -1226,6 +1226,77 @@ def hisup_polygons_checked(out, who="hisup_polygons"):
                                  (2, "a region's ring is longer than the bound the workspace is sized for (include/p3hip.h)")), dict(pos=0, src=0))
 
 
+def hisup_polygon_rings_capacity(B, H, W, max_regions):
+    """(max_vertices, max_rings, max_ring_vertices) that can never overflow (include/p3hip.h, the ring bounds of p3_hisup_polygons_rings)"""
+    q = (H * W) // 50
+    return hisup_polygons_capacity(B, H, W, max_regions), max(1, B * q), max(1, B * (2 * (H * (W - 1) + W * (H - 1)) + 17 * q))
+
+
+def hisup_polygon_rings_device(labels, n_regions, bbox, juncs, junc_counts, max_vertices=None, max_rings=None, max_ring_vertices=None, force_fallback=False,
+                               out=None):
+    """p3_hisup_polygons_rings (models/hisup/polygon.py `get_poly_crowdai` with its hole branch `inn_c_to_poly_coco`) without any
+    synchronisation.  Inputs and the first seven outputs as hisup_polygons_device, with the same bits.  Further outputs, rings in (image, label, hole) order:
+    ring_pos f32 [max_ring_vertices,2], ring_src i32 [max_ring_vertices], ring_slice i64 [max_rings,2], ring_region i32 [max_rings] (b R + l - 1),
+    ring_flags i32 [max_rings] (bit 0 junction ring, bit 2 nothing kept), ring_area2 i32 [max_rings] (twice the area of the hole border), region_rings
+    i32 [B,R,2], n_holes i32 [B,R], ring_counts i32 [3] = (rings, ring vertices, longest ring); status i32 [1]: bits 0 to 2 as hisup_polygons_device, bit 3
+    max_rings was too small, bit 4 max_ring_vertices was too small (the counts are the true totals then).  The default capacities cannot overflow.
+    out: the caller's own tensors for any of the outputs (`_outputs`)."""
+    if labels.dim() != 3 or labels.dtype != torch.int32 or min(labels.shape) < 1:
+        raise P3Error(f"hisup_polygon_rings: labels int32 [B, H, W] expected, got {labels.dtype} {tuple(labels.shape)}")
+    B, H, W = labels.shape
+    if bbox.dim() != 3 or bbox.shape[0] != B or bbox.shape[2] != 4 or bbox.shape[1] < 1 or bbox.dtype != torch.int32 or tuple(n_regions.shape) != (B,) \
+            or n_regions.dtype != torch.int32:
+        raise P3Error(f"hisup_polygon_rings: n_regions int32 [{B}] and bbox int32 [{B}, R, 4] expected, got {tuple(n_regions.shape)}, {tuple(bbox.shape)}")
+    if tuple(juncs.shape) != (B, 2 * HISUP_TOPK, 2) or juncs.dtype != torch.float32 or tuple(junc_counts.shape) != (B, 2) or junc_counts.dtype != torch.int32:
+        raise P3Error(f"hisup_polygon_rings: juncs float32 [{B}, {2 * HISUP_TOPK}, 2] and junc_counts int32 [{B}, 2] expected, got {tuple(juncs.shape)}, "
+                      f"{tuple(junc_counts.shape)}")
+    if H > HISUP_MAX_EDGE or W > HISUP_MAX_EDGE or H * W > HISUP_MAX_HW:
+        raise P3Error(f"hisup_polygon_rings: {H} x {W} is beyond the {HISUP_MAX_EDGE} pixels per edge / {HISUP_MAX_HW} pixels per map the kernel supports")
+    R = bbox.shape[1]
+    cap = hisup_polygon_rings_capacity(B, H, W, R)
+    nv, nr_, nrv = (c if v is None else int(v) for c, v in zip(cap, (max_vertices, max_rings, max_ring_vertices)))
+    for k, v in (("max_vertices", nv), ("max_rings", nr_), ("max_ring_vertices", nrv)):
+        if v < 1 or v >= 1 << 31:
+            raise P3Error(f"hisup_polygon_rings: {k} = {v}")
+    for t in (labels, n_regions, bbox, juncs, junc_counts):
+        _dev(t)
+    dev, i32, f32, i64 = labels.device, torch.int32, torch.float32, torch.int64
+    out = _outputs("hisup_polygon_rings", dev, (("pos", (nv, 2), f32), ("src", (nv,), i32), ("poly_slice", (B, R, 2), i64), ("poly_flags", (B, R), i32),
+                                                ("hole_pixels", (B, R), i32), ("n_vertices", (B,), i32), ("counts", (2,), i32), ("ring_pos", (nrv, 2), f32),
+                                                ("ring_src", (nrv,), i32), ("ring_slice", (nr_, 2), i64), ("ring_region", (nr_,), i32),
+                                                ("ring_flags", (nr_,), i32), ("ring_area2", (nr_,), i32), ("region_rings", (B, R, 2), i32),
+                                                ("n_holes", (B, R), i32), ("ring_counts", (3,), i32), ("status", (1,), i32)), out)
+    lab, nr, bb, jc, cn = labels.contiguous(), n_regions.contiguous(), bbox.contiguous(), juncs.contiguous(), junc_counts.contiguous()
+    ws = workspace(int(lib().p3_hisup_polygons_rings_workspace_bytes(B, H, W, R, nv, nr_, nrv)), dev, "hisup_polygon_rings")
+    check(lib().p3_hisup_polygons_rings(ptr(lab), ptr(nr), ptr(bb), ptr(jc), ptr(cn), B, H, W, R, nv, nr_, nrv, int(bool(force_fallback)),
+                                        *(ptr(out[k]) for k in ("pos", "src", "poly_slice", "poly_flags", "hole_pixels", "n_vertices", "counts", "ring_pos",
+                                                                "ring_src", "ring_slice", "ring_region", "ring_flags", "ring_area2", "region_rings", "n_holes",
+                                                                "ring_counts", "status")), ptr(ws), stream()), "p3_hisup_polygons_rings")
+    return out
+
+
+def hisup_polygon_rings(labels, n_regions, bbox, juncs, junc_counts, max_vertices=None, max_rings=None, max_ring_vertices=None, force_fallback=False):
+    """the checking form of hisup_polygon_rings_device: reads the counts and status once (the only read-back), raises on any status bit and narrows pos / src
+    to the vertices, ring_pos / ring_src to the ring vertices and the per-ring outputs to the rings found; counts = (vertices, longest polygon) and
+    ring_counts = (rings, ring vertices, longest ring) as Python ints."""
+    return hisup_polygon_rings_checked(hisup_polygon_rings_device(labels, n_regions, bbox, juncs, junc_counts, max_vertices, max_rings, max_ring_vertices,
+                                                                  force_fallback))
+
+
+def hisup_polygon_rings_checked(out, who="hisup_polygon_rings"):
+    """the one read-back of counts, ring_counts and status of a hisup_polygon_rings_device result"""
+    res = dict(out)
+    res["counts"] = torch.cat([out["counts"], out["ring_counts"]])
+    res = _read_back(res, who, ((1, lambda V, *_: f"{V} vertices do not fit max_vertices = {out['pos'].shape[0]}"),
+                                (8, lambda V, L, Q, *_: f"{Q} rings do not fit max_rings = {out['ring_region'].shape[0]}"),
+                                (16, lambda V, L, Q, RV, _: f"{RV} ring vertices do not fit max_ring_vertices = {out['ring_pos'].shape[0]}"),
+                                (4, "P3_HISUP_POLY_STOP is set: the run was cut short for a measurement and has no result"),
+                                (2, "a ring is longer than the bound the workspace is sized for (include/p3hip.h)")),
+                     dict(pos=0, src=0, ring_pos=3, ring_src=3, ring_slice=2, ring_region=2, ring_flags=2, ring_area2=2))
+    res["counts"], res["ring_counts"] = res["counts"][:2], res["counts"][2:]
+    return res
+
+
 # ------------------------------------------------------------------------------------------ FFL active-contour polygon optimiser
 ACM_LDS_CAP = 4096          # csrc/acm.hip: vertices of one polygon that fit the one-launch LDS path
 

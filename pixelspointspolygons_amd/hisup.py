@@ -14,6 +14,7 @@ The whole model for inference (second half of this file): `HiSupModel` (the refe
 """
 import math
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -245,7 +246,7 @@ class EncoderDecoder(HiSupHeads):
     """model_hisup.py:122-308, inference: encoder + head set (`HiSupHeads` is the base class, so the state_dict is the reference's: `encoder.*`
     and the head keys at the top level) + what `forward_val` does after the heads, on the device: validation losses (p3_hisup_val_loss),
     junctions (p3_hisup_junctions), building regions (p3_hisup_regions) and, with polygons=True, the outer polygon of every region (p3_hisup_polygons,
-    `get_poly_crowdai`).  Inner rings of regions with holes stay host code of the reference (OpenCV contours), see INTEGRATION.md."""
+    `get_poly_crowdai`), with inner_rings=True also the inner rings of its holes (p3_hisup_polygons_rings); see INTEGRATION.md for the order of sibling holes."""
 
     def __init__(self, cfg, encoder, max_regions=1024):
         super().__init__(cfg)
@@ -289,11 +290,12 @@ class EncoderDecoder(HiSupHeads):
         return targets, HiSupHeads.forward(self, features)
 
     @torch.no_grad()
-    def forward_val_device(self, x_images, x_lidar, y=None, polygons=False):
+    def forward_val_device(self, x_images, x_lidar, y=None, polygons=False, inner_rings=False):
         """`forward_val` without any host synchronisation: -> (output, loss_dict) of device tensors.  output: juncs [B,600,2], junc_scores [B,600],
         junc_index [B,600], junc_counts [B,2] (hip.hisup_junctions), mask [B,H,W], regions = dict(labels, n_regions, area, bbox, score, status)
         (hip.hisup_regions_device; status[b] = 1: more than max_regions regions in image b) and `heads`, the five NCHW maps.  polygons=True adds
-        output["polygons"], the dict of hip.hisup_polygons_device (outer polygons; a region with holes is flagged, its inner rings are not built)."""
+        output["polygons"], the dict of hip.hisup_polygons_device (outer polygons; a region with holes is flagged, its inner rings are not built) or, with
+        inner_rings=True, the dict of hip.hisup_polygon_rings_device (the same outer polygons and the rings of the holes)."""
         targets, heads = self.forward_common(x_images, x_lidar, y)
         B, _, H, W = heads["joff"].shape
         assert H == self.pred_height and W == self.pred_width
@@ -311,18 +313,22 @@ class EncoderDecoder(HiSupHeads):
         output = {"juncs": juncs, "junc_scores": scores, "junc_index": index, "junc_counts": counts, "mask": reg.pop("mask"), "regions": reg,
                   "heads": heads}
         if polygons:
-            output["polygons"] = hip.hisup_polygons_device(reg["labels"], reg["n_regions"], reg["bbox"], juncs, counts)
+            build = hip.hisup_polygon_rings_device if inner_rings else hip.hisup_polygons_device
+            output["polygons"] = build(reg["labels"], reg["n_regions"], reg["bbox"], juncs, counts)
         return output, loss_dict
 
     @torch.no_grad()
-    def forward_val(self, x_images, x_lidar, y=None, polygons=False):
+    def forward_val(self, x_images, x_lidar, y=None, polygons=False, inner_rings=False):
         """model_hisup.py:229-293: -> (output, loss_dict).  output["juncs_pred"]: list of [n, 2] fp32 numpy arrays (x, y), class 2 first;
         output["mask_pred"]: list of [H, W] fp32 numpy arrays; output["regions"]: per image dict(labels int32 [H, W], area int32 [n], bbox int32 [n, 4],
         score fp32 [n]).  One device-to-host copy per kind.  polygons=True adds the reference's `polys_pred` (per image a list of closed float64 [k+1, 2]
         arrays (x, y), one per region that has a polygon, in label order) and `scores` (per image the matching regions' scores), and `poly_flags` (per image
         int32 [n]: bit 0 junction polygon, bit 1 the region has holes, bit 2 no polygon).  Only OUTER polygons are built: for a region with bit 1 the
-        reference may add inner rings, see INTEGRATION.md for the host hand-over."""
-        out, loss_dict = self.forward_val_device(x_images, x_lidar, y, polygons=polygons)
+        reference may add inner rings.  polygons=True with inner_rings=True builds them too: `polys_pred[b][i]` is what `get_poly_crowdai` returns, the outer
+        polygon followed by the region's kept rings (those of holes with a border area of at least 50, in raster order of the holes' first cells), each
+        closed, in one float64 [k, 2] array, and `poly_parts[b][i]` lists the length of each part (the reference's `edge_index`).  A ring in which the
+        simplification keeps nothing is left out."""
+        out, loss_dict = self.forward_val_device(x_images, x_lidar, y, polygons=polygons, inner_rings=inner_rings)
         reg = out["regions"]
         status, n_reg = reg["status"].cpu().numpy(), reg["n_regions"].cpu().numpy()
         if status.any():
@@ -335,9 +341,20 @@ class EncoderDecoder(HiSupHeads):
                   "regions": [{"labels": labels[b], "area": area[b, :n_reg[b]].copy(), "bbox": bbox[b, :n_reg[b]].copy(),
                                "score": score[b, :n_reg[b]].copy()} for b in range(B)]}
         if polygons:
-            pg = hip.hisup_polygons_checked(dict(out["polygons"]), "forward_val(polygons=True)")
+            checked = hip.hisup_polygon_rings_checked if inner_rings else hip.hisup_polygons_checked
+            pg = checked(dict(out["polygons"]), "forward_val(polygons=True)")
             pos, sl, flags = pg["pos"].cpu().numpy().astype("float64"), pg["poly_slice"].cpu().numpy(), pg["poly_flags"].cpu().numpy()
             output["polys_pred"] = [[pos[sl[b, i, 0]:sl[b, i, 1]] for i in range(n_reg[b]) if not flags[b, i] & 4] for b in range(B)]
+            if inner_rings:
+                rpos, rsl = pg["ring_pos"].cpu().numpy().astype("float64"), pg["ring_slice"].cpu().numpy()
+                rflags, rr = pg["ring_flags"].cpu().numpy(), pg["region_rings"].cpu().numpy()
+                output["poly_parts"] = []
+                for b in range(B):
+                    regions = [i for i in range(n_reg[b]) if not flags[b, i] & 4]
+                    parts = [[poly] + [rpos[rsl[q, 0]:rsl[q, 1]] for q in range(rr[b, i, 0], rr[b, i, 1]) if not rflags[q] & 4]
+                             for poly, i in zip(output["polys_pred"][b], regions)]
+                    output["polys_pred"][b] = [np.concatenate(p) for p in parts]
+                    output["poly_parts"].append([[len(x) for x in p] for p in parts])
             output["scores"] = [score[b, :n_reg[b]][(flags[b, :n_reg[b]] & 4) == 0].copy() for b in range(B)]
             output["poly_flags"] = [flags[b, :n_reg[b]].copy() for b in range(B)]
         return output, loss_dict
