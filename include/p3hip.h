@@ -187,8 +187,6 @@ int p3_gemm_dma(const void* A, const void* W, void* C, const p3_gemm_desc* d, in
  * p3_gemm_x3:  C = epilogue(A W^T),  A = a_hi + a_lo [M, K], W = w_hi + w_lo [N, K]
  *   v = A W^T + bias;  act == P3_ACT_GELU: aux <- GELU'(v) (fp32 [M, N], ldaux), v <- GELU(v);  mul != NULL: v *= mul[m, n] (fp32, ldmul: the backward of
  *   that GELU);  residual != NULL: v += residual[m, n] (fp32, ldr);  then C <- v as fp32 (c, ldc; c_lo == NULL) or as planes (c = hi, c_lo = lo, ldc).
- *   Fused LayerNorm of the OUTPUT row (ln_gamma != NULL; needs N == 384 == the tile width, fp32 C): besides C the kernel writes LN(C) as planes (ln_hi, ln_lo,
- *   ldln) and the row statistics (ln_mean, ln_rstd) - the norm2 / next block's norm1 of timm's Block, whose separate pass re-read the 77 MB stream.
  * Shapes: K % 32 == 0, N % 8 == 0, 16-byte aligned rows.  Kernels: K = 256 / 384 with 1024 <= N <= 4096, N % 32 == 0 - the A-stationary persistent kernel
  * (gemm_x3_as.hip: the A rows of a wave live in registers, the weights stream through LDS, one workgroup per CU walks (row block, column block) units);
  * otherwise tiles of 128 x 128 (4 waves) or, for N == 384 and K >= 1024, 128 x 384 (8 waves).
@@ -203,14 +201,10 @@ typedef struct {
     int act;
     float* aux; int ldaux;
     const float* mul; int ldmul;
-    const float* ln_gamma; const float* ln_beta; float ln_eps;
-    void* ln_hi; void* ln_lo; int ldln;
-    float* ln_mean; float* ln_rstd;
     int tile;             /* 0: the library picks the kernel (measured rule); 1: the 128 x 128 tile kernel, 2: the 128 x 384 tile kernel, 3: the A-stationary kernel -
                            * for THIS call (the host splits a launch with a ragged last round of 128 x 384 tiles into a head on tile 2 and a remainder on tile 1);
                            * the process-wide p3_gemm_x3_tile hook is for measurement tools only and loses against this field */
-    /* 3 x 3 convolution as a GEMM over a zero-bordered planes image (conv_ci > 0; the two tile kernels only, P3_EUNSUP on the A-stationary one and with a fused
-     * LayerNorm): A is the image [conv_B, conv_H + 2, conv_W + 2, lda] (p3_pad_nhwc_planes), K = 9 * conv_ci, W is laid out [N, (ky, kx, ci)].  Output row m is
+    /* 3 x 3 convolution as a GEMM over a zero-bordered planes image (conv_ci > 0; the two tile kernels only, P3_EUNSUP on the A-stationary one): A is the image [conv_B, conv_H + 2, conv_W + 2, lda] (p3_pad_nhwc_planes), K = 9 * conv_ci, W is laid out [N, (ky, kx, ci)].  Output row m is
      * interior pixel (b, y, x) = unravel(conv_row0 + m) of the UNPADDED [conv_B, conv_H, conv_W] grid, its A row b P_h P_w + (y + 1) P_w + (x + 1) with
      * P_h = conv_H + 2, P_w = conv_W + 2; the 32-deep slice kt belongs to tap t = kt * 32 / conv_ci and reads A at row + (ky - 1) P_w + (kx - 1), column
      * kt * 32 - t * conv_ci: an interior row +- one pixel never leaves its own padded image.  conv_ci % 32 == 0.  conv_row0: first output pixel of this launch
@@ -221,9 +215,6 @@ int p3_gemm_x3(const p3_gemm_x3_desc* d, void* stream);
 /* measurement hook (tools/mb_x3.py, tools/mb_as.py): 0 = the library's rule, 1 = every product on the 128 x 128 tile, 2 = on the 128 x 384 tile, 3 = on the
  * A-stationary persistent kernel (csrc/gemm_x3_as.hip; P3_EUNSUP unless K = 256 / 384, N % 32 == 0, N <= 4096); returns the previous mode */
 int p3_gemm_x3_tile(int mode);
-/* measurement hook: device buffer [256][8][8] of 64-bit cycle sums written by the instrumented variants of the A-stationary kernel (environment P3_AS_VAR & 64);
- * NULL switches it off */
-int p3_gemm_x3_as_debug(void* buf);
 /* weight gradient from planes:  C[N, K] (+)= (a_hi + a_lo)[M, N]^T (b_hi + b_lo)[M, K]  (fp32 C, split over M: fp32 atomics, or - `slabs` given - partial
  * tiles + a fixed-order reduce like p3_gemm_tn_ex); colsum (optional, [N]) += column sums of A (the bias gradient).  M % 64 == 0, N % 128 == 0, K % 128 == 0. */
 int p3_gemm_tn_x3(const void* a_hi, const void* a_lo, int lda, const void* b_hi, const void* b_lo, int ldb, float* C, int ldc, int M, int N, int K,

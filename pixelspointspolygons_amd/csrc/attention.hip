@@ -544,11 +544,8 @@ extern "C" int p3_attention(const void* Q, const void* K, const void* V, void* O
         P3_LAUNCH_CHECK();
         return P3_OK;
     }
-    // fp32x3 at head dim 32: raw fp32 images of the K and V tile in dynamic LDS (2 x 8 KB, plus the diagnostic padding)
-    size_t dyn = d->dtype == P3_F32X3 && d->head_dim == 32 ? (size_t)2 * ATr<f32s, 32>::KT * 32 * 4 : 0;
-    static int pad_lds = -1;              // P3_ATTN_PAD_LDS=<bytes> (diagnostic): extra dynamic LDS per workgroup of the fp32x3 kernels - 40000 leaves ONE workgroup per CU
-    if (pad_lds < 0) { const char* e = getenv("P3_ATTN_PAD_LDS"); pad_lds = e ? atoi(e) : 0; }
-    if (d->dtype == P3_F32X3) dyn += (size_t)pad_lds;
+    // fp32x3 at head dim 32: raw fp32 images of the K and V tile in dynamic LDS (2 x 8 KB)
+    const size_t dyn = d->dtype == P3_F32X3 && d->head_dim == 32 ? (size_t)2 * ATr<f32s, 32>::KT * 32 * 4 : 0;
 #define P3_ATTN_FWD(T, D)                                                                                                  \
     (drop ? p3_launch<attn_fwd_kernel<T, D, true>>("attn_fwd_kernel<" #T ", " #D ", true>", grid, block, dyn, s, a)        \
           : p3_launch<attn_fwd_kernel<T, D, false>>("attn_fwd_kernel<" #T ", " #D ", false>", grid, block, dyn, s, a))

@@ -597,7 +597,7 @@ extern "C" int p3_gemm_tn_ex(const void* A, const void* B, float* C, int M, int 
     g.tiles_k = p3_ceil_div(K, TK);
     const int tiles = tiles_n * g.tiles_k;
     const int bm = dtype == P3_BF16 ? 64 : 16;
-    // M-split count (measured r01, tools/mb_tn.py sweep 512..2048): ~768 workgroups (1.5 x the 512 that fit the chip at 2 per CU)
+    // M-split count (measured r01, sweep 512..2048): ~768 workgroups (1.5 x the 512 that fit the chip at 2 per CU)
     // balances per-block prologue / atomic-epilogue overhead against tail imbalance: +8..13 % over 1024; exactly one full wave of
     // 512 blocks is better still when the tile count divides it (decoder linear1: 64 vs 82 us).  P3_TN_BLOCKS overrides for sweeps.
     // same-box sweep r01: 600 -> 60.1 ms, 700 -> 59.6, 768 -> 59.6, 850 -> 59.3, 950 -> 59.3; r03 (two-deep prefetch since r02, every split costs

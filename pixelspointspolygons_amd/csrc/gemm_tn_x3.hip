@@ -396,9 +396,7 @@ static int tn_x3_launch(const void* a_hi, const void* a_lo, int lda, const void*
     const int tiles_n = N / 128;
     // the wide tile (128 x 384, every wave on all rows) where K is a multiple of 384 and there are enough tiles for its split count to stay moderate
     // (p3_gemm_tn_x3_wide(0) switches it off: same-box A/B, tools/mb_x3.py)
-    static int env_wide = -1;                        // P3_TN_WIDE=0: same-box A/B of the step (bench.py --lean)
-    if (env_wide < 0) { const char* e = getenv("P3_TN_WIDE"); env_wide = (e && atoi(e) == 0) ? 0 : 1; }
-    const bool wide = g_tn_wide && env_wide && K % 384 == 0 && tiles_n * (K / 384) >= 8 && conv_ci % 384 == 0;       // conv: a column tile lies inside one tap
+    const bool wide = g_tn_wide && K % 384 == 0 && tiles_n * (K / 384) >= 8 && conv_ci % 384 == 0;       // conv: a column tile lies inside one tap
     g.tiles_k = wide ? K / 384 : K / 128;
     const int step_rows = wide ? TW_BM : TD_BM;
     const int tiles = tiles_n * g.tiles_k;

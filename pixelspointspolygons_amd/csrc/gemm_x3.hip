@@ -13,9 +13,8 @@
 // every ds_read_b128 lane group touches 16 distinct 16-byte bank groups).  Two slices in LDS, one in flight.
 //   128 x 128 tile, 4 waves (2 x 2), 64 KB of operands -> 2 workgroups / CU: the wide outputs (qkv 1152, fc1 / dX of fc2 1536);
 //   128 x 384 tile, 8 waves (2 x 4), 128 KB -> 1 workgroup / CU: the 384-column outputs (proj, fc2, dX of fc1 / qkv / proj) - the A panel is staged once,
-//     and the whole output row lies in one workgroup (the fused LayerNorm of the output row: ln_* of the descriptor).
+//     and the whole output row lies in one workgroup.
 #include <stdio.h>
-#include <stdlib.h>
 
 #include "p3_common.h"
 #include "gemm_x3_epi.h"
@@ -211,10 +210,11 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(X3Args g) {
 //   * one barrier per 32-deep slice, in the MIDDLE of the iteration (slice kt + 1 readable / slice kt's LDS image dead), vmcnt(0) there: the only DMA in
 //     flight is slice kt + 1, issued a whole iteration (36 MFMAs x 2 waves = 2304 pipe cycles) earlier.
 // 64-byte rows (slot = chunk ^ ((row >> 2) & 3) on the source address), two slices of 64 KB in LDS.  The tile serves every ViT product: N = 384 with the whole
-// output row in one workgroup (LN = true: LayerNorm of that row in the epilogue), N = 1152 / 1536 as 3 / 4 column tiles (consecutive workgroups = one A panel).
+// output row in one workgroup, N = 1152 / 1536 as 3 / 4 column tiles (consecutive workgroups = one A panel).  (r05 also built a three-pass LayerNorm of that
+// row into this epilogue; it measured slower than the separate launch - proj 86 -> 133 us, fc2 230 -> 281 us against 27 us - and is gone.)
 struct X3Frag { uint4 ah[2], al[2], bh[3], bl[3]; };
 
-template <bool LN, bool CONV>
+template <bool CONV>
 __global__ __launch_bounds__(512, 2) void gemm_x3_n384_kernel(X3Args g) {
     constexpr int CPR = 4, A_U4 = 128 * CPR, B_U4 = 384 * CPR, STAGE_U4 = 2 * A_U4 + 2 * B_U4;      // a_hi | a_lo | w_hi | w_lo = 64 KB
     extern __shared__ __attribute__((aligned(1024))) uint4 lds[];
@@ -341,131 +341,36 @@ __global__ __launch_bounds__(512, 2) void gemm_x3_n384_kernel(X3Args g) {
     }
     wait_vm_lgkm0<0>();
     __builtin_amdgcn_s_barrier();
-    // ---- epilogue: 32 x 32 blocks through a private fp32 image [32][36] (8 waves x 4.5 KB); LN: + row statistics [128 rows][4 column waves] behind the images
+    // ---- epilogue: 32 x 32 blocks through a private fp32 image [32][36] (8 waves x 4.5 KB)
     constexpr int EP = 36;
     float* st = reinterpret_cast<float*>(lds) + wave * (32 * EP);
-    float* rstat = reinterpret_cast<float*>(lds) + 8 * 32 * EP;            // [128][4]
     const int c8 = (lane & 3) * 8, rl0 = lane >> 2;
     const bool planes = d.c_lo != nullptr;
 
-    // value of (row block ib, column block j, pass) in row-chunk layout: acc -> image -> + bias -> GELU / mul / residual (the x3_epi8 arithmetic without its stores)
+    // value of (row block ib, column block j, pass) in row-chunk layout: acc -> image -> + bias -> GELU / mul / residual (x3_epi8)
     auto load_block = [&](int ib, int j) __attribute__((always_inline)) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) st[crow32(r, hi) * EP + l31] = acc[ib][j][r];
     };
-    if constexpr (!LN) {
 #pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const int col = tn * 384 + wc * 96 + j * 32 + c8;
-            float bias[8];
+    for (int j = 0; j < 3; ++j) {
+        const int col = tn * 384 + wc * 96 + j * 32 + c8;
+        float bias[8];
 #pragma unroll
-            for (int k = 0; k < 8; ++k) bias[k] = (d.bias && col + k < d.N) ? d.bias[col + k] : 0.f;
+        for (int k = 0; k < 8; ++k) bias[k] = (d.bias && col + k < d.N) ? d.bias[col + k] : 0.f;
 #pragma unroll
-            for (int ib = 0; ib < 2; ++ib) {
-                load_block(ib, j);
+        for (int ib = 0; ib < 2; ++ib) {
+            load_block(ib, j);
 #pragma unroll
-                for (int pass = 0; pass < 2; ++pass) {
-                    const int rl = pass * 16 + rl0;
-                    const int row = tm * 128 + wr * 64 + ib * 32 + rl;
-                    const float4 v0 = *reinterpret_cast<const float4*>(st + rl * EP + c8);
-                    const float4 v1 = *reinterpret_cast<const float4*>(st + rl * EP + c8 + 4);
-                    if (row >= d.M || col >= d.N) continue;
-                    float v[8] = {v0.x + bias[0], v0.y + bias[1], v0.z + bias[2], v0.w + bias[3], v1.x + bias[4], v1.y + bias[5], v1.z + bias[6], v1.w + bias[7]};
-                    if (planes) x3_epi8<true>(d, row, col, v); else x3_epi8<false>(d, row, col, v);
-                }
+            for (int pass = 0; pass < 2; ++pass) {
+                const int rl = pass * 16 + rl0;
+                const int row = tm * 128 + wr * 64 + ib * 32 + rl;
+                const float4 v0 = *reinterpret_cast<const float4*>(st + rl * EP + c8);
+                const float4 v1 = *reinterpret_cast<const float4*>(st + rl * EP + c8 + 4);
+                if (row >= d.M || col >= d.N) continue;
+                float v[8] = {v0.x + bias[0], v0.y + bias[1], v0.z + bias[2], v0.w + bias[3], v1.x + bias[4], v1.y + bias[5], v1.z + bias[6], v1.w + bias[7]};
+                if (planes) x3_epi8<true>(d, row, col, v); else x3_epi8<false>(d, row, col, v);
             }
-        }
-    } else {
-        // LN needs the full 384-wide row (host checks N == 384, fp32 C, no GELU / mul).  v = product + bias + residual.
-        // pass 0: store C, row sums -> mean; pass 1: sum of squared deviations -> rstd; pass 2: (v - mean) * rstd * gamma + beta as planes.
-        float mean_[2][2], rstd_[2][2];                // this lane's rows: [ib][pass]
-#pragma unroll
-        for (int phase = 0; phase < 3; ++phase) {
-            float part[2][2] = {{0.f, 0.f}, {0.f, 0.f}};
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const int col = wc * 96 + j * 32 + c8;
-                float bias[8], gam[8], bet[8];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) bias[k] = d.bias ? d.bias[col + k] : 0.f;
-                if (phase == 2) {
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) { gam[k] = d.ln_gamma[col + k]; bet[k] = d.ln_beta[col + k]; }
-                }
-#pragma unroll
-                for (int ib = 0; ib < 2; ++ib) {
-                    load_block(ib, j);
-#pragma unroll
-                    for (int pass = 0; pass < 2; ++pass) {
-                        const int rl = pass * 16 + rl0;
-                        const int row = tm * 128 + wr * 64 + ib * 32 + rl;
-                        const float4 v0 = *reinterpret_cast<const float4*>(st + rl * EP + c8);
-                        const float4 v1 = *reinterpret_cast<const float4*>(st + rl * EP + c8 + 4);
-                        if (row >= d.M) continue;
-                        float v[8] = {v0.x + bias[0], v0.y + bias[1], v0.z + bias[2], v0.w + bias[3], v1.x + bias[4], v1.y + bias[5], v1.z + bias[6], v1.w + bias[7]};
-                        if (d.residual) {
-                            const float* r = d.residual + (int64_t)row * d.ldr + col;
-                            const float4 r0 = *reinterpret_cast<const float4*>(r), r1 = *reinterpret_cast<const float4*>(r + 4);
-                            v[0] += r0.x; v[1] += r0.y; v[2] += r0.z; v[3] += r0.w; v[4] += r1.x; v[5] += r1.y; v[6] += r1.z; v[7] += r1.w;
-                        }
-                        if (phase == 0) {
-                            float* c = reinterpret_cast<float*>(d.c) + (int64_t)row * d.ldc + col;
-                            *reinterpret_cast<float4*>(c) = make_float4(v[0], v[1], v[2], v[3]);
-                            *reinterpret_cast<float4*>(c + 4) = make_float4(v[4], v[5], v[6], v[7]);
-                            part[ib][pass] += ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-                        } else if (phase == 1) {
-                            float s = 0.f;
-#pragma unroll
-                            for (int k = 0; k < 8; ++k) { const float dv = v[k] - mean_[ib][pass]; s = fmaf(dv, dv, s); }
-                            part[ib][pass] += s;
-                        } else {
-                            float y[8];
-#pragma unroll
-                            for (int k = 0; k < 8; ++k) y[k] = fmaf((v[k] - mean_[ib][pass]) * rstd_[ib][pass], gam[k], bet[k]);
-                            uint4 h, l;
-                            x3_split8(y, h, l);
-                            const int64_t lo_ = (int64_t)row * d.ldln + col;
-                            *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(d.ln_hi) + lo_) = h;
-                            *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(d.ln_lo) + lo_) = l;
-                        }
-                    }
-                }
-            }
-            if (phase < 2) {
-                // fold the 4 lanes of a row (lane & 3), then the 4 column waves through LDS
-#pragma unroll
-                for (int ib = 0; ib < 2; ++ib)
-#pragma unroll
-                    for (int pass = 0; pass < 2; ++pass) {
-                        float s = part[ib][pass];
-                        s += __shfl_xor(s, 1, 64);
-                        s += __shfl_xor(s, 2, 64);
-                        if ((lane & 3) == 0) rstat[(wr * 64 + ib * 32 + pass * 16 + rl0) * 4 + wc] = s;
-                    }
-                __syncthreads();
-#pragma unroll
-                for (int ib = 0; ib < 2; ++ib)
-#pragma unroll
-                    for (int pass = 0; pass < 2; ++pass) {
-                        const float4 q = *reinterpret_cast<const float4*>(rstat + (wr * 64 + ib * 32 + pass * 16 + rl0) * 4);
-                        const float tot = (q.x + q.y) + (q.z + q.w);
-                        if (phase == 0) mean_[ib][pass] = tot * (1.0f / 384.0f);
-                        else rstd_[ib][pass] = rsqrtf(tot * (1.0f / 384.0f) + d.ln_eps);
-                    }
-                __syncthreads();                       // rstat is rewritten by the next phase
-            }
-        }
-        if (wc == 0 && (lane & 3) == 0) {
-#pragma unroll
-            for (int ib = 0; ib < 2; ++ib)
-#pragma unroll
-                for (int pass = 0; pass < 2; ++pass) {
-                    const int row = tm * 128 + wr * 64 + ib * 32 + pass * 16 + rl0;
-                    if (row < d.M) {
-                        if (d.ln_mean) d.ln_mean[row] = mean_[ib][pass];
-                        if (d.ln_rstd) d.ln_rstd[row] = rstd_[ib][pass];
-                    }
-                }
         }
     }
 }
@@ -531,18 +436,13 @@ extern "C" int p3_gemm_x3(const p3_gemm_x3_desc* d, void* stream) {
     P3_CHECK(!d->mul || (d->ldmul % 4 == 0 && (uintptr_t)d->mul % 16 == 0), P3_EALIGN, "p3_gemm_x3: mul alignment");
     P3_CHECK(d->act == P3_ACT_NONE || d->act == P3_ACT_GELU, P3_EUNSUP, "p3_gemm_x3: act NONE or GELU");
     P3_CHECK((d->conv_ci != 0 || (int64_t)d->M * d->lda * 2 < (1ll << 31)) && (int64_t)d->N * d->ldb * 2 < (1ll << 31), P3_EUNSUP, "p3_gemm_x3: operand larger than the 32-bit DMA offsets");
-    const bool ln = d->ln_gamma != nullptr;
     const bool conv = d->conv_ci != 0;
     if (conv) {
         P3_CHECK(d->conv_ci > 0 && d->conv_ci % 32 == 0 && d->K == 9 * d->conv_ci, P3_ESHAPE, "p3_gemm_x3: conv needs conv_ci % 32 == 0 and K == 9 * conv_ci");
         P3_CHECK(d->conv_B > 0 && d->conv_H > 0 && d->conv_W > 0 && d->conv_row0 >= 0 && d->lda >= d->conv_ci, P3_EINVAL, "p3_gemm_x3: conv_B / conv_H / conv_W / conv_row0");
         P3_CHECK((int64_t)d->conv_row0 + d->M <= (int64_t)d->conv_B * d->conv_H * d->conv_W, P3_ESHAPE, "p3_gemm_x3: conv_row0 + M beyond the conv_B * conv_H * conv_W output pixels");
         P3_CHECK((int64_t)d->conv_B * (d->conv_H + 2) * (d->conv_W + 2) * d->lda * 2 < (1ll << 31), P3_EUNSUP, "p3_gemm_x3: padded image larger than the 32-bit DMA offsets");
-        P3_CHECK(!ln && d->tile != 3, P3_EUNSUP, "p3_gemm_x3: the conv addressing is built into the two tile kernels only (no fused LayerNorm, no A-stationary kernel)");
-    }
-    if (ln) {
-        P3_CHECK(d->N == 384 && !planes && d->act == P3_ACT_NONE && !d->mul, P3_EUNSUP, "p3_gemm_x3: fused LayerNorm needs N == 384, fp32 C, no activation");
-        P3_CHECK(d->ln_beta && d->ln_hi && d->ln_lo && d->ldln % 8 == 0 && ((uintptr_t)d->ln_hi | (uintptr_t)d->ln_lo) % 16 == 0, P3_EINVAL, "p3_gemm_x3: ln_* arguments");
+        P3_CHECK(d->tile != 3, P3_EUNSUP, "p3_gemm_x3: the conv addressing is built into the two tile kernels only (no A-stationary kernel)");
     }
     X3Args g;
     g.d = *d;
@@ -552,25 +452,21 @@ extern "C" int p3_gemm_x3(const p3_gemm_x3_desc* d, void* stream) {
     // K = 256 / 384 with a 32-column-block output: the A-stationary persistent kernel (p3_gemm_x3_tile(3) asks for it explicitly, (1) / (2) keep the tile kernels)
     // default rule (tools/mb_as.py, profiles/r06_mb_as.txt): the wide outputs - qkv 1152, fc1 / dX of fc2 1536, the decoder's linear1 2048 - where a
     // workgroup walks >= 28 units per A slice; the 384- / 256- / 768-wide ones stay on the tile kernels (their 9 - 12 units per workgroup do not pay the slice load)
-    static int as_on = -1;                            // P3_X3_AS=0: same-box A/B of the step without the A-stationary kernel (bench.py --lean)
-    if (as_on < 0) { const char* e = getenv("P3_X3_AS"); as_on = (e && atoi(e) == 0) ? 0 : 1; }
     // the kernel of THIS call: p3_gemm_x3_desc.tile (1 / 2 / 3; the host's ragged-round split uses it) before the process-wide measurement hook p3_gemm_x3_tile before
     // the measured rule
     P3_CHECK(d->tile >= 0 && d->tile <= 3, P3_EINVAL, "p3_gemm_x3: tile must be 0 (the library's choice), 1 (128 x 128), 2 (128 x 384) or 3 (A-stationary)");
     const int tile = d->tile ? d->tile : g_x3_tile;
-    if (((tile == 0 && as_on && p3_gemm_x3_as_default(d)) || tile == 3) && p3_gemm_x3_as_ok(d)) return p3_gemm_x3_as(d, s);
-    P3_CHECK(tile != 3, P3_EUNSUP, "p3_gemm_x3: the A-stationary kernel needs K = 256 / 384, N % 32 == 0, N <= 4096, an epilogue it builds, no fused LayerNorm");
+    if (((tile == 0 && p3_gemm_x3_as_default(d)) || tile == 3) && p3_gemm_x3_as_ok(d)) return p3_gemm_x3_as(d, s);
+    P3_CHECK(tile != 3, P3_EUNSUP, "p3_gemm_x3: the A-stationary kernel needs K = 256 / 384, N % 32 == 0, N <= 4096, an epilogue it builds");
     // tile choice: 1 forces the 128 x 128 kernel, 2 the 128 x 384 kernel, 0 the measured rule (tools/mb_x3.py, profiles/r05_mb_x3.txt)
     const bool big = tile == 2 ? d->N > 128 : (tile == 1 ? false : x3_big_tile(d));
-    if (ln || big) {
+    if (big) {
         g.tiles_n = p3_ceil_div(d->N, 384);
         constexpr size_t LDS = 2 * (2 * 128 * 4 + 2 * 384 * 4) * 16;          // 2 slices x 64 KB
         const dim3 grid(g.tiles_m * g.tiles_n), block(512);
-        if (conv) return p3_launch<gemm_x3_n384_kernel<false, true>>("gemm_x3_n384_conv_kernel", grid, block, LDS, s, g);
-        return !ln ? p3_launch<gemm_x3_n384_kernel<false, false>>("gemm_x3_n384_kernel<false>", grid, block, LDS, s, g)
-                   : p3_launch<gemm_x3_n384_kernel<true, false>>("gemm_x3_n384_kernel<true>", grid, block, LDS, s, g);
+        if (conv) return p3_launch<gemm_x3_n384_kernel<true>>("gemm_x3_n384_conv_kernel", grid, block, LDS, s, g);
+        return p3_launch<gemm_x3_n384_kernel<false>>("gemm_x3_n384_kernel<false>", grid, block, LDS, s, g);
     }
-    P3_CHECK(!ln, P3_EUNSUP, "p3_gemm_x3: fused LayerNorm needs N == 384");
     g.tiles_n = p3_ceil_div(d->N, 128);
     if (p3_tracing()) p3_note_kernel(conv ? (planes ? "gemm_x3_conv_kernel<true>" : "gemm_x3_conv_kernel<false>") : (planes ? "gemm_x3_kernel<true>" : "gemm_x3_kernel<false>"));
     dim3 grid(g.tiles_m * g.tiles_n), block(256);

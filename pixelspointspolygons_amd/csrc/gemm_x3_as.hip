@@ -27,7 +27,6 @@
 //   * unit -> (row block, column block) is kept incrementally (no division in the loop).
 // MFMA order per 16-deep step: w_lo a_hi, w_hi a_lo, w_hi a_hi (small terms first), ascending k - one accumulator per wave, the partner's MFMAs in between.
 #include <stdio.h>
-#include <stdlib.h>
 
 #include "p3_common.h"
 #include "gemm_x3_epi.h"
@@ -38,21 +37,19 @@ struct AsArgs {
     p3_gemm_x3_desc d;
     int CB;              // column blocks of 32
     int units;           // row blocks x CB
-    unsigned long long* dbg;   // DBG: [workgroup][wave][8] cycle sums (barrier wait, epilogue, DMA issue, A reload, half 0, half 1, total, ticks)
 };
 
 typedef uint32_t as_u32x4 __attribute__((ext_vector_type(4)));
 
-// 16- / 8-byte stores at wave-uniform base + 32-bit byte offset; SC1: write-through (the line is not kept in this XCD's L2, where the weight stream lives)
+// 16- / 8-byte stores at wave-uniform base + 32-bit byte offset, write-through (sc1): the output lines do not stay in this XCD's L2, where the weight stream
+// lives (r06 same-box A/B against plain stores, profiles/r06_mb_as.txt: qkv 161 -> 151 us, fc1 279 -> 271)
 typedef float as_f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t as_u32x2 __attribute__((ext_vector_type(2)));
-template <bool SC1> __device__ __forceinline__ void as_store16(void* base, uint32_t off, as_f32x4 v) {
-    if constexpr (SC1) asm volatile("global_store_dwordx4 %0, %1, %2 sc1\n\ts_nop 1" :: "v"(off), "v"(v), "s"(base) : "memory");
-    else *reinterpret_cast<as_f32x4*>(reinterpret_cast<char*>(base) + (size_t)off) = v;
+__device__ __forceinline__ void as_store16(void* base, uint32_t off, as_f32x4 v) {
+    asm volatile("global_store_dwordx4 %0, %1, %2 sc1\n\ts_nop 1" :: "v"(off), "v"(v), "s"(base) : "memory");
 }
-template <bool SC1> __device__ __forceinline__ void as_store8(void* base, uint32_t off, as_u32x2 v) {
-    if constexpr (SC1) asm volatile("global_store_dwordx2 %0, %1, %2 sc1\n\ts_nop 1" :: "v"(off), "v"(v), "s"(base) : "memory");
-    else *reinterpret_cast<as_u32x2*>(reinterpret_cast<char*>(base) + (size_t)off) = v;
+__device__ __forceinline__ void as_store8(void* base, uint32_t off, as_u32x2 v) {
+    asm volatile("global_store_dwordx2 %0, %1, %2 sc1\n\ts_nop 1" :: "v"(off), "v"(v), "s"(base) : "memory");
 }
 
 // The lane id again, opaque to the optimiser: what the epilogue and the A reload derive from it (row, column chunk, pointers) is computed where it is used
@@ -64,15 +61,13 @@ __device__ __forceinline__ int as_lane() {
 }
 
 constexpr int AS_PLANES = 1, AS_GELU = 2, AS_MUL = 4, AS_RES = 8;      // EPI bits (bias and aux stay run-time switches: wave-uniform, cheap)
-constexpr int AS_NOEPI = 16, AS_NODMA = 32, AS_FOLD = 64;             // measurement: no epilogue / no weight stream / every row block's epilogue traffic folded
-                                                                      // onto rows 0..255 (cache-resident) - tools/mb_as.py; wrong results, timing only
-constexpr int AS_SC1 = 128;                                           // write-through (sc1) epilogue stores: the output lines do not stay in the XCD's L2, where the weight
-                                                                      // stream lives (r06 same-box A/B, profiles/r06_mb_as.txt: qkv 161 -> 151 us, fc1 279 -> 271); var 5 = plain
-constexpr int AS_NOPRIO = 256;                                        // measurement: the finisher's MFMAs at normal priority
+constexpr int AS_SC1 = 128;                                           // set in every instantiation (the stores are write-through) and tested nowhere: it is part of the
+                                                                      // kernel's NAME, by which bench.py finds the committed PMC tables
 constexpr int AS_SLOTS = 5;                                           // half blocks in the LDS ring (120 KB at K = 384; + bias, junk, 18 KB of epilogue images)
 
 // KS = K / 16 (24: K = 384, 16: K = 256); EPI: which epilogue streams exist (compile-time: the register budget has no room for the union of their operands)
-template <int KS, int EPI, bool DBG>
+// (the third parameter, always false, was the instrumented twin of r06: it stays in the signature for the same reason as AS_SC1)
+template <int KS, int EPI, bool>
 __global__ __launch_bounds__(512, 2) void gemm_x3_as_kernel(AsArgs g) {
     constexpr int HS = KS / 2;                  // 16-deep steps per half block
     constexpr int GH = HS / 4;                  // 64-deep groups per half block
@@ -273,10 +268,6 @@ __global__ __launch_bounds__(512, 2) void gemm_x3_as_kernel(AsArgs g) {
     // Row-major, 8 lanes cover 128 contiguous bytes of a row.
     float* stage = reinterpret_cast<float*>(lds + AS_SLOTS * HALF_B + d.N * 4 + 8 * 256) + wave * (16 * 36);
     auto epi_half = [&](int pr, int rb, int cb) __attribute__((always_inline)) {      // pr is a compile-time constant at both call sites
-        if constexpr ((EPI & AS_NOEPI) != 0) {
-            asm volatile("" :: "v"(acc[0][pr]), "v"(acc[1][pr]));
-            return;
-        }
         const int ln = as_lane();
         {
             float v[8];
@@ -291,7 +282,7 @@ __global__ __launch_bounds__(512, 2) void gemm_x3_as_kernel(AsArgs g) {
             *reinterpret_cast<float4*>(wp + 4) = make_float4(v[4], v[5], v[6], v[7]);
         }
         const uint32_t col = (uint32_t)(cb * 32 + (ln & 7) * 4);
-        const uint32_t urow0 = (uint32_t)(((EPI & AS_FOLD) ? 0 : rb * 256) + wave * 32 + 16 * pr + (ln >> 3));       // pass p: row urow0 + 8 p
+        const uint32_t urow0 = (uint32_t)(rb * 256 + wave * 32 + 16 * pr + (ln >> 3));       // pass p: row urow0 + 8 p
         // rows beyond M take no part at all: a load issued for them and never consumed would leave hipcc a pending register at the join, i.e. an
         // `s_waitcnt vmcnt(0)` in front of the next LDS read - which waits for every store and DMA piece this wave has in flight
         float4 xq[2];
@@ -316,7 +307,7 @@ __global__ __launch_bounds__(512, 2) void gemm_x3_as_kernel(AsArgs g) {
                 float gd[4];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) gelu_and_grad(v[k], v[k], gd[k]);
-                if (d.aux && live) as_store16<(EPI & AS_SC1) != 0>(d.aux, (urow * (uint32_t)d.ldaux + col) * 4u, as_f32x4{gd[0], gd[1], gd[2], gd[3]});
+                if (d.aux && live) as_store16(d.aux, (urow * (uint32_t)d.ldaux + col) * 4u, as_f32x4{gd[0], gd[1], gd[2], gd[3]});
             }
             if (live) {
                 if constexpr (PLANES) {
@@ -324,26 +315,19 @@ __global__ __launch_bounds__(512, 2) void gemm_x3_as_kernel(AsArgs g) {
                     const uint32_t l0 = pack_bf2(v[0] - __uint_as_float(h0 << 16), v[1] - __uint_as_float(h0 & 0xffff0000u));
                     const uint32_t l1 = pack_bf2(v[2] - __uint_as_float(h1 << 16), v[3] - __uint_as_float(h1 & 0xffff0000u));
                     const uint32_t co = (urow * (uint32_t)d.ldc + col) * 2u;
-                    as_store8<(EPI & AS_SC1) != 0>(d.c, co, as_u32x2{h0, h1});
-                    as_store8<(EPI & AS_SC1) != 0>(d.c_lo, co, as_u32x2{l0, l1});
+                    as_store8(d.c, co, as_u32x2{h0, h1});
+                    as_store8(d.c_lo, co, as_u32x2{l0, l1});
                 } else {
-                    as_store16<(EPI & AS_SC1) != 0>(d.c, (urow * (uint32_t)d.ldc + col) * 4u, as_f32x4{v[0], v[1], v[2], v[3]});
+                    as_store16(d.c, (urow * (uint32_t)d.ldc + col) * 4u, as_f32x4{v[0], v[1], v[2], v[3]});
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
         }
     };
 
-    unsigned long long tsum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    auto now = [&]() __attribute__((always_inline)) -> unsigned long long {
-        if constexpr (DBG) { wait_lgkm0(); return __builtin_amdgcn_s_memtime(); }
-        return 0ull;
-    };
-    const unsigned long long t_start = now();
-
     // ---- prologue: the first four half blocks on their way
     const int nhb = 2 * nU;
-    if (grp == 0 && (EPI & AS_NODMA) == 0) {
+    if (grp == 0) {
 #pragma unroll
         for (int k = 0; k < 3; ++k)
             if (k < nhb) dma_next();
@@ -356,10 +340,9 @@ __global__ __launch_bounds__(512, 2) void gemm_x3_as_kernel(AsArgs g) {
     int S1 = 0, S2 = 0, S3 = 0;
     bool F1 = false, F2 = false, F3 = false;
     // store instructions of one epilogue half of a wave whose 16 rows are ALL live (counted only then: an under-count merely waits a little longer)
-    const int s_half = (EPI & AS_NOEPI) ? 0 : (PLANES ? 4 : 2) + (((EPI & AS_GELU) != 0 && d.aux) ? 2 : 0);
+    const int s_half = (PLANES ? 4 : 2) + (((EPI & AS_GELU) != 0 && d.aux) ? 2 : 0);
     const int nticks = nhb + 2;                    // group 1 runs one tick behind group 0; a wave's last epilogue half is the tick after its last MFMAs
     for (int tt = 0; tt < nticks; ++tt) {
-        const unsigned long long t0 = now();
         // Opening of tick tt.  Waves 0..3 (the DMA issuers): half block tt's pieces were issued three ticks ago and two batches (4 GH pieces) since - with at
         // most that many operations in flight they have landed, while the newest pieces and the epilogue's stores stay in flight across the barrier; once the
         // stream has run out (tt + 2 >= nhb) everything is waited for.  Waves 4..7 issue no pieces: nothing of theirs has to land before the barrier.  After the
@@ -390,14 +373,12 @@ __global__ __launch_bounds__(512, 2) void gemm_x3_as_kernel(AsArgs g) {
         }
         S3 = S2; F3 = F2; S2 = S1; F2 = F1; S1 = 0; F1 = false;          // tick tt's own counts are filled in below
         __builtin_amdgcn_s_barrier();
-        const unsigned long long t1 = now();
-        tsum[0] += t1 - t0; tsum[7] += 1;
         const int lt = tt - grp;                   // this wave's own half-block counter
         // (one home for the accumulators per tick: without this pin hipcc splits their live ranges over the two role branches - MFMAs with vdst != srcC, copies,
         // and a spilled A fragment to pay for them)
         asm volatile("" : "+v"(acc[0][0]), "+v"(acc[0][1]), "+v"(acc[1][0]), "+v"(acc[1][1]));
         if (lt < 0 || lt > nhb) continue;
-        const bool dma = (EPI & AS_NODMA) == 0 && grp == 0 && tt + 3 < nhb;
+        const bool dma = grp == 0 && tt + 3 < nhb;
         if ((lt & 1) == 0) {
             // STARTER of this tick: the parked epilogue half of the unit it finished last tick FIRST (the partner wave of the SIMD, at raised priority, has the
             // matrix pipe), then the first half of the next unit
@@ -405,59 +386,32 @@ __global__ __launch_bounds__(512, 2) void gemm_x3_as_kernel(AsArgs g) {
                 epi_half(1, e_rb, e_cb);
                 if (e_rb * 256 + wave * 32 + 32 <= d.M) S1 += s_half;
             }
-            const unsigned long long t2 = now();
-            tsum[1] += t2 - t1;
             if (lt == nhb) continue;               // that was this wave's last unit
             prefetch_x(c_rb, c_cb);
             if (c_cb == CB - 1 && c_left > 1) prefetch_a(c_rb + 1);
             if (c_rb != cur_rb) { load_a(c_rb); cur_rb = c_rb; }
             init_acc(c_cb);
-            const unsigned long long t4 = now();
             half_mma(0, (uint32_t)((lt % AS_SLOTS) * HALF_B), dma);
-            const unsigned long long t5 = now();
-            tsum[3] += t4 - t2; tsum[4] += t5 - t4;
         } else {
             // FINISHER: second half at RAISED priority (its MFMAs go first), then the unit's first epilogue half under the rest of the partner's MFMAs; the
             // second half waits in the accumulators for the next tick.  The stores stay in flight across the barrier.
-            if constexpr ((EPI & AS_NOPRIO) == 0) __builtin_amdgcn_s_setprio(1);
+            __builtin_amdgcn_s_setprio(1);
             half_mma(1, (uint32_t)((lt % AS_SLOTS) * HALF_B), dma);
-            if constexpr ((EPI & AS_NOPRIO) == 0) __builtin_amdgcn_s_setprio(0);
-            const unsigned long long t5 = now();
+            __builtin_amdgcn_s_setprio(0);
             epi_half(0, c_rb, c_cb);
             if (c_rb * 256 + wave * 32 + 16 <= d.M) S1 += s_half;
             F1 = true;
             e_rb = c_rb; e_cb = c_cb;
             if (++c_cb == CB) { c_cb = 0; ++c_rb; }
             --c_left;
-            tsum[5] += t5 - t1;
-            if constexpr (DBG) tsum[2] += now() - t5;
-        }
-    }
-    if constexpr (DBG) {
-        tsum[6] = now() - t_start;
-        if (g.dbg && lane == 0) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) g.dbg[((size_t)blockIdx.x * 8 + wave) * 8 + k] = tsum[k];
         }
     }
 }
 
-template <int KS, int EPI, bool DBG>
-int as_launch1(const AsArgs& g, int nwg, hipStream_t s) {
-    const size_t LDS = AS_SLOTS * ((KS / 8) * 2 * 4096) + (size_t)g.d.N * 4 + 8 * 256 + 8 * 16 * 36 * 4;
-    return p3_launch<gemm_x3_as_kernel<KS, EPI, DBG>>(nullptr, dim3(nwg), dim3(512), LDS, s, g);      // p3_gemm_x3_as records the name
-}
-
-// var: 0 the kernel, 1 its instrumented twin (s_memtime sums), 2 without epilogue, 3 without epilogue and weight stream (measurement)
 template <int KS, int EPI>
-int as_launch(const AsArgs& g, int var, int nwg, hipStream_t s) {
-    if (var == 1) return as_launch1<KS, EPI | AS_SC1, true>(g, nwg, s);
-    if (var == 2) return as_launch1<KS, EPI | AS_NOEPI, false>(g, nwg, s);
-    if (var == 3) return as_launch1<KS, EPI | AS_NOEPI | AS_NODMA, false>(g, nwg, s);
-    if (var == 4) return as_launch1<KS, EPI | AS_FOLD, false>(g, nwg, s);
-    if (var == 5) return as_launch1<KS, EPI, false>(g, nwg, s);
-    if (var == 6) return as_launch1<KS, EPI | AS_SC1 | AS_NOPRIO, false>(g, nwg, s);
-    return as_launch1<KS, EPI | AS_SC1, false>(g, nwg, s);
+int as_launch(const AsArgs& g, int nwg, hipStream_t s) {
+    const size_t LDS = AS_SLOTS * ((KS / 8) * 2 * 4096) + (size_t)g.d.N * 4 + 8 * 256 + 8 * 16 * 36 * 4;
+    return p3_launch<gemm_x3_as_kernel<KS, EPI | AS_SC1, false>>(nullptr, dim3(nwg), dim3(512), LDS, s, g);      // p3_gemm_x3_as records the name
 }
 
 int as_epi_of(const p3_gemm_x3_desc* d) {
@@ -468,15 +422,15 @@ bool as_epi_built(int epi) {
 }
 
 template <int KS>
-int as_dispatch(const AsArgs& g, int epi, int var, int nwg, hipStream_t s) {
+int as_dispatch(const AsArgs& g, int epi, int nwg, hipStream_t s) {
     switch (epi) {
-        case 0: return as_launch<KS, 0>(g, var, nwg, s);
-        case AS_RES: return as_launch<KS, AS_RES>(g, var, nwg, s);
-        case AS_MUL: return as_launch<KS, AS_MUL>(g, var, nwg, s);
-        case AS_GELU: return as_launch<KS, AS_GELU>(g, var, nwg, s);
-        case AS_PLANES: return as_launch<KS, AS_PLANES>(g, var, nwg, s);
-        case AS_PLANES | AS_GELU: return as_launch<KS, AS_PLANES | AS_GELU>(g, var, nwg, s);
-        case AS_PLANES | AS_MUL: return as_launch<KS, AS_PLANES | AS_MUL>(g, var, nwg, s);
+        case 0: return as_launch<KS, 0>(g, nwg, s);
+        case AS_RES: return as_launch<KS, AS_RES>(g, nwg, s);
+        case AS_MUL: return as_launch<KS, AS_MUL>(g, nwg, s);
+        case AS_GELU: return as_launch<KS, AS_GELU>(g, nwg, s);
+        case AS_PLANES: return as_launch<KS, AS_PLANES>(g, nwg, s);
+        case AS_PLANES | AS_GELU: return as_launch<KS, AS_PLANES | AS_GELU>(g, nwg, s);
+        case AS_PLANES | AS_MUL: return as_launch<KS, AS_PLANES | AS_MUL>(g, nwg, s);
         default: break;
     }
     p3_set_error("p3_gemm_x3: epilogue combination not built for the A-stationary kernel");
@@ -492,15 +446,11 @@ int as_dispatch(const AsArgs& g, int epi, int var, int nwg, hipStream_t s) {
 bool p3_gemm_x3_as_default(const p3_gemm_x3_desc* d) { return d->N >= 1024 && !(d->mul && d->c_lo); }
 
 bool p3_gemm_x3_as_ok(const p3_gemm_x3_desc* d) {
-    return d->conv_ci == 0 && (d->K == 384 || d->K == 256) && d->N % 32 == 0 && d->N <= 4096 && !d->ln_gamma && as_epi_built(as_epi_of(d)) &&
+    return d->conv_ci == 0 && (d->K == 384 || d->K == 256) && d->N % 32 == 0 && d->N <= 4096 && as_epi_built(as_epi_of(d)) &&
            (int64_t)d->N * d->ldb * 2 < (1ll << 31) && (!d->bias || (uintptr_t)d->bias % 16 == 0) &&
            (int64_t)d->M * d->ldc * 4 < (1ll << 32) && (!d->aux || (int64_t)d->M * d->ldaux * 4 < (1ll << 32)) &&
            (!d->mul || (int64_t)d->M * d->ldmul * 4 < (1ll << 32)) && (!d->residual || (int64_t)d->M * d->ldr * 4 < (1ll << 32));
 }
-
-static unsigned long long* g_as_dbg = nullptr;
-// measurement hook (tools/mb_as.py): device buffer [256 workgroups][8 waves][8] for the cycle sums of the instrumented twin (P3_AS_VAR=1)
-extern "C" int p3_gemm_x3_as_debug(void* buf) { g_as_dbg = (unsigned long long*)buf; return P3_OK; }
 
 int p3_gemm_x3_as(const p3_gemm_x3_desc* d, hipStream_t s) {
     static int n_cu = 0;
@@ -514,15 +464,12 @@ int p3_gemm_x3_as(const p3_gemm_x3_desc* d, hipStream_t s) {
     g.d = *d;
     g.CB = d->N / 32;
     g.units = p3_ceil_div(d->M, 256) * g.CB;
-    g.dbg = g_as_dbg;
     const int nwg = g.units < n_cu ? g.units : n_cu;
     const int epi = as_epi_of(d);
-    static int var = -1;
-    if (var < 0) { const char* e = getenv("P3_AS_VAR"); var = e ? atoi(e) : 0; }
     if (p3_tracing()) {                               // the instantiation as rocprofv3 spells it (bench.py matches its PMC table by this name)
         char nm[64];
-        snprintf(nm, sizeof(nm), "gemm_x3_as_kernel<%d, %d, false>", d->K / 16, epi | (var == 0 ? AS_SC1 : 0));
+        snprintf(nm, sizeof(nm), "gemm_x3_as_kernel<%d, %d, false>", d->K / 16, epi | AS_SC1);
         p3_note_kernel(nm);
     }
-    return d->K == 384 ? as_dispatch<24>(g, epi, var, nwg, s) : as_dispatch<16>(g, epi, var, nwg, s);
+    return d->K == 384 ? as_dispatch<24>(g, epi, nwg, s) : as_dispatch<16>(g, epi, nwg, s);
 }

@@ -139,7 +139,7 @@ __device__ __forceinline__ void attn_block_of(int lid, int nblk, int L, int pair
         else { const int l2 = local - p8; pair = x * p8 + l2 / (nblk - 1); blk = l2 % (nblk - 1); }
     } else { blk = lid % nblk; pair = lid / nblk; }
 }
-int p3_attn_order(void);      // host: 1 unless P3_ATTN_TAIL_FIRST=0 (A/B switch)
+int p3_attn_order(void);      // host: always 1, tail blocks first (attention.hip)
 
 // row index of accumulator register r of a 32x32 MFMA C/D fragment (col = lane & 31)
 __device__ __forceinline__ int crow32(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }

@@ -6,8 +6,6 @@ HIP data flow: both stems write straight into one token-major (NHWC) canvas [B, 
 conv is an implicit-GEMM gather over that canvas with the BN batch statistics accumulated in the GEMM epilogue, and
 BN + ReLU + CLS + pos_embed are applied by one assemble kernel that produces the fp32 residual stream.
 """
-import os
-
 import torch
 import torch.nn as nn
 
@@ -66,8 +64,8 @@ class EarlyFusionViT(nn.Module):
 
 
 # A/B switch: the fp32x3 fusion convolution (forward, dX, dW) on the planes GEMM kernels - conv-tap addressing over one zero-bordered planes image per operand
-# (DESIGN section 0s); 0 keeps the register-staged implicit GEMM and the nine shifted fp32 weight-gradient products
-CONV_PLANES = [os.environ.get("P3_CONV_PLANES", "1") != "0"]
+# (DESIGN section 0s); False keeps the register-staged implicit GEMM and the nine shifted fp32 weight-gradient products
+CONV_PLANES = [True]
 
 
 def _zero_lidar(canvas, D):
@@ -101,7 +99,7 @@ class _FusionConvBN(torch.autograd.Function):
                 hip.col_stats(pre, sums)
         else:
             pre = hip.gemm(canvas.view(B * g * g, 2 * D), w2, bias=b.detach(), a_mode=hip.A_CONV3X3, conv=(B, g, g, 2 * D), lda=2 * D,
-                           out_dtype=cd, colsum=sums[:D] if training else None, colsumsq=sums[D:] if training else None, w_planes=ops.wpl(w2))
+                           out_dtype=cd, colsum=sums[:D] if training else None, colsumsq=sums[D:] if training else None)
         world = ops.sync_stats(sums) if training else 1
         scale, shift, mean, rstd = hip.bn_finalize(sums, float(B * g * g * world), gamma.detach(), beta.detach(), bn.running_mean, bn.running_var,
                                                    bn.eps, bn.momentum, training, save=True)
@@ -138,7 +136,7 @@ class _FusionConvBN(torch.autograd.Function):
         dW2 = torch.zeros((D, 9 * 2 * D), dtype=torch.float32, device=dpre.device)
         # the nine products leave their split-M partial tiles parked side by side (column slices of one matrix) and ONE flush adds them - whatever the
         # backward pass had parked before rides along, earlier than it would have - instead of nine reduce launches of ~27 us
-        with hip.tn_parking(hip.CONV_PARK) as parking:
+        with hip.tn_parking(True) as parking:
             for t in range(9):
                 s = (t // 3 - 1) * P + (t % 3 - 1)
                 r0, r1 = max(0, -s), R - max(0, s)
@@ -148,7 +146,7 @@ class _FusionConvBN(torch.autograd.Function):
         dw = dW2.view(D, 3, 3, 2 * D).permute(0, 3, 1, 2).contiguous()
         # input gradient: correlation with the flipped kernel, [Ci, (ky', kx', co)]
         wf = ops.shadow(w, cd, key="flipT", fn=lambda t_: t_.flip(2, 3).permute(1, 2, 3, 0).reshape(t_.shape[1], -1))
-        dcanvas = hip.gemm(dpre, wf, a_mode=hip.A_CONV3X3, conv=(B, g, g, D), lda=D, out_dtype=cd, w_planes=ops.wpl(wf)).view(B, g * g, 2 * D)
+        dcanvas = hip.gemm(dpre, wf, a_mode=hip.A_CONV3X3, conv=(B, g, g, D), lda=D, out_dtype=cd).view(B, g * g, 2 * D)
         return dcanvas, dw, db, dg, dbt, None, None
 
     @staticmethod
@@ -167,7 +165,7 @@ class _FusionConvBN(torch.autograd.Function):
         fix = dict(pre=pre, a=a, b=b) if mod.training else {}
         dp = hip.pad_nhwc_planes(dpre.view(M, D), B, g, g, guard=0, cols=Dp, **fix)
         dW2 = torch.zeros((Dp, 9 * 2 * D), dtype=torch.float32, device=dpre.device)
-        with hip.tn_parking(hip.CONV_PARK) as parking:
+        with hip.tn_parking(True) as parking:
             hip.gemm_tn_x3_conv(dp, cp, P, out=dW2)
         if parking.on and hip.reduce_pending():
             hip.reduce_flush()

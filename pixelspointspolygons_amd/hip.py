@@ -242,9 +242,6 @@ def _drop(spec):
     return d
 
 
-W_PLANES = [os.environ.get("P3_W_PLANES", "0") == "1"]      # fp32x3: the register-staged GEMM takes the weight as planes when the caller has them.  OFF: measured no gain (r06, profiles/r06_w_planes_colsum_park_ab.txt: 65.55 vs 65.65 ms same-box) - the option and its test stay
-
-
 class GemmDesc(Structure):
     _fields_ = [("M", c_int), ("N", c_int), ("K", c_int), ("lda", c_int), ("ldb", c_int), ("ldc", c_int),
                 ("dtype_in", c_int), ("dtype_out", c_int), ("act", c_int), ("a_mode", c_int),
@@ -278,7 +275,7 @@ def gemm(a, w, *, bias=None, act=ACT_NONE, residual=None, out=None, out_dtype=No
         N, K = wpl[0].shape
     else:
         N, K = w.shape
-        # (the callers gate on their switches - ops.wpl: W_PLANES; planes that are handed in and fit are used)
+        # (planes that are handed in and fit are used)
         if w_planes is not None and dt_mm(a) == F32X3 and a_mode in (A_PLAIN, A_CONV3X3, A_CONV3X3_AFFINE_RELU) and tuple(w_planes[0].shape) == (N, K) \
                 and w_planes_fit(w_planes, K):
             wpl = w_planes
@@ -420,10 +417,6 @@ def tn_defer_release():
     _tn_park["buf"] = None
 
 
-COLSUM_PARK = os.environ.get("P3_COLSUM_PARK", "1") != "0"   # bias-gradient column sums of the weight-gradient GEMMs park with the deferred reduces (A/B switch)
-CONV_PARK = os.environ.get("P3_CONV_PARK", "1") != "0"     # the nine shifted weight-gradient products of a 3 x 3 convolution park their partial tiles, one flush (A/B switch)
-
-
 class tn_parking:
     """`with hip.tn_parking(on):` weight-gradient launches inside may leave their split-M partial tiles parked for reduce_flush() (their outputs must be
     accumulation targets that stay valid and unread until then: views of the optimizer's gradient arena)"""
@@ -432,7 +425,7 @@ class tn_parking:
         self.on = bool(on) and DETERMINISTIC >= 1 and tn_defer_arena()
         # r06: the launch's bias-gradient column sums (colsum_out = a view of the gradient arena) park with the deferred parameter reduces (p3_reduce_park) - one
         # det_reduce launch of ~6 us less per Linear and train step
-        self.on_colsum = self.on and COLSUM_PARK and param_reduce_arena()
+        self.on_colsum = self.on and param_reduce_arena()
 
     def __enter__(self):
         if self.on:
@@ -1625,18 +1618,13 @@ def attention_bwd(q, k, v, o, lse, do, heads, scale, causal=False, key_bias=None
     return dq, dk, dv
 
 
-TN_MAX_SLABS = 0     # > 0 (tools/mb_tn.py): store split-M partials in scratch slabs + reduce instead of fp32 atomics also outside deterministic launches
-
-
 def _tn_slabs(N, K, a):
     """(scratch, max slabs) for the split-M partial tiles of the weight-gradient GEMM: stored + summed in split order by tn_reduce_kernel
-    instead of fp32 atomics.  Always in deterministic launches (hip.det_on); TN_MAX_SLABS forces it elsewhere (r02 A/B: 43.3 ms with atomics, 43.7 - 48 with slabs)."""
+    instead of fp32 atomics - in deterministic launches (hip.det_on) only: elsewhere the atomics were faster (r02 A/B: 43.3 ms with atomics, 43.7 - 48 with slabs)."""
     if det_on(a):
         ns = max(8, min(512, (64 << 20) // (N * K * 4)))         # <= 64 MB of slabs, at least 8
         return workspace(ns * N * K * 4 + 16, a.device, "tn_slabs"), ns
-    if TN_MAX_SLABS <= 0:
-        return None, 0
-    return workspace(TN_MAX_SLABS * N * K * 4 + 16, a.device, "tn_slabs"), TN_MAX_SLABS
+    return None, 0
 
 
 def gemm_tn(a, b, out=None, colsum_out=None):
@@ -2035,8 +2023,7 @@ class GemmX3Desc(Structure):
                 ("c", c_void_p), ("c_lo", c_void_p), ("ldc", c_int),
                 ("bias", c_void_p), ("residual", c_void_p), ("ldr", c_int), ("act", c_int),
                 ("aux", c_void_p), ("ldaux", c_int), ("mul", c_void_p), ("ldmul", c_int),
-                ("ln_gamma", c_void_p), ("ln_beta", c_void_p), ("ln_eps", c_float),
-                ("ln_hi", c_void_p), ("ln_lo", c_void_p), ("ldln", c_int), ("ln_mean", c_void_p), ("ln_rstd", c_void_p), ("tile", c_int),
+                ("tile", c_int),
                 ("conv_B", c_int), ("conv_H", c_int), ("conv_W", c_int), ("conv_ci", c_int), ("conv_row0", c_int)]
 
 
@@ -2052,7 +2039,7 @@ def x3_cus(device):
     return _x3_cus[idx]
 
 
-X3_RAGGED_SPLIT = [os.environ.get("P3_X3_RAGGED", "1") != "0"]               # A/B switch of the ragged-round rule below
+X3_RAGGED_SPLIT = [True]               # A/B switch of the ragged-round rule below
 
 
 def x3_conv_row(m, H, W):
@@ -2062,10 +2049,10 @@ def x3_conv_row(m, H, W):
     return (b * (H + 2) + y + 1) * (W + 2) + x + 1
 
 
-def gemm_x3(a, w, *, bias=None, act=ACT_NONE, residual=None, aux=None, mul=None, out=None, out_planes=False, ln=None, conv=None, conv_rows=None, tile=0,
+def gemm_x3(a, w, *, bias=None, act=ACT_NONE, residual=None, aux=None, mul=None, out=None, out_planes=False, conv=None, conv_rows=None, tile=0,
             ragged=None):
     """C = epilogue((a_hi + a_lo) (w_hi + w_lo)^T).  a: Planes [M, K]; w: (hi, lo) bf16 [N, K] tensors (or Planes); out: fp32 [M, N] tensor or Planes
-    (out_planes=True allocates one).  ln = (gamma, beta, eps, Planes out, mean, rstd): LayerNorm of the output row fused into the epilogue (N == 384).
+    (out_planes=True allocates one).
     conv = (B, H, W, Ci): 3 x 3 convolution - a is the zero-bordered planes image [B (H+2) (W+2), Ci] (pad_nhwc_planes), w is [N, (ky, kx, ci)], the output rows
     are the B H W interior pixels (conv_rows = (first, count): only these output pixels; out, residual, ... start at pixel `first`).  tile: 0 the library's rule, 1 / 2 force a tile kernel for this call; ragged: False keeps the launch whole (measurement)."""
     M, K = a.rows, a.cols
@@ -2104,18 +2091,13 @@ def gemm_x3(a, w, *, bias=None, act=ACT_NONE, residual=None, aux=None, mul=None,
         d.aux, d.ldaux = aux.data_ptr(), aux.stride(-2)
     if mul is not None:
         d.mul, d.ldmul = mul.data_ptr(), mul.stride(-2)
-    if ln is not None:
-        gamma, beta, eps, lnout, mean, rstd = ln
-        d.ln_gamma, d.ln_beta, d.ln_eps = gamma.data_ptr(), beta.data_ptr(), float(eps)
-        d.ln_hi, d.ln_lo, d.ldln = lnout.hi.data_ptr(), lnout.lo.data_ptr(), lnout.ld
-        d.ln_mean, d.ln_rstd = (mean.data_ptr() if mean is not None else None), (rstd.data_ptr() if rstd is not None else None)
     def launch(dd, rows):
         ev = KTIMER.begin()
         check(lib().p3_gemm_x3(byref(dd), stream()), "p3_gemm_x3")
         if ev is not None:
             a_rows = rows if conv is None else a.rows * rows / M          # conv: the image is read once (nine taps of it from L2), not K / Ci times
             nbytes = 4.0 * (a_rows * a.cols + N * K + rows * N) + (4.0 * rows * N if residual is not None else 0) + (4.0 * rows * N if aux is not None else 0) \
-                + (4.0 * rows * N if mul is not None else 0) + (4.0 * rows * N if ln is not None else 0)
+                + (4.0 * rows * N if mul is not None else 0)
             KTIMER.end(ev, lib().p3_last_kernel().decode() or "gemm_x3_kernel", 2.0 * rows * N * K, nbytes)
 
     # A ragged last round of the 128 x 384 tile (csrc/gemm_x3.hip picks it for N > 256, K >= 1024; one workgroup per CU): M = 50 240 is 393 row tiles = a full round
@@ -2131,7 +2113,7 @@ def gemm_x3(a, w, *, bias=None, act=ACT_NONE, residual=None, aux=None, mul=None,
         cus //= 2
     rem = tm % cus
     split_ok = X3_RAGGED_SPLIT[0] if ragged is None else ragged
-    if split_ok and tile == 0 and ln is None and ((conv is None and 256 < N <= 384) or (conv is not None and 384 < N <= 768)) and K >= 1024 and tm > cus \
+    if split_ok and tile == 0 and ((conv is None and 256 < N <= 384) or (conv is not None and 384 < N <= 768)) and K >= 1024 and tm > cus \
             and 0 < rem <= (3 * cus) // 4:
         head = (tm - rem) * 128
         d2 = GemmX3Desc()

@@ -25,8 +25,8 @@ GRAD_READY = [None]     # callable(param) installed by GradBucketReducer: the ke
 # Deferred parameter-gradient reduces (r04): the LayerNorm backward launches that accumulate straight into the gradient arena park their workgroup partials and ONE
 # launch at the end of the backward pass adds them all (p3_reduce_defer / p3_reduce_flush: 42 reduce launches of ~7 us less per Pix2Poly train step, bit-identical
 # gradients).  Only without a reducer (its bucket triggers need a parameter's gradient complete when the operator reports it); the flush is queued on the autograd
-# engine the first time a launch parks, so whoever reads a gradient after backward() sees it complete.  P3_DEFER_REDUCE=0: off.
-DEFER_PARAM_REDUCE = [os.environ.get("P3_DEFER_REDUCE", "1") == "1"]
+# engine the first time a launch parks, so whoever reads a gradient after backward() sees it complete.
+DEFER_PARAM_REDUCE = [True]
 _flush_queued = [False]
 
 
@@ -368,18 +368,7 @@ def derived_planes(p, key, fn):
     return pl.hi, pl.lo
 
 
-def wpl(p, transpose=False):
-    """(hi, lo) of weight / derived weight tensor `p` for hip.gemm(w_planes=...) - the register-staged fp32x3 GEMM then copies the weight's planes instead of
-    splitting the fp32 weight in every tile - or None outside an fp32x3 scope / for a non-fp32 or non-2-D tensor.  Callers slice the pair the way they slice the
-    weight; hip.gemm checks shape / alignment and falls back to the fp32 weight when they do not fit."""
-    if not hip.W_PLANES[0] or not hip.split_now() or p.dtype != torch.float32 or p.dim() != 2:
-        return None
-    if p.shape[0 if transpose else 1] % 8 != 0:          # p3_to_planes: 16-byte rows (the 227-row vocabulary layer's transpose stays an fp32 operand)
-        return None
-    return weight_planes(p, transpose)
-
-
-WT_PLANES = [os.environ.get("P3_WT_PLANES", "1") != "0"]      # A/B switch of wpl_T_registered below
+WT_PLANES = [True]      # A/B switch of wpl_T_registered below
 
 
 def wpl_T_registered(p):
@@ -570,7 +559,7 @@ def clear_twins():
     _stream.clear()
 
 
-# ---- bf16 residual-GRADIENT stream of the ViT (P3_GRAD_BF16=1) -------------------------------------------------------------------------
+# ---- bf16 residual-GRADIENT stream of the ViT (GRAD_STREAM_BF16) -------------------------------------------------------------------------
 # The forward residual stream stays fp32 (its bf16 form costs accuracy: encoder feature error 1.0 % -> 3.3 %, r02); its GRADIENT need not:
 # every consumer (the dX / dW GEMMs of proj, fc2, the next LayerNorm backward) reads it in bf16 anyway.  autograd insists that the gradient
 # of an fp32 tensor is fp32, so what travels along the stream through autograd is a CARRIER - an fp32 tensor of the right shape with stride 0
@@ -579,7 +568,7 @@ def clear_twins():
 # twin, one 38 MB read instead of 77 MB per LayerNorm backward).  Consumers resolve a carrier with _stream_real(): _to_cd (the GEMMs),
 # _LayerNormFork.backward (dres), _Assemble.backward (end of the chain: one cast back to fp32).  A residual pass-through (`dres = dy` in
 # _Linear / _Mlp backward) hands the carrier on untouched.
-GRAD_STREAM_BF16 = [os.environ.get("P3_GRAD_BF16", "1") == "1"]    # r03: -0.35 ms per step (ln_bwd 68.6 -> 55.8 us x 24), encoder gradient cosine at the run-to-run noise floor (tools/diag_gradstream.py)
+GRAD_STREAM_BF16 = [True]    # r03: -0.35 ms per step (ln_bwd 68.6 -> 55.8 us x 24), encoder gradient cosine at the run-to-run noise floor (tools/diag_gradstream.py)
 # Only an operator that was TOLD its input is the ViT stream emits a carrier (layernorm_fork(..., stream_grad=True) from Block.run, the final
 # norm's layernorm(..., stream_grad=True)); the generic operators never do (a carrier that reaches a consumer that cannot resolve
 # it is garbage).  A carrier's one element is NaN (a slot of a NaN-filled pool, one fill per device), so whoever reads it as data gets NaN,
@@ -688,11 +677,9 @@ class _Linear(torch.autograd.Function):
         if ctx.gin is not None:
             gin.armed = True
         ctx.gout_res = gout_res if (gout_res is not None and gout_res.armed and residual is not None) else None
-        wp = wpl(weight) if cd == torch.float32 else None
         if rows is not None:
             w = w[rows[0]:rows[1]]
             bias = bias[rows[0]:rows[1]] if bias is not None else None
-            wp = (wp[0][rows[0]:rows[1]], wp[1][rows[0]:rows[1]]) if wp is not None else None
         ctx.rows = rows
         x2 = x.reshape(-1, x.shape[-1])
         need = any(ctx.needs_input_grad)
@@ -700,7 +687,7 @@ class _Linear(torch.autograd.Function):
         if need and act == hip.ACT_GELU:
             aux = torch.empty((x2.shape[0], w.shape[0]), dtype=out_dtype, device=x.device)
         res2 = residual.reshape(-1, residual.shape[-1]) if residual is not None else None
-        y = hip.gemm(x2, w, bias=bias, act=act, residual=res2, out_dtype=out_dtype, aux=aux, drop=drop, w_planes=wp)
+        y = hip.gemm(x2, w, bias=bias, act=act, residual=res2, out_dtype=out_dtype, aux=aux, drop=drop)
         ctx.drop = drop if (drop is not None and drop[2] > 0.0) else None
         if ctx.drop is not None and act == hip.ACT_GELU:
             raise NotImplementedError("dropout after GELU is not on the reference path")
@@ -748,10 +735,7 @@ class _Linear(torch.autograd.Function):
                 nfull = (weight.shape[0] + 63) // 64 * 64
                 wt = shadow(weight, cd, key="T", fn=lambda t: _pad_cols(t.t(), nfull))         # [K, N_full (zero padded to %64)]
                 wt = wt[:, rows[0]:rows[1]] if rows is not None else wt[:, :dpre.shape[1]]
-                wtp = wpl(weight, transpose=True) if cd == torch.float32 else None          # [K, N] planes of W^T (unpadded: a padded N falls back inside hip.gemm)
-                if wtp is not None and rows is not None:
-                    wtp = (wtp[0][:, rows[0]:rows[1]], wtp[1][:, rows[0]:rows[1]])
-                dx = hip.gemm(dpre, wt, out_dtype=cd, residual=res_g, w_planes=wtp).view(ctx.xshape)
+                dx = hip.gemm(dpre, wt, out_dtype=cd, residual=res_g).view(ctx.xshape)
             if ctx.gout_x is not None:
                 ctx.gout_x.g, dx = dx, None
         direct = DIRECT_GRAD[0] and weight.is_leaf and weight.grad is not None and dpre.shape[1] == n_true    # a derived weight (LayerScale fold) has no arena slot
@@ -833,10 +817,9 @@ class _Mlp(torch.autograd.Function):
         if drop1 is not None and act != hip.ACT_RELU:
             raise NotImplementedError("dropout after GELU is not on the reference path")
         aux = torch.empty((x2.shape[0], w1.shape[0]), dtype=cd, device=x.device) if (need and act == hip.ACT_GELU) else None
-        wp1, wp2 = (wpl(w1), wpl(w2)) if cd == torch.float32 else (None, None)
-        h = hip.gemm(x2, w1c, bias=b1, act=act, out_dtype=cd, aux=aux, aux_grad=True, drop=drop1, w_planes=wp1)   # aux <- GELU'(pre), not pre
+        h = hip.gemm(x2, w1c, bias=b1, act=act, out_dtype=cd, aux=aux, aux_grad=True, drop=drop1)   # aux <- GELU'(pre), not pre
         res2 = residual.reshape(-1, residual.shape[-1]) if residual is not None else None
-        y = hip.gemm(h, w2c, bias=b2, residual=res2, out_dtype=out_dtype, drop=drop2, w_planes=wp2)
+        y = hip.gemm(h, w2c, bias=b2, residual=res2, out_dtype=out_dtype, drop=drop2)
         ctx.cfg = (act, cd, residual is not None, drop1, drop2, x.shape)
         ctx.b1, ctx.b2 = b1, b2
         if need:
@@ -861,7 +844,7 @@ class _Mlp(torch.autograd.Function):
             dpre1 = hip.gemm(dpre2, None, out_dtype=cd, bwd=bwd, w_planes=w2r)               # dH * act'(.) in the epilogue
         else:
             w2t = shadow(w2, cd, key="T", fn=lambda t: t.t().contiguous())                   # [hidden, out]
-            dpre1 = hip.gemm(dpre2, w2t, out_dtype=cd, bwd=bwd, w_planes=wpl(w2, transpose=True) if cd == torch.float32 else None)
+            dpre1 = hip.gemm(dpre2, w2t, out_dtype=cd, bwd=bwd)
         dw1, db1 = _weight_grads(dpre1, x2, w1, ctx.b1, ctx.needs_input_grad[1], ctx.needs_input_grad[2])
         dx = None
         if ctx.needs_input_grad[0]:
@@ -870,8 +853,7 @@ class _Mlp(torch.autograd.Function):
                 dx = hip.gemm(dpre1, None, out_dtype=cd, residual=_materialize(dy2) if ctx.res_is_x else None, w_planes=w1r).view(xshape)
             else:
                 w1t = shadow(w1, cd, key="T", fn=lambda t: t.t().contiguous())               # [in, hidden]
-                dx = hip.gemm(dpre1, w1t, out_dtype=cd, residual=_materialize(dy2) if ctx.res_is_x else None,
-                              w_planes=wpl(w1, transpose=True) if cd == torch.float32 else None).view(xshape)
+                dx = hip.gemm(dpre1, w1t, out_dtype=cd, residual=_materialize(dy2) if ctx.res_is_x else None).view(xshape)
             if ctx.res_is_x:
                 dres = None
         return dx, dw1, db1, dw2, db2, dres, None, None, None, None, None, None

@@ -6,13 +6,11 @@ One autograd node for all blocks: the residual stream stays an fp32 tensor; ever
 the LayerNorm backward (the residual-gradient stream), the GELU' epilogue of the hidden gradient - so that every product (forward, dX, dW) stages its four
 operand images by LDS-DMA and issues a_lo b_hi + a_hi b_lo + a_hi b_hi on the bf16 MFMA: the arithmetic of P3_F32X3, 2^-17 per product.
 
-Per block, forward:   h1 = LN1(x) | qkv = h1 Wqkv^T + b | o = SDPA(qkv) | x1 = x + o Wp^T + b (+ LN2 fused into that epilogue) | hid = GELU(h2 W1^T + b), aux = GELU'
+Per block, forward:   h1 = LN1(x) | qkv = h1 Wqkv^T + b | o = SDPA(qkv) | x1 = x + o Wp^T + b | h2 = LN2(x1) | hid = GELU(h2 W1^T + b), aux = GELU'
                       | x2 = x1 + hid W2^T + b
 backward (reverse):   dW2 / db2 = g^T hid | dU = (g W2) * aux | dW1 / db1 = dU^T h2 | dh2 = dU W1 | g1 = g + LN2'(dh2) | dWp / dbp = g1^T o | do = g1 Wp
                       | dqkv = SDPA'(do) | dWqkv / dbqkv = dqkv^T h1 | dh1 = dqkv Wqkv | g0 = g1 + LN1'(dh1)
 """
-import os
-
 import torch
 
 from . import hip, ops
@@ -47,7 +45,7 @@ def _accum(weight, bias, dy, x, grads, iw, ib):
 @hip.precision_scoped
 class _ViTStackX3(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, heads, eps, fuse_ln, grad_on, *params):
+    def forward(ctx, x, heads, eps, grad_on, *params):
         B, L, D = x.shape
         M = B * L
         nblk = len(params) // PER_BLOCK
@@ -60,45 +58,26 @@ class _ViTStackX3(torch.autograd.Function):
         if not xs.is_contiguous():
             xs = xs.contiguous()
         saved, scale = [], (D // heads) ** -0.5
-        h1 = m1 = r1 = None               # LN1 output of the block about to run, when the previous block's fc2 epilogue produced it
         for i in range(nblk):
             n1w, n1b, wqkv, bqkv, wp, bp, n2w, n2b, w1, b1, w2, b2 = params[i * PER_BLOCK:(i + 1) * PER_BLOCK]
-            if h1 is None:
-                h1, m1, r1 = hip.layernorm_planes(xs, n1w, n1b, eps)
+            h1, m1, r1 = hip.layernorm_planes(xs, n1w, n1b, eps)
             qkv = hip.gemm_x3(h1, ops.weight_planes(wqkv), bias=bqkv).view(B, L, 3 * D)
             q, k, v = qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:]
-            o = hip.Planes.empty(M, D, dev) if ATTN_OUT_PLANES[0] else None     # the attention launch writes its output as planes too (p3_attn_desc.o_planes): no conversion pass
+            o = hip.Planes.empty(M, D, dev)     # the attention launch writes its output as planes too (p3_attn_desc.o_planes): no conversion pass
             if need:
                 o32, lse = hip.attention(q, k, v, heads, scale, need_lse=True, out_planes=o)
             else:
                 o32, lse = hip.attention(q, k, v, heads, scale, out_planes=o), None
-            if o is None:
-                o = hip.to_planes(o32.view(M, D))
             x1 = torch.empty((M, D), dtype=torch.float32, device=dev)
-            if fuse_ln and D == 384:
-                h2 = hip.Planes.empty(M, D, dev)
-                m2 = torch.empty(M, dtype=torch.float32, device=dev)
-                r2 = torch.empty(M, dtype=torch.float32, device=dev)
-                hip.gemm_x3(o, ops.weight_planes(wp), bias=bp, residual=xs, out=x1, ln=(n2w, n2b, eps, h2, m2, r2))
-            else:
-                hip.gemm_x3(o, ops.weight_planes(wp), bias=bp, residual=xs, out=x1)
-                h2, m2, r2 = hip.layernorm_planes(x1, n2w, n2b, eps)
+            hip.gemm_x3(o, ops.weight_planes(wp), bias=bp, residual=xs, out=x1)
+            h2, m2, r2 = hip.layernorm_planes(x1, n2w, n2b, eps)
             aux = torch.empty((M, w1.shape[0]), dtype=torch.float32, device=dev) if need else None
             hid = hip.gemm_x3(h2, ops.weight_planes(w1), bias=b1, act=hip.ACT_GELU, aux=aux, out_planes=True)
             x2 = torch.empty((M, D), dtype=torch.float32, device=dev)
-            nxt = None
-            if fuse_ln and D == 384 and i + 1 < nblk:            # the NEXT block's LN1 rides on this fc2 epilogue
-                nw, nb = params[(i + 1) * PER_BLOCK], params[(i + 1) * PER_BLOCK + 1]
-                nh = hip.Planes.empty(M, D, dev)
-                nm, nr = torch.empty(M, dtype=torch.float32, device=dev), torch.empty(M, dtype=torch.float32, device=dev)
-                hip.gemm_x3(hid, ops.weight_planes(w2), bias=b2, residual=x1, out=x2, ln=(nw, nb, eps, nh, nm, nr))
-                nxt = (nh, nm, nr)
-            else:
-                hip.gemm_x3(hid, ops.weight_planes(w2), bias=b2, residual=x1, out=x2)
+            hip.gemm_x3(hid, ops.weight_planes(w2), bias=b2, residual=x1, out=x2)
             if need:
                 saved.append((xs, m1, r1, h1, qkv, o32, lse, o, x1, m2, r2, h2, hid, aux))
             xs = x2
-            h1, m1, r1 = nxt if nxt is not None else (None, None, None)
         if need:
             ctx.saved = saved                  # plain attribute: Planes are not tensors; nothing here is an input or output of the node
             ctx.cfg = (B, L, D, heads, scale, nblk)
@@ -144,7 +123,7 @@ class _ViTStackX3(torch.autograd.Function):
             del dqp, h1
             g, gp = _ln_bwd(dh1, xs, n1w, n1b, m1, r1, g1, grads, k0 + 0, k0 + 1, direct)
             del dh1, g1, g1p
-        return (g.view(B, L, D), None, None, None, None) + tuple(grads)
+        return (g.view(B, L, D), None, None, None) + tuple(grads)
 
 
 def _ln_bwd(dy, x, gamma, beta, mean, rstd, dres, grads, ig, ib, direct):
@@ -159,16 +138,11 @@ def _ln_bwd(dy, x, gamma, beta, mean, rstd, dres, grads, ig, ib, direct):
     return dx, dxp
 
 
-# LayerNorm of the proj / fc2 output row inside that GEMM's epilogue (N == 384).  Measured r05 (tools/mb_x3.py, M = 50 240): proj 86 -> 133 us, fc2 230 -> 281 us
-# against 27 us for the separate LayerNorm launch it replaces - the three-pass epilogue (store + mean, variance, normalise) runs with the matrix pipe idle
-# (one workgroup per CU: nothing overlaps it).  Kept as a tested option, OFF.
-FUSE_LN = [False]
-ATTN_OUT_PLANES = [os.environ.get("P3_ATTN_OPLANES", "1") != "0"]      # A/B switch: 0 = a p3_to_planes pass over the attention output instead of planes written by the attention launch
-
-
+# (LayerNorm stays its own launch: fused into the proj / fc2 epilogue it measured slower, r05 - proj 86 -> 133 us, fc2 230 -> 281 us against 27 us for the
+# launch it replaced: the three-pass epilogue ran with the matrix pipe idle.  That form is gone.)
 def vit_stack(x, blocks, heads, eps):
     """x [B, L, D] fp32 residual stream -> after all blocks (fp32)"""
     params = []
     for blk in blocks:
         params.extend(block_params(blk))
-    return _ViTStackX3.apply(x, heads, eps, FUSE_LN[0], torch.is_grad_enabled(), *params)
+    return _ViTStackX3.apply(x, heads, eps, torch.is_grad_enabled(), *params)

@@ -19,7 +19,7 @@ from . import hip, ops, ops_x3
 # leading dimension of the patch rows when K = Cin*P*P is no multiple of 32 (patch 14: K = 588, which neither p3_gemm nor the LDS-DMA GEMM takes): K rounded up to this
 # multiple, zero filled.  64 -> 640 (K % 64 == 0: the bf16 LDS-DMA GEMM is eligible); 32 -> 608, the smallest legal value.  Measured: DESIGN "DINOv2 encoder".
 PATCH_LDK_ALIGN = [int(os.environ.get("P3_PATCH_LDK_ALIGN", "32"))]
-X3_STACK = [os.environ.get("P3_X3_STACK", "1") == "1"]      # 0: 'fp32x3' blocks on the per-operator path (fp32 operands split while staged, gemm.hip SPLIT): the A/B and cross-check arm
+X3_STACK = [True]      # False: 'fp32x3' blocks on the per-operator path (fp32 operands split while staged, gemm.hip SPLIT): the A/B and cross-check arm
 
 
 def compute_dtype(cfg):
@@ -85,8 +85,8 @@ class _PatchGemm(torch.autograd.Function):
         ctx.wshape, ctx.D = weight.shape, D
         ctx.chain = canvas is not None and canvas.requires_grad      # the pillar stem wrote into this canvas first: hand its gradient on
         if canvas is None:
-            return hip.gemm(patches, w2, bias=bias, out_dtype=cd, w_planes=ops.wpl(w2))
-        hip.gemm(patches, w2, bias=bias, out=canvas[..., :D], w_planes=ops.wpl(w2))
+            return hip.gemm(patches, w2, bias=bias, out_dtype=cd)
+        hip.gemm(patches, w2, bias=bias, out=canvas[..., :D])
         ctx.mark_dirty(canvas)
         return canvas
 

@@ -522,34 +522,6 @@ def test_gemm_x3_tiles(tile, M, N, K):
         _close(f"x3 tile {tile} mul planes", _planes_value(dp), ref * mul.double(), 2e-5)
 
 
-def test_gemm_x3_fused_layernorm():
-    """(129, 384, 64) with LayerNorm of the output row in the epilogue: C in a padded guarded view, LN(C) as guarded planes (zero tail), mean and rstd guarded.
-    Tolerances of test_gemm_x3_fused_layernorm_of_the_output_row: 1e-5, planes 3e-5, statistics 1e-5."""
-    h = _h()
-    M, N, K = 129, 384, 64
-    a, w = _rand(M, K, seed=11), _rand(N, K, seed=12, scale=0.05)
-    bias, res = _rand(N, seed=13), _rand(M, N, seed=14) * 3.0 + 0.5
-    gamma, beta = _rand(N, seed=15) * 0.2 + 1.0, _rand(N, seed=16) * 0.1
-    ap, wp = _planes_in(a), _planes_in(w, pad=1)
-    c, gc = guarded(M, N, F32, ld=N + 8, device=DEV)
-    lp, gl, own = _planes_out(M, N)
-    mean, gm = _vec(M)
-    rstd, gr = _vec(M)
-    R = poisoned(res, ld=N + 4, extra_rows=2, device=DEV)
-    _, name = _launch(lambda: h.gemm_x3(ap, wp, bias=bias.to(DEV), residual=R, out=c, ln=(gamma.to(DEV), beta.to(DEV), 1e-6, lp, mean, rstd)))
-    torch.cuda.synchronize()
-    assert name == "gemm_x3_n384_kernel<true>", name
-    gc.check()
-    gl.check(valid=own)
-    gm.check()
-    gr.check()
-    ref = _planes_value(ap) @ _planes_value(wp).t() + bias.double() + res.double()
-    _close("x3 ln C", c, ref, 1e-5)
-    _close("x3 ln planes", _planes_value(lp), F.layer_norm(ref, (N,), gamma.double(), beta.double(), 1e-6), 3e-5)
-    _close("x3 ln mean", mean, ref.mean(-1), 1e-5)
-    _close("x3 ln rstd", rstd, (ref.var(-1, unbiased=False) + 1e-6).rsqrt(), 1e-5)
-
-
 def test_gemm_tn_x3_accumulates_into_a_column_slice():
     """M = 70 rows (planes padded to 128, zero tail), N = 128, K = 256, out a preset column slice of a guarded matrix, the bias column sums guarded; 1e-5
     (test_gemm_tn_x3_weight_gradient)"""
@@ -779,7 +751,7 @@ def _ln_data(rows, cols):
 @pytest.mark.parametrize("odt", [F32, BF])
 def test_layernorm_forward_strided(odt, rows, cols):
     """x in NaN-padded rows (ldx = cols + 8), y in a guarded padded view, mean / rstd guarded; 2e-6 / 5e-3 for bf16 out (test_layernorm_fwd_bwd), the row
-    statistics at the fused kernel's 1e-5 (test_gemm_x3_fused_layernorm_of_the_output_row)"""
+    statistics at 1e-5"""
     h = _h()
     x, gamma, beta = _ln_data(rows, cols)
     X = poisoned(x, ld=cols + 8, extra_rows=4, device=DEV)

@@ -250,7 +250,7 @@ def _node_run(B, g, D, planes):
 
 
 def test_fusion_conv_bn_node_on_planes():
-    """_FusionConvBN on a stub module (B = 2, g = 6, D = 64), train mode, inside an fp32x3 scope: against float64 autograd, against P3_CONV_PLANES = 0, and twice.
+    """_FusionConvBN on a stub module (B = 2, g = 6, D = 64), train mode, inside an fp32x3 scope: against float64 autograd, against fusion_layers.CONV_PLANES off, and twice.
     Tolerance: 2e-5 in the l2 metric - what tests/test_backward_gpu.py holds its fp32x3 BatchNorm node (test_pair_bwd_fused_x3...) to: a split product carries
     2^-17 per term, the BatchNorm statistics and coefficients are fp32 sums reduced in float64; the ReLU decisions of a handful of elements within that error of
     the kink differ, which the l2 metric absorbs."""

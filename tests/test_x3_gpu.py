@@ -134,30 +134,6 @@ def test_gemm_x3_ragged_last_round_goes_to_the_small_tile():
     assert torch.equal(y[:32768], y1[:32768])                      # the whole-round rows run the same kernel on the same tiles
 
 
-@pytest.mark.parametrize("M,K", [(1570, 384), (1000, 1536), (128, 384)])
-def test_gemm_x3_fused_layernorm_of_the_output_row(M, K):
-    """proj / fc2 of timm's Block with the following LayerNorm in the epilogue (N == 384): C, LN(C) as planes, mean and rstd"""
-    hip = _h()
-    N = 384
-    a, w = _rand(M, K, seed=11), _rand(N, K, seed=12, scale=0.05)
-    bias, res = _rand(N, seed=13), _rand(M, N, seed=14) * 3.0 + 0.5
-    gamma, beta = _rand(N, seed=15) * 0.2 + 1.0, _rand(N, seed=16) * 0.1
-    ap, wp = hip.to_planes(a.to(DEV)), hip.to_planes(w.to(DEV), pad=1)
-    c = torch.empty(M, N, device=DEV)
-    h = hip.Planes.empty(M, N, DEV)
-    mean, rstd = torch.empty(M, device=DEV), torch.empty(M, device=DEV)
-    hip.gemm_x3(ap, wp, bias=bias.to(DEV), residual=res.to(DEV), out=c, ln=(gamma.to(DEV), beta.to(DEV), 1e-6, h, mean, rstd))
-    ref = a.double() @ w.double().t() + bias.double() + res.double()
-    assert rel_err(c.cpu(), ref.float()) < 1e-5
-    lref = F.layer_norm(ref, (N,), gamma.double(), beta.double(), 1e-6)
-    assert rel_err(hip.from_planes(h).cpu(), lref.float()) < 3e-5
-    assert rel_err(mean.cpu(), ref.mean(-1).float()) < 1e-5
-    assert rel_err(rstd.cpu(), (ref.var(-1, unbiased=False) + 1e-6).rsqrt().float()) < 1e-5
-    # the separate kernel gives the same planes from the same C (statistics over the fp32 values either way)
-    h2, m2, r2 = hip.layernorm_planes(c, gamma.to(DEV), beta.to(DEV), 1e-6)
-    assert rel_err(hip.from_planes(h2).cpu(), hip.from_planes(h).cpu()) < 1e-5 and rel_err(m2.cpu(), mean.cpu()) < 1e-5 and rel_err(r2.cpu(), rstd.cpu()) < 1e-5
-
-
 @pytest.mark.parametrize("wide", [1, 0])
 @pytest.mark.parametrize("M,N,K", [(1570, 384, 384), (1570, 1536, 384), (1570, 384, 1536), (3200, 1152, 384), (130, 768, 768), (50240, 1536, 384)])
 def test_gemm_tn_x3_weight_gradient(M, N, K, wide):
@@ -217,26 +193,23 @@ def _vit(precision, depth=2):
     return ViT(cfg, bottleneck=True).to(DEV)
 
 
-@pytest.mark.parametrize("fuse_ln", [True, False])
-def test_block_stack_on_planes_equals_the_per_operator_fp32x3_path_and_float64_autograd(fuse_ln):
+def test_block_stack_on_planes_equals_the_per_operator_fp32x3_path_and_float64_autograd():
     """ViT encoder (2 blocks, 785 tokens) forward + backward in 'fp32x3': the planes stack (ops_x3.py) against (a) the per-operator path - the same products with
     the operands split while they are staged (vision_transformer.X3_STACK off) - and (b) the exact fp32 path: outputs 1e-4, every parameter gradient 2e-3 of the
-    largest one.  fuse_ln: LayerNorm inside the proj / fc2 epilogue or as its own launch."""
-    from pixelspointspolygons_amd import ops_x3
+    largest one."""
     import pixelspointspolygons_amd.vision_transformer as vt
     img = torch.rand(2, 3, 224, 224, generator=torch.Generator().manual_seed(3)).to(DEV)
     w = torch.randn(2, 784, 256, generator=torch.Generator().manual_seed(4)).to(DEV)
 
     def run(precision, stack):
         was, vt.X3_STACK[0] = vt.X3_STACK[0], stack
-        wasf, ops_x3.FUSE_LN[0] = ops_x3.FUSE_LN[0], fuse_ln
         try:
             m = _vit(precision).train()
             y = m(img)
             (y.float() * w).sum().backward()
             return y.detach().float().cpu(), {k: p.grad.float().cpu() for k, p in m.named_parameters()}
         finally:
-            vt.X3_STACK[0], ops_x3.FUSE_LN[0] = was, wasf
+            vt.X3_STACK[0] = was
     y_st, g_st = run("fp32x3", True)
     y_op, g_op = run("fp32x3", False)
     y_ex, g_ex = run("fp32", False)
@@ -284,11 +257,7 @@ def test_register_staged_gemm_with_the_weight_as_planes_gives_the_bits_of_the_fp
     a, w = _rand(M, K, seed=1).to(DEV), _rand(N, K, seed=2, scale=0.1).to(DEV)
     bias, res = _rand(N, seed=3).to(DEV), _rand(M, N, seed=4).to(DEV)
     wp = hip.to_planes(w, pad=1)
-    was, hip.W_PLANES[0] = hip.W_PLANES[0], True              # the option is off by default (no measured gain): switched on for the test
-    try:
-        _weight_planes_checks(hip, a, w, bias, res, wp)
-    finally:
-        hip.W_PLANES[0] = was
+    _weight_planes_checks(hip, a, w, bias, res, wp)
 
 
 def _weight_planes_checks(hip, a, w, bias, res, wp):
@@ -320,16 +289,12 @@ def test_conv3x3_gather_with_the_weight_as_planes():
     x = _rand(B * H * W_, C, seed=5).to(DEV)
     w = _rand(Co, 9 * C, seed=6, scale=0.05).to(DEV)
     wp = hip.to_planes(w, pad=1)
-    was, hip.W_PLANES[0] = hip.W_PLANES[0], True
-    try:
-        with hip.gemm_split(True):
-            ref = hip.gemm(x, w, a_mode=hip.A_CONV3X3, conv=(B, H, W_, C), lda=C)
-            hip.lib().p3_trace_kernels(1)
-            out = hip.gemm(x, w, a_mode=hip.A_CONV3X3, conv=(B, H, W_, C), lda=C, w_planes=(wp.hi, wp.lo))
-            name = hip.lib().p3_last_kernel().decode()
-            hip.lib().p3_trace_kernels(0)
-    finally:
-        hip.W_PLANES[0] = was
+    with hip.gemm_split(True):
+        ref = hip.gemm(x, w, a_mode=hip.A_CONV3X3, conv=(B, H, W_, C), lda=C)
+        hip.lib().p3_trace_kernels(1)
+        out = hip.gemm(x, w, a_mode=hip.A_CONV3X3, conv=(B, H, W_, C), lda=C, w_planes=(wp.hi, wp.lo))
+        name = hip.lib().p3_last_kernel().decode()
+        hip.lib().p3_trace_kernels(0)
     assert name == "gemm_kernel<float, float, 1, 18, false>", name
     assert torch.equal(out, ref)
 

@@ -1,4 +1,4 @@
-"""bf16 residual-gradient stream (P3_GRAD_BF16=1) against the fp32 one on the bench model: per-parameter gradient cosine and norm ratio of
+"""bf16 residual-gradient stream (ops.GRAD_STREAM_BF16) against the fp32 one on the bench model: per-parameter gradient cosine and norm ratio of
 one train-mode backward (same weights, same batch, dropout off), and the step time of both.   python tools/diag_gradstream.py"""
 import sys
 import time

@@ -1,4 +1,4 @@
-"""The A-stationary planes GEMM (csrc/gemm_x3_as.hip) against float64 and against the tile kernels: python tools/mb_as.py [check|time|all]"""
+"""The A-stationary planes GEMM (csrc/gemm_x3_as.hip) against float64 and against the tile kernels: python tools/mb_as.py [check|time|as|one <row>|all]"""
 import sys
 import torch
 import torch.nn.functional as F
@@ -115,35 +115,6 @@ def timing():
         print(f"{name:44s} " + " ".join(f"{c:>20s}" for c in cols), flush=True)
 
 
-def dbg():
-    """P3_AS_VAR=1 (the instrumented twin): s_memtime sums per wave -> mean cycles per tick and stage, by wave group"""
-    import ctypes
-    M = 64 * 785
-    x384 = hip.to_planes(torch.randn(M, 384, device=dev))
-    buf = torch.zeros(256 * 8 * 8, dtype=torch.int64, device=dev)
-    lib().p3_gemm_x3_as_debug(ctypes.c_void_p(buf.data_ptr()))
-    lib().p3_gemm_x3_tile(3)
-    names = ["wait+barrier", "epilogue", "dma issue", "A reload", "half 0", "half 1", "total", "ticks"]
-    aux = torch.randn(M, 1536, device=dev)
-    for label, N, kw in (("qkv 1152 -> f32", 1152, {}), ("fc1 1536 GELU+aux -> planes", 1536, dict(act=hip.ACT_GELU, aux=aux, out_planes=True)),
-                         ("dX fc2 1536 *mul -> planes", 1536, dict(mul=aux, out_planes=True)), ("proj 384 -> f32", 384, {})):
-        w = hip.to_planes(torch.randn(N, 384, device=dev), pad=1)
-        b = torch.randn(N, device=dev)
-        for _ in range(3):
-            buf.zero_()
-            hip.gemm_x3(x384, w, bias=b, **kw)
-        torch.cuda.synchronize()
-        t = buf.view(256, 8, 8).double().cpu()
-        print(label)
-        for grp in (0, 1):
-            tg = t[:, grp * 4:(grp + 1) * 4].reshape(-1, 8)
-            ticks = tg[:, 7].mean()
-            print(f"  waves {grp * 4}..{grp * 4 + 3}: ticks {ticks:.1f}  total {tg[:, 6].mean():.0f} cyc = {tg[:, 6].mean() / ticks:.0f} / tick | per tick: "
-                  + "  ".join(f"{names[k]} {tg[:, k].mean() / ticks:.0f}" for k in range(6)) + f" | max total {tg[:, 6].max():.0f}", flush=True)
-    lib().p3_gemm_x3_as_debug(None)
-    lib().p3_gemm_x3_tile(0)
-
-
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "all"
     bad = 0
@@ -152,12 +123,8 @@ if __name__ == "__main__":
     if what == "one":               # python tools/mb_as.py one <row substring>: that row on the A-stationary kernel only (for rocprofv3 --pmc)
         AS_ONLY, ONLY = True, sys.argv[2]
         timing()
-    if what == "dbg":
-        dbg()
-    if what == "as":
-        import os
+    if what == "as":                # every row on the A-stationary kernel only
         AS_ONLY = True
-        print("P3_AS_VAR =", os.environ.get("P3_AS_VAR", "default"))
         timing()
     if what in ("time", "all"):
         timing()

@@ -30,17 +30,14 @@ res = torch.randn(M, 384, device=dev)
 aux = torch.empty(M, 1536, device=dev)
 out384, out1152 = torch.empty(M, 384, device=dev), torch.empty(M, 1152, device=dev)
 outp1536, outp384 = hip.Planes.empty(M, 1536, dev), hip.Planes.empty(M, 384, dev)
-mean, rstd = torch.empty(M, device=dev), torch.empty(M, device=dev)
 gam, bet = torch.ones(384, device=dev), torch.zeros(384, device=dev)
 W = {(n, k): P(n, k, 1) for n, k in ((1152, 384), (384, 384), (1536, 384), (384, 1536), (384, 1152))}
 b = {n: torch.randn(n, device=dev) for n in (384, 1152, 1536)}
 rows = [
     ("qkv      1152x384  -> f32", lambda: hip.gemm_x3(x384, W[(1152, 384)], bias=b[1152], out=out1152), 2.0 * M * 1152 * 384),
     ("proj     384x384   +res -> f32", lambda: hip.gemm_x3(x384, W[(384, 384)], bias=b[384], residual=res, out=out384), 2.0 * M * 384 * 384),
-    ("proj     384x384   +res +LN", lambda: hip.gemm_x3(x384, W[(384, 384)], bias=b[384], residual=res, out=out384, ln=(gam, bet, 1e-6, outp384, mean, rstd)), 2.0 * M * 384 * 384),
     ("fc1      1536x384  GELU+aux -> planes", lambda: hip.gemm_x3(x384, W[(1536, 384)], bias=b[1536], act=hip.ACT_GELU, aux=aux, out=outp1536), 2.0 * M * 1536 * 384),
     ("fc2      384x1536  +res -> f32", lambda: hip.gemm_x3(x1536, W[(384, 1536)], bias=b[384], residual=res, out=out384), 2.0 * M * 1536 * 384),
-    ("fc2      384x1536  +res +LN", lambda: hip.gemm_x3(x1536, W[(384, 1536)], bias=b[384], residual=res, out=out384, ln=(gam, bet, 1e-6, outp384, mean, rstd)), 2.0 * M * 1536 * 384),
     ("dX fc2   1536x384  *aux -> planes", lambda: hip.gemm_x3(x384, W[(1536, 384)], mul=aux, out=outp1536), 2.0 * M * 1536 * 384),
     ("dX fc1   384x1536  -> f32", lambda: hip.gemm_x3(x1536, W[(384, 1536)], out=out384), 2.0 * M * 1536 * 384),
     ("dX qkv   384x1152  -> f32", lambda: hip.gemm_x3(x1152, W[(384, 1152)], out=out384), 2.0 * M * 1152 * 384),
@@ -58,7 +55,7 @@ print(f"{'':42s} {'128x128 tile':>22s} {'128x384 tile':>22s}")
 for name, fn, flop in rows:
     cols = []
     for mode in (1, 2):
-        if mode == 2 and ("dW" in name or "planes " in name or "+LN" in name and False):
+        if mode == 2 and ("dW" in name or "planes " in name):
             cols.append("")
             continue
         lib().p3_gemm_x3_tile(mode)
