@@ -348,10 +348,10 @@ int p3_pillar_stem(const float* values, const int64_t* offsets, const float* w1,
                    const float* bn1_beta, float* bn1_rmean, float* bn1_rvar, const void* w2, const float* bn2_gamma,
                    const float* bn2_beta, float* bn2_rmean, float* bn2_rvar, void* out, void* workspace,
                    const p3_pillar_desc* d, void* stream);
-/* byte offsets (17 int64) of the workspace sections: sorted, vox_xy, vox_start, vox_cnt, vox_row, nvox, X2, H2, hmax, hmin, F8 (decorated
+/* byte offsets (18 int64) of the workspace sections: sorted, vox_xy, vox_start, vox_cnt, vox_row, nvox, X2, H2, hmax, hmin, F8 (decorated
  * point features per X2 row), row_vox (pillar slot per row, -1 unused), row_w, then the statistics SyncBatchNorm all-reduces between the
- * phases: totals (int32: kept pillars of the batch), sums1 (fp32 [2*32]), sums2 (fp32 [2*C]), acc1 (fp32 [584]: layer-0 backward sums,
- * dbeta1 at [520:552], dgamma1 at [552:584]) */
+ * phases: totals (int32: kept pillars of the batch), sums1 (fp32 [2*32]), sums2 (fp32 [2*C]), acc1 (fp32 [584]: layer-0 backward sums),
+ * acc1_stat (inside acc1: fp32 [2*32] = dbeta1 | dgamma1, acc1[520:584]) */
 int p3_pillar_stem_layout(const p3_pillar_desc* d, int64_t* offsets);
 /* p3_pillar_stem split at its two BatchNorm statistics (nn.SyncBatchNorm.convert_sync_batchnorm, model_pix2poly.py:326): phases is a
  * bit mask, 1 = pillarize + layer-0 sums, 2 = layer-0 apply + layer-1 GEMM + sums, 4 = finalize + scatter; all-reduce totals / sums1

@@ -196,34 +196,26 @@ extern "C" int p3_act_bwd(const void* dy, int dtype_dy, const void* saved, int d
     P3_CHECK(dy && saved && out && (act == P3_ACT_GELU || act == P3_ACT_RELU), P3_EINVAL, "p3_act_bwd: bad arguments");
     if (n <= 0) return P3_OK;
     hipStream_t s = (hipStream_t)stream;
-    dim3 g(grid_for(n)), b(256);
-#define AB(TDY, TS, TO) hipLaunchKernelGGL((act_bwd_kernel<TDY, TS, TO>), g, b, 0, s, (const TDY*)dy, (const TS*)saved, (TO*)out, n, act, scale)
-    const int key = dtype_dy * 4 + dtype_saved * 2 + dtype_out;
-    switch (key) {
-        case 0: AB(float, float, float); break;
-        case 1: AB(float, float, bf16_t); break;
-        case 2: AB(float, bf16_t, float); break;
-        case 3: AB(float, bf16_t, bf16_t); break;
-        case 4: AB(bf16_t, float, float); break;
-        case 5: AB(bf16_t, float, bf16_t); break;
-        case 6: AB(bf16_t, bf16_t, float); break;
-        case 7: AB(bf16_t, bf16_t, bf16_t); break;
-        default: p3_set_error("p3_act_bwd: dtype"); return P3_EUNSUP;
-    }
-#undef AB
-    P3_LAUNCH_CHECK();
-    return P3_OK;
+    return p3_by_dtype(dtype_dy, false, "p3_act_bwd", [&](auto tdy) {
+        return p3_by_dtype(dtype_saved, false, "p3_act_bwd", [&](auto ts) {
+            return p3_by_dtype(dtype_out, false, "p3_act_bwd", [&](auto to) {
+                using TDY = typename decltype(tdy)::type;
+                using TS = typename decltype(ts)::type;
+                using TO = typename decltype(to)::type;
+                return p3_launch<act_bwd_kernel<TDY, TS, TO>>(nullptr, dim3(grid_for(n)), dim3(256), 0, s, (const TDY*)dy, (const TS*)saved, (TO*)out, n, act, scale);
+            });
+        });
+    });
 }
 
 extern "C" int p3_embed_tokens_bwd(const void* dx, int dtype, const int64_t* tokens, float* demb, float* dpos, int B, int L, int D, void* stream) {
     P3_CHECK(dx && tokens && demb && B > 0, P3_EINVAL, "p3_embed_tokens_bwd: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     const int64_t total = (int64_t)B * L * D;
-    if (dtype == P3_BF16) hipLaunchKernelGGL((embed_bwd_kernel<bf16_t>), dim3(grid_for(total)), dim3(256), 0, s, (const bf16_t*)dx, tokens, demb, dpos, B, L, D);
-    else if (dtype == P3_F32) hipLaunchKernelGGL((embed_bwd_kernel<float>), dim3(grid_for(total)), dim3(256), 0, s, (const float*)dx, tokens, demb, dpos, B, L, D);
-    else { p3_set_error("p3_embed_tokens_bwd: dtype"); return P3_EUNSUP; }
-    P3_LAUNCH_CHECK();
-    return P3_OK;
+    return p3_by_dtype(dtype, false, "p3_embed_tokens_bwd", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return p3_launch<embed_bwd_kernel<T>>(nullptr, dim3(grid_for(total)), dim3(256), 0, s, (const T*)dx, tokens, demb, dpos, B, L, D);
+    });
 }
 
 extern "C" int p3_embed_tokens_bwd_v(const void* dx, int dtype, const int64_t* tokens, float* demb, int B, int L, int D, int V, void* stream) {
@@ -232,21 +224,19 @@ extern "C" int p3_embed_tokens_bwd_v(const void* dx, int dtype, const int64_t* t
     hipStream_t s = (hipStream_t)stream;
     const int64_t rows = (int64_t)B * L;
     const int rpb = (int)p3_ceil_div(rows, (int64_t)64) < 32 ? 32 : (int)p3_ceil_div(rows, (int64_t)64);     // ~64 row groups x D/64 channel groups
-    dim3 grid((unsigned)p3_ceil_div(rows, (int64_t)rpb), (unsigned)p3_ceil_div(D, 64)), block(256);
     const size_t lds = (size_t)V * 64 * sizeof(float);
     // deterministic mode: one wave per workgroup, 128 row groups, the workgroups' tables through the scratch (128 x V x D floats: 30 MB at V = 227, D = 256)
     const int det_groups = 128;
     const int det_rpb = (int)p3_ceil_div(rows, (int64_t)det_groups);
     const int det_grid = (int)p3_ceil_div(rows, (int64_t)det_rpb);
-    float* slab = p3_det_scratch((int64_t)det_grid * V * D, dtype);
-    if (slab) { grid = dim3((unsigned)det_grid, (unsigned)p3_ceil_div(D, 64)); block = dim3(64); }
-    const int rpb_used = slab ? det_rpb : rpb;
-    if (dtype == P3_BF16) hipLaunchKernelGGL((embed_bwd_lds_kernel<bf16_t>), grid, block, lds, s, (const bf16_t*)dx, tokens, demb, rows, D, V, rpb_used, slab);
-    else if (dtype == P3_F32) hipLaunchKernelGGL((embed_bwd_lds_kernel<float>), grid, block, lds, s, (const float*)dx, tokens, demb, rows, D, V, rpb_used, slab);
-    else { p3_set_error("p3_embed_tokens_bwd_v: dtype"); return P3_EUNSUP; }
-    P3_LAUNCH_CHECK();
-    if (slab) return p3_det_reduce(slab, det_grid, (int64_t)V * D, demb, V * D, 1, s);
-    return P3_OK;
+    return p3_by_dtype(dtype, false, "p3_embed_tokens_bwd_v", [&](auto t) {
+        using T = typename decltype(t)::type;
+        float* slab = p3_det_scratch((int64_t)det_grid * V * D, dtype);
+        const dim3 grid((unsigned)(slab ? det_grid : p3_ceil_div(rows, (int64_t)rpb)), (unsigned)p3_ceil_div(D, 64)), block(slab ? 64 : 256);
+        const int rc = p3_launch<embed_bwd_lds_kernel<T>>(nullptr, grid, block, lds, s, (const T*)dx, tokens, demb, rows, D, V, slab ? det_rpb : rpb, slab);
+        if (rc != P3_OK || !slab) return rc;
+        return p3_det_reduce(slab, det_grid, (int64_t)V * D, demb, V * D, 1, s);
+    });
 }
 
 extern "C" int p3_tokens_assemble_bwd(const float* dx, const void* src, int src_ld, int dtype_src, const float* scale, const float* shift, const float* mean,
@@ -254,63 +244,54 @@ extern "C" int p3_tokens_assemble_bwd(const float* dx, const void* src, int src_
     P3_CHECK(dx && src && dsrc && B > 0, P3_EINVAL, "p3_tokens_assemble_bwd: bad arguments");
     P3_CHECK(!scale || (shift && dscale && dshift), P3_EINVAL, "p3_tokens_assemble_bwd: scale needs shift/dscale/dshift");
     hipStream_t s = (hipStream_t)stream;
-    // rows per workgroup (P3_ASM_RPB): fewer rows = more same-address atomics on the per-channel sums, more rows = a longer serial walk per
-    // workgroup; measured 8: 200 us, 16: 125, 32: 94, 64: 99, 128: 142, 192: 205
-    // r03: with the partial sums going through the scratch slab (no atomics) short walks win: 16 rows per workgroup (no scratch: atomics, 48 rows)
-    int rpb = 48;
-    float* slab = nullptr;
-    int64_t slab_floats = 0;
-    if (scale) {
-        const int rpb_s = 16;
-        const int64_t nb = p3_ceil_div((int64_t)B * np, rpb_s);
-        slab_floats = nb * 2 * D;
-        slab = p3_reduce_scratch(slab_floats + p3_ceil_div(nb, 128) * 2 * D);
-        if (slab) rpb = rpb_s;
-    }
-    dim3 g(p3_ceil_div((int64_t)B * np, rpb)), b(256);
-    if (dtype_src == P3_BF16) hipLaunchKernelGGL((assemble_bwd_kernel<bf16_t>), g, b, 0, s, dx, (const bf16_t*)src, src_ld, scale, shift, mean, (bf16_t*)dsrc, dscale, dshift, B, np, D, rpb, slab);
-    else if (dtype_src == P3_F32) hipLaunchKernelGGL((assemble_bwd_kernel<float>), g, b, 0, s, dx, (const float*)src, src_ld, scale, shift, mean, (float*)dsrc, dscale, dshift, B, np, D, rpb, slab);
-    else { p3_set_error("p3_tokens_assemble_bwd: dtype"); return P3_EUNSUP; }
-    P3_LAUNCH_CHECK();
-    if (slab) return p3_det_reduce2(slab, (int)g.x, 2 * D, slab + slab_floats, dscale, dshift, D, 2 * D, 1, s);
-    return P3_OK;
+    return p3_by_dtype(dtype_src, false, "p3_tokens_assemble_bwd", [&](auto t) {
+        using T = typename decltype(t)::type;
+        // rows per workgroup (P3_ASM_RPB): fewer rows = more same-address atomics on the per-channel sums, more rows = a longer serial walk per
+        // workgroup; measured 8: 200 us, 16: 125, 32: 94, 64: 99, 128: 142, 192: 205
+        // r03: with the partial sums going through the scratch slab (no atomics) short walks win: 16 rows per workgroup (no scratch: atomics, 48 rows)
+        int rpb = 48;
+        float* slab = nullptr;
+        int64_t slab_floats = 0;
+        if (scale) {
+            const int rpb_s = 16;
+            const int64_t nb = p3_ceil_div((int64_t)B * np, rpb_s);
+            slab_floats = nb * 2 * D;
+            slab = p3_reduce_scratch(slab_floats + p3_ceil_div(nb, 128) * 2 * D);
+            if (slab) rpb = rpb_s;
+        }
+        const dim3 g(p3_ceil_div((int64_t)B * np, rpb));
+        const int rc = p3_launch<assemble_bwd_kernel<T>>(nullptr, g, dim3(256), 0, s, dx, (const T*)src, src_ld, scale, shift, mean, (T*)dsrc, dscale, dshift, B, np,
+                                                         D, rpb, slab);
+        if (rc != P3_OK || !slab) return rc;
+        return p3_det_reduce2(slab, (int)g.x, 2 * D, slab + slab_floats, dscale, dshift, D, 2 * D, 1, s);
+    });
 }
 
 extern "C" int p3_pool_pos_bwd(const void* dout, int dtype_dout, void* dy, int dtype_dy, int B, int np, int Din, int Dout, void* stream) {
     P3_CHECK(dout && dy && B > 0, P3_EINVAL, "p3_pool_pos_bwd: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     const int64_t total = (int64_t)B * (np + 1) * Din;
-    if (Din <= 1024 && (int64_t)Din * Dout < (1ll << 30)) {      // thread-per-channel form
-        const int64_t rows = (int64_t)B * (np + 1);
-        const int rpb = (int)p3_ceil_div(rows, 2048) < 8 ? 8 : (int)p3_ceil_div(rows, 2048);
-        dim3 g2((unsigned)p3_ceil_div(rows, rpb)), b2((unsigned)((Din + 63) / 64 * 64));
-#define P3_POOL_ROWS(TG, TY) hipLaunchKernelGGL((pool_bwd_rows_kernel<TG, TY>), g2, b2, 0, s, (const TG*)dout, (TY*)dy, rows, np, Din, Dout, rpb)
-        if (dtype_dout == P3_BF16 && dtype_dy == P3_BF16) P3_POOL_ROWS(bf16_t, bf16_t);
-        else if (dtype_dout == P3_F32 && dtype_dy == P3_F32) P3_POOL_ROWS(float, float);
-        else if (dtype_dout == P3_F32 && dtype_dy == P3_BF16) P3_POOL_ROWS(float, bf16_t);
-        else if (dtype_dout == P3_BF16 && dtype_dy == P3_F32) P3_POOL_ROWS(bf16_t, float);
-        else { p3_set_error("p3_pool_pos_bwd: dtype"); return P3_EUNSUP; }
-#undef P3_POOL_ROWS
-        P3_LAUNCH_CHECK();
-        return P3_OK;
-    }
-    dim3 g(grid_for(total)), b(256);
-    if (dtype_dout == P3_BF16 && dtype_dy == P3_BF16) hipLaunchKernelGGL((pool_bwd_kernel<bf16_t, bf16_t>), g, b, 0, s, (const bf16_t*)dout, (bf16_t*)dy, B, np, Din, Dout);
-    else if (dtype_dout == P3_F32 && dtype_dy == P3_F32) hipLaunchKernelGGL((pool_bwd_kernel<float, float>), g, b, 0, s, (const float*)dout, (float*)dy, B, np, Din, Dout);
-    else if (dtype_dout == P3_F32 && dtype_dy == P3_BF16) hipLaunchKernelGGL((pool_bwd_kernel<float, bf16_t>), g, b, 0, s, (const float*)dout, (bf16_t*)dy, B, np, Din, Dout);
-    else if (dtype_dout == P3_BF16 && dtype_dy == P3_F32) hipLaunchKernelGGL((pool_bwd_kernel<bf16_t, float>), g, b, 0, s, (const bf16_t*)dout, (float*)dy, B, np, Din, Dout);
-    else { p3_set_error("p3_pool_pos_bwd: dtype"); return P3_EUNSUP; }
-    P3_LAUNCH_CHECK();
-    return P3_OK;
+    return p3_by_dtype(dtype_dout, false, "p3_pool_pos_bwd", [&](auto tg) {
+        return p3_by_dtype(dtype_dy, false, "p3_pool_pos_bwd", [&](auto ty) {
+            using TG = typename decltype(tg)::type;
+            using TY = typename decltype(ty)::type;
+            if (Din <= 1024 && (int64_t)Din * Dout < (1ll << 30)) {      // thread-per-channel form
+                const int64_t rows = (int64_t)B * (np + 1);
+                const int rpb = (int)p3_ceil_div(rows, 2048) < 8 ? 8 : (int)p3_ceil_div(rows, 2048);
+                return p3_launch<pool_bwd_rows_kernel<TG, TY>>(nullptr, dim3((unsigned)p3_ceil_div(rows, rpb)), dim3((unsigned)((Din + 63) / 64 * 64)), 0, s,
+                                                               (const TG*)dout, (TY*)dy, rows, np, Din, Dout, rpb);
+            }
+            return p3_launch<pool_bwd_kernel<TG, TY>>(nullptr, dim3(grid_for(total)), dim3(256), 0, s, (const TG*)dout, (TY*)dy, B, np, Din, Dout);
+        });
+    });
 }
 
 extern "C" int p3_pair_mean_bwd(const float* dF, void* dfeats, int dtype, int B, int L, int N, int D, int accumulate, void* stream) {
     P3_CHECK(dF && dfeats && B > 0, P3_EINVAL, "p3_pair_mean_bwd: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     const int64_t total = (int64_t)B * L * D;
-    if (dtype == P3_BF16) hipLaunchKernelGGL((pair_mean_bwd_kernel<bf16_t>), dim3(grid_for(total)), dim3(256), 0, s, dF, (bf16_t*)dfeats, B, L, N, D, accumulate);
-    else if (dtype == P3_F32) hipLaunchKernelGGL((pair_mean_bwd_kernel<float>), dim3(grid_for(total)), dim3(256), 0, s, dF, (float*)dfeats, B, L, N, D, accumulate);
-    else { p3_set_error("p3_pair_mean_bwd: dtype"); return P3_EUNSUP; }
-    P3_LAUNCH_CHECK();
-    return P3_OK;
+    return p3_by_dtype(dtype, false, "p3_pair_mean_bwd", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return p3_launch<pair_mean_bwd_kernel<T>>(nullptr, dim3(grid_for(total)), dim3(256), 0, s, dF, (T*)dfeats, B, L, N, D, accumulate);
+    });
 }

@@ -122,18 +122,12 @@ extern "C" int p3_patchify_ld(const float* img, void* out, int B, int Cin, int H
     P3_CHECK(img && out && B > 0 && Cin > 0 && P > 0 && H > 0 && W > 0 && H % P == 0 && W % P == 0, P3_ESHAPE, "p3_patchify_ld: bad arguments");
     P3_CHECK(ldk >= Cin * P * P && ldk <= 1024, P3_ESHAPE, "p3_patchify_ld: need Cin*P*P <= ldk <= 1024");
     P3_CHECK((int64_t)B * (H / P) * (W / P) < (1ll << 31), P3_ESHAPE, "p3_patchify_ld: too many patches");
-    P3_CHECK(dtype_out == P3_BF16 || dtype_out == P3_F32, P3_EUNSUP, "p3_patchify_ld: dtype");
     hipStream_t s = (hipStream_t)stream;
     const dim3 gr((unsigned)(B * (H / P) * (W / P))), bl((unsigned)((ldk + 63) / 64 * 64));
-    if (dtype_out == P3_BF16) {
-        if (p3_tracing()) p3_note_kernel("patchify_ld_kernel<bf16>");
-        hipLaunchKernelGGL((patchify_ld_kernel<bf16_t>), gr, bl, 0, s, img, (bf16_t*)out, Cin, H, W, P, ldk);
-    } else {
-        if (p3_tracing()) p3_note_kernel("patchify_ld_kernel<float>");
-        hipLaunchKernelGGL((patchify_ld_kernel<float>), gr, bl, 0, s, img, (float*)out, Cin, H, W, P, ldk);
-    }
-    P3_LAUNCH_CHECK();
-    return P3_OK;
+    return p3_by_dtype(dtype_out, false, "p3_patchify_ld", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return p3_launch<patchify_ld_kernel<T>>(p3_kname<T>("patchify_ld_kernel"), gr, bl, 0, s, img, (T*)out, Cin, H, W, P, ldk);
+    });
 }
 
 static int resample_args_ok(const void* a, const void* wy, const void* wx, const void* o, int n_in, int n_out, int D) {

@@ -395,28 +395,18 @@ __global__ void rng_advance_kernel(unsigned long long* seed) {
 
 }  // namespace
 
-#define DISPATCH_T(dtype, CALL_BF, CALL_F32, name)                 \
-    if ((dtype) == P3_BF16) { CALL_BF; }                           \
-    else if ((dtype) == P3_F32) { CALL_F32; }                      \
-    else { p3_set_error(name ": dtype"); return P3_EUNSUP; }
-
 extern "C" int p3_patchify(const float* img, void* out, int B, int Cin, int H, int W, int P, int dtype_out, void* stream) {
     P3_CHECK(img && out && B > 0 && H % P == 0 && W % P == 0, P3_ESHAPE, "p3_patchify: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     const int64_t total = (int64_t)B * Cin * H * W;
-    if (Cin * P * P <= 1024 && (int64_t)B * (H / P) * (W / P) < (1ll << 31)) {
-        if (p3_tracing()) p3_note_kernel(dtype_out == P3_BF16 ? "patchify_rows_kernel<bf16>" : "patchify_rows_kernel<float>");
-        const dim3 gr((unsigned)(B * (H / P) * (W / P))), bl((unsigned)((Cin * P * P + 63) / 64 * 64));
-        DISPATCH_T(dtype_out, hipLaunchKernelGGL((patchify_rows_kernel<bf16_t>), gr, bl, 0, s, img, (bf16_t*)out, Cin, H, W, P),
-                   hipLaunchKernelGGL((patchify_rows_kernel<float>), gr, bl, 0, s, img, (float*)out, Cin, H, W, P), "p3_patchify");
-        P3_LAUNCH_CHECK();
-        return P3_OK;
-    }
-    if (p3_tracing()) p3_note_kernel(dtype_out == P3_BF16 ? "patchify_kernel<bf16>" : "patchify_kernel<float>");
-    DISPATCH_T(dtype_out, hipLaunchKernelGGL((patchify_kernel<bf16_t>), dim3(grid_for(total)), dim3(256), 0, s, img, (bf16_t*)out, B, Cin, H, W, P),
-               hipLaunchKernelGGL((patchify_kernel<float>), dim3(grid_for(total)), dim3(256), 0, s, img, (float*)out, B, Cin, H, W, P), "p3_patchify");
-    P3_LAUNCH_CHECK();
-    return P3_OK;
+    return p3_by_dtype(dtype_out, false, "p3_patchify", [&](auto t) {
+        using T = typename decltype(t)::type;
+        if (Cin * P * P <= 1024 && (int64_t)B * (H / P) * (W / P) < (1ll << 31)) {
+            const dim3 gr((unsigned)(B * (H / P) * (W / P))), bl((unsigned)((Cin * P * P + 63) / 64 * 64));
+            return p3_launch<patchify_rows_kernel<T>>(p3_kname<T>("patchify_rows_kernel"), gr, bl, 0, s, img, (T*)out, Cin, H, W, P);
+        }
+        return p3_launch<patchify_kernel<T>>(p3_kname<T>("patchify_kernel"), dim3(grid_for(total)), dim3(256), 0, s, img, (T*)out, B, Cin, H, W, P);
+    });
 }
 
 extern "C" int p3_tokens_assemble(const void* src, int src_ld, int dtype_src, const float* scale, const float* shift, const float* cls,
@@ -424,26 +414,14 @@ extern "C" int p3_tokens_assemble(const void* src, int src_ld, int dtype_src, co
     P3_CHECK(src && cls && pos && x && B > 0, P3_EINVAL, "p3_tokens_assemble: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     const int64_t total = (int64_t)B * (np + 1) * D;
-    if (D % 4 == 0 && src_ld % 4 == 0 && ((uintptr_t)src % 16) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)pos % 16) == 0) {
-        if (p3_tracing()) p3_note_kernel(dtype_src == P3_BF16 ? "tokens_assemble_rows_kernel<bf16>" : "tokens_assemble_rows_kernel<float>");
-        const dim3 gr((unsigned)(B * (np + 1)));
-        DISPATCH_T(dtype_src, hipLaunchKernelGGL((tokens_assemble_rows_kernel<bf16_t>), gr, dim3(128), 0, s, (const bf16_t*)src, src_ld, scale, shift, cls, pos, x, np, D),
-                   hipLaunchKernelGGL((tokens_assemble_rows_kernel<float>), gr, dim3(128), 0, s, (const float*)src, src_ld, scale, shift, cls, pos, x, np, D), "p3_tokens_assemble");
-        P3_LAUNCH_CHECK();
-        return P3_OK;
-    }
-    if (p3_tracing()) p3_note_kernel(dtype_src == P3_BF16 ? "tokens_assemble_kernel<bf16>" : "tokens_assemble_kernel<float>");
-    DISPATCH_T(dtype_src, hipLaunchKernelGGL((tokens_assemble_kernel<bf16_t>), dim3(grid_for(total)), dim3(256), 0, s, (const bf16_t*)src, src_ld, scale, shift, cls, pos, x, B, np, D),
-               hipLaunchKernelGGL((tokens_assemble_kernel<float>), dim3(grid_for(total)), dim3(256), 0, s, (const float*)src, src_ld, scale, shift, cls, pos, x, B, np, D), "p3_tokens_assemble");
-    P3_LAUNCH_CHECK();
-    return P3_OK;
-}
-
-static const char* pool_pos_name(bool rows, int dtype_in, int dtype_out) {
-    static const char* const names[2][4] = {{"pool_pos_kernel<float, float>", "pool_pos_kernel<float, bf16>", "pool_pos_kernel<bf16, float>", "pool_pos_kernel<bf16, bf16>"},
-                                            {"pool_pos_rows_kernel<float, float>", "pool_pos_rows_kernel<float, bf16>", "pool_pos_rows_kernel<bf16, float>",
-                                             "pool_pos_rows_kernel<bf16, bf16>"}};
-    return names[rows ? 1 : 0][(dtype_in == P3_BF16 ? 2 : 0) + (dtype_out == P3_BF16 ? 1 : 0)];
+    return p3_by_dtype(dtype_src, false, "p3_tokens_assemble", [&](auto t) {
+        using T = typename decltype(t)::type;
+        if (D % 4 == 0 && src_ld % 4 == 0 && ((uintptr_t)src % 16) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)pos % 16) == 0)
+            return p3_launch<tokens_assemble_rows_kernel<T>>(p3_kname<T>("tokens_assemble_rows_kernel"), dim3((unsigned)(B * (np + 1))), dim3(128), 0, s,
+                                                             (const T*)src, src_ld, scale, shift, cls, pos, x, np, D);
+        return p3_launch<tokens_assemble_kernel<T>>(p3_kname<T>("tokens_assemble_kernel"), dim3(grid_for(total)), dim3(256), 0, s, (const T*)src, src_ld, scale,
+                                                    shift, cls, pos, x, B, np, D);
+    });
 }
 
 extern "C" int p3_pool_pos(const void* y, int dtype_in, const float* pos, void* out, void* out_nopos, int dtype_out, int B, int np, int Din,
@@ -451,30 +429,21 @@ extern "C" int p3_pool_pos(const void* y, int dtype_in, const float* pos, void* 
     P3_CHECK(y && out && B > 0 && Dout > 0 && Din >= Dout, P3_EINVAL, "p3_pool_pos: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     const int64_t total = (int64_t)B * np * Dout;
-    if (Dout <= 1024 && (int64_t)Din * Dout < (1ll << 30)) {
-        const int64_t rows = (int64_t)B * np;
-        const int rpb = (int)p3_ceil_div(rows, 2048) < 8 ? 8 : (int)p3_ceil_div(rows, 2048);
-        dim3 g2((unsigned)p3_ceil_div(rows, rpb)), b2((unsigned)((Dout + 63) / 64 * 64));
-#define P3_POOL_ROWS(TI, TO) hipLaunchKernelGGL((pool_pos_rows_kernel<TI, TO>), g2, b2, 0, s, (const TI*)y, pos, (TO*)out, (TO*)out_nopos, rows, np, Din, Dout, rpb)
-        if (p3_tracing()) p3_note_kernel(pool_pos_name(true, dtype_in, dtype_out));
-        if (dtype_in == P3_F32 && dtype_out == P3_F32) P3_POOL_ROWS(float, float);
-        else if (dtype_in == P3_F32 && dtype_out == P3_BF16) P3_POOL_ROWS(float, bf16_t);
-        else if (dtype_in == P3_BF16 && dtype_out == P3_BF16) P3_POOL_ROWS(bf16_t, bf16_t);
-        else if (dtype_in == P3_BF16 && dtype_out == P3_F32) P3_POOL_ROWS(bf16_t, float);
-        else { p3_set_error("p3_pool_pos: dtype"); return P3_EUNSUP; }
-#undef P3_POOL_ROWS
-        P3_LAUNCH_CHECK();
-        return P3_OK;
-    }
-    dim3 g(grid_for(total)), b(256);
-    if (p3_tracing()) p3_note_kernel(pool_pos_name(false, dtype_in, dtype_out));
-    if (dtype_in == P3_F32 && dtype_out == P3_F32) hipLaunchKernelGGL((pool_pos_kernel<float, float>), g, b, 0, s, (const float*)y, pos, (float*)out, (float*)out_nopos, B, np, Din, Dout);
-    else if (dtype_in == P3_F32 && dtype_out == P3_BF16) hipLaunchKernelGGL((pool_pos_kernel<float, bf16_t>), g, b, 0, s, (const float*)y, pos, (bf16_t*)out, (bf16_t*)out_nopos, B, np, Din, Dout);
-    else if (dtype_in == P3_BF16 && dtype_out == P3_BF16) hipLaunchKernelGGL((pool_pos_kernel<bf16_t, bf16_t>), g, b, 0, s, (const bf16_t*)y, pos, (bf16_t*)out, (bf16_t*)out_nopos, B, np, Din, Dout);
-    else if (dtype_in == P3_BF16 && dtype_out == P3_F32) hipLaunchKernelGGL((pool_pos_kernel<bf16_t, float>), g, b, 0, s, (const bf16_t*)y, pos, (float*)out, (float*)out_nopos, B, np, Din, Dout);
-    else { p3_set_error("p3_pool_pos: dtype"); return P3_EUNSUP; }
-    P3_LAUNCH_CHECK();
-    return P3_OK;
+    return p3_by_dtype(dtype_in, false, "p3_pool_pos", [&](auto ti) {
+        return p3_by_dtype(dtype_out, false, "p3_pool_pos", [&](auto to) {
+            using TI = typename decltype(ti)::type;
+            using TO = typename decltype(to)::type;
+            if (Dout <= 1024 && (int64_t)Din * Dout < (1ll << 30)) {
+                const int64_t rows = (int64_t)B * np;
+                const int rpb = (int)p3_ceil_div(rows, 2048) < 8 ? 8 : (int)p3_ceil_div(rows, 2048);
+                return p3_launch<pool_pos_rows_kernel<TI, TO>>(p3_kname<TI, TO>("pool_pos_rows_kernel"), dim3((unsigned)p3_ceil_div(rows, rpb)),
+                                                               dim3((unsigned)((Dout + 63) / 64 * 64)), 0, s, (const TI*)y, pos, (TO*)out, (TO*)out_nopos, rows,
+                                                               np, Din, Dout, rpb);
+            }
+            return p3_launch<pool_pos_kernel<TI, TO>>(p3_kname<TI, TO>("pool_pos_kernel"), dim3(grid_for(total)), dim3(256), 0, s, (const TI*)y, pos, (TO*)out,
+                                                      (TO*)out_nopos, B, np, Din, Dout);
+        });
+    });
 }
 
 extern "C" int p3_embed_tokens(const int64_t* tokens, const float* emb, const float* pos, void* x, float* key_bias, int B, int L, int D,
@@ -482,31 +451,32 @@ extern "C" int p3_embed_tokens(const int64_t* tokens, const float* emb, const fl
     P3_CHECK(tokens && emb && pos && x && B > 0, P3_EINVAL, "p3_embed_tokens: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     const int64_t total = (int64_t)B * L * D;
-    DISPATCH_T(dtype_out, hipLaunchKernelGGL((embed_tokens_kernel<bf16_t>), dim3(grid_for(total)), dim3(256), 0, s, tokens, emb, pos, (bf16_t*)x, key_bias, B, L, D, pad_idx),
-               hipLaunchKernelGGL((embed_tokens_kernel<float>), dim3(grid_for(total)), dim3(256), 0, s, tokens, emb, pos, (float*)x, key_bias, B, L, D, pad_idx), "p3_embed_tokens");
-    P3_LAUNCH_CHECK();
-    return P3_OK;
+    return p3_by_dtype(dtype_out, false, "p3_embed_tokens", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return p3_launch<embed_tokens_kernel<T>>(nullptr, dim3(grid_for(total)), dim3(256), 0, s, tokens, emb, pos, (T*)x, key_bias, B, L, D, pad_idx);
+    });
 }
 
 extern "C" int p3_pair_mean(const void* feats, void* out, int B, int L, int N, int D, int dtype, void* stream) {
     P3_CHECK(feats && out && B > 0 && L >= 2 * N + 1, P3_ESHAPE, "p3_pair_mean: need L >= 2N+1");
     hipStream_t s = (hipStream_t)stream;
     const int64_t total = (int64_t)B * N * D;
-    DISPATCH_T(dtype, hipLaunchKernelGGL((pair_mean_kernel<bf16_t>), dim3(grid_for(total)), dim3(256), 0, s, (const bf16_t*)feats, (bf16_t*)out, B, L, N, D),
-               hipLaunchKernelGGL((pair_mean_kernel<float>), dim3(grid_for(total)), dim3(256), 0, s, (const float*)feats, (float*)out, B, L, N, D), "p3_pair_mean");
-    P3_LAUNCH_CHECK();
-    return P3_OK;
+    return p3_by_dtype(dtype, false, "p3_pair_mean", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return p3_launch<pair_mean_kernel<T>>(nullptr, dim3(grid_for(total)), dim3(256), 0, s, (const T*)feats, (T*)out, B, L, N, D);
+    });
 }
 
 extern "C" int p3_pair_stats(const void* U, const void* V, int B, int N, int C, int dtype, float* sums, void* stream) {
     P3_CHECK(U && V && sums && B > 0, P3_EINVAL, "p3_pair_stats: bad arguments");
     hipStream_t s = (hipStream_t)stream;
-    float* slab = p3_det_scratch((int64_t)B * 2 * C, dtype);
-    DISPATCH_T(dtype, hipLaunchKernelGGL((pair_stats_kernel<bf16_t>), dim3(B), dim3(256), 0, s, (const bf16_t*)U, (const bf16_t*)V, N, C, sums, slab),
-               hipLaunchKernelGGL((pair_stats_kernel<float>), dim3(B), dim3(256), 0, s, (const float*)U, (const float*)V, N, C, sums, slab), "p3_pair_stats");
-    P3_LAUNCH_CHECK();
-    if (slab) return p3_det_reduce(slab, B, 2 * (int64_t)C, sums, 2 * C, 1, s);
-    return P3_OK;
+    return p3_by_dtype(dtype, false, "p3_pair_stats", [&](auto t) {
+        using T = typename decltype(t)::type;
+        float* slab = p3_det_scratch((int64_t)B * 2 * C, dtype);
+        const int rc = p3_launch<pair_stats_kernel<T>>(nullptr, dim3(B), dim3(256), 0, s, (const T*)U, (const T*)V, N, C, sums, slab);
+        if (rc != P3_OK || !slab) return rc;
+        return p3_det_reduce(slab, B, 2 * (int64_t)C, sums, 2 * C, 1, s);
+    });
 }
 
 extern "C" int p3_bn_finalize(const float* sums, int C, float count, const float* gamma, const float* beta, float* running_mean,
@@ -526,17 +496,14 @@ extern "C" int p3_score_out(const void* H3, int dtype, const float* scale, const
     P3_CHECK(C == 64, P3_EUNSUP, "p3_score_out: ScoreNet conv3 width must be 64 (model_pix2poly.py:78)");
     hipStream_t s = (hipStream_t)stream;
     const int64_t total = (int64_t)B * N * N;
-    if (dtype == P3_BF16 && C == 64 && ((uintptr_t)H3 % 16) == 0) {
-        if (p3_tracing()) p3_note_kernel("score_out64_kernel");
-        hipLaunchKernelGGL(score_out64_kernel, dim3(grid_for(total * 8)), dim3(256), 0, s, (const bf16_t*)H3, scale, shift, w4, b4, out, B, N, transpose_accumulate);
-        P3_LAUNCH_CHECK();
-        return P3_OK;
-    }
-    if (p3_tracing()) p3_note_kernel(dtype == P3_BF16 ? "score_out_kernel<bf16>" : "score_out_kernel<float>");
-    DISPATCH_T(dtype, hipLaunchKernelGGL((score_out_kernel<bf16_t>), dim3(grid_for(total)), dim3(256), 0, s, (const bf16_t*)H3, scale, shift, w4, b4, out, B, N, C, transpose_accumulate),
-               hipLaunchKernelGGL((score_out_kernel<float>), dim3(grid_for(total)), dim3(256), 0, s, (const float*)H3, scale, shift, w4, b4, out, B, N, C, transpose_accumulate), "p3_score_out");
-    P3_LAUNCH_CHECK();
-    return P3_OK;
+    if (dtype == P3_BF16 && ((uintptr_t)H3 % 16) == 0)
+        return p3_launch<score_out64_kernel>("score_out64_kernel", dim3(grid_for(total * 8)), dim3(256), 0, s, (const bf16_t*)H3, scale, shift, w4, b4, out, B, N,
+                                             transpose_accumulate);
+    return p3_by_dtype(dtype, false, "p3_score_out", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return p3_launch<score_out_kernel<T>>(p3_kname<T>("score_out_kernel"), dim3(grid_for(total)), dim3(256), 0, s, (const T*)H3, scale, shift, w4, b4, out, B,
+                                              N, C, transpose_accumulate);
+    });
 }
 
 extern "C" int p3_argmax(const float* x, int64_t* out, int rows, int cols, int ld, void* stream) {
@@ -550,24 +517,23 @@ extern "C" int p3_cast(const void* a, int dtype_a, void* b, int dtype_b, int64_t
     if (n == 0) return P3_OK;                                   // an empty tensor may have no storage (NULL data pointer)
     P3_CHECK(a && b && n > 0, P3_EINVAL, "p3_cast: bad arguments");
     hipStream_t s = (hipStream_t)stream;
-    dim3 g(grid_for(n)), blk(256);
-    if (dtype_a == P3_F32 && dtype_b == P3_BF16) hipLaunchKernelGGL((cast_kernel<float, bf16_t>), g, blk, 0, s, (const float*)a, (bf16_t*)b, n);
-    else if (dtype_a == P3_BF16 && dtype_b == P3_F32) hipLaunchKernelGGL((cast_kernel<bf16_t, float>), g, blk, 0, s, (const bf16_t*)a, (float*)b, n);
-    else if (dtype_a == P3_F32 && dtype_b == P3_F32) hipLaunchKernelGGL((cast_kernel<float, float>), g, blk, 0, s, (const float*)a, (float*)b, n);
-    else if (dtype_a == P3_BF16 && dtype_b == P3_BF16) hipLaunchKernelGGL((cast_kernel<bf16_t, bf16_t>), g, blk, 0, s, (const bf16_t*)a, (bf16_t*)b, n);
-    else { p3_set_error("p3_cast: dtype"); return P3_EUNSUP; }
-    P3_LAUNCH_CHECK();
-    return P3_OK;
+    return p3_by_dtype(dtype_a, false, "p3_cast", [&](auto ta) {
+        return p3_by_dtype(dtype_b, false, "p3_cast", [&](auto tb) {
+            using TA = typename decltype(ta)::type;
+            using TB = typename decltype(tb)::type;
+            return p3_launch<cast_kernel<TA, TB>>(nullptr, dim3(grid_for(n)), dim3(256), 0, s, (const TA*)a, (TB*)b, n);
+        });
+    });
 }
 
 extern "C" int p3_add_pos(const void* x, const float* pos, void* out, int B, int L, int D, int dtype, void* stream) {
     P3_CHECK(x && pos && out && B > 0, P3_EINVAL, "p3_add_pos: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     const int64_t total = (int64_t)B * L * D, LD = (int64_t)L * D;
-    DISPATCH_T(dtype, hipLaunchKernelGGL((add_pos_kernel<bf16_t>), dim3(grid_for(total)), dim3(256), 0, s, (const bf16_t*)x, pos, (bf16_t*)out, total, LD),
-               hipLaunchKernelGGL((add_pos_kernel<float>), dim3(grid_for(total)), dim3(256), 0, s, (const float*)x, pos, (float*)out, total, LD), "p3_add_pos");
-    P3_LAUNCH_CHECK();
-    return P3_OK;
+    return p3_by_dtype(dtype, false, "p3_add_pos", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return p3_launch<add_pos_kernel<T>>(nullptr, dim3(grid_for(total)), dim3(256), 0, s, (const T*)x, pos, (T*)out, total, LD);
+    });
 }
 
 extern "C" int p3_rng_advance(unsigned long long* seed, void* stream) {
@@ -583,15 +549,14 @@ extern "C" int p3_dropout_apply(const void* in, int dtype_in, void* out, int dty
     P3_CHECK(drop->p >= 0.f && drop->p < 1.f, P3_EINVAL, "p3_dropout_apply: p must be in [0, 1)");
     if (n == 0) return P3_OK;
     hipStream_t s = (hipStream_t)stream;
-    dim3 g(grid_for(n)), blk(256);
     const p3_dropout dr = *drop;
-    if (dtype_in == P3_F32 && dtype_out == P3_BF16) hipLaunchKernelGGL((dropout_apply_kernel<float, bf16_t>), g, blk, 0, s, (const float*)in, (bf16_t*)out, n, ncols, dr);
-    else if (dtype_in == P3_BF16 && dtype_out == P3_F32) hipLaunchKernelGGL((dropout_apply_kernel<bf16_t, float>), g, blk, 0, s, (const bf16_t*)in, (float*)out, n, ncols, dr);
-    else if (dtype_in == P3_F32 && dtype_out == P3_F32) hipLaunchKernelGGL((dropout_apply_kernel<float, float>), g, blk, 0, s, (const float*)in, (float*)out, n, ncols, dr);
-    else if (dtype_in == P3_BF16 && dtype_out == P3_BF16) hipLaunchKernelGGL((dropout_apply_kernel<bf16_t, bf16_t>), g, blk, 0, s, (const bf16_t*)in, (bf16_t*)out, n, ncols, dr);
-    else { p3_set_error("p3_dropout_apply: dtype"); return P3_EUNSUP; }
-    P3_LAUNCH_CHECK();
-    return P3_OK;
+    return p3_by_dtype(dtype_in, false, "p3_dropout_apply", [&](auto ti) {
+        return p3_by_dtype(dtype_out, false, "p3_dropout_apply", [&](auto to) {
+            using TI = typename decltype(ti)::type;
+            using TO = typename decltype(to)::type;
+            return p3_launch<dropout_apply_kernel<TI, TO>>(nullptr, dim3(grid_for(n)), dim3(256), 0, s, (const TI*)in, (TO*)out, n, ncols, dr);
+        });
+    });
 }
 
 extern "C" int p3_transpose_many(const void* src, void* dst, const void* table, int n_entries, int total_tiles, void* stream) {

@@ -370,14 +370,14 @@ __global__ void upsample_bwd_y_kernel(const float* __restrict__ tmp, T* __restri
 extern "C" int p3_upsample_bilinear(const void* src, int dtype_src, void* dst, int dtype_dst, int B, int h, int w, int C, int H, int W, int ld,
                                     int src_tok_off, int src_tok_per_img, void* stream) {
     P3_CHECK(src && dst && B > 0 && C % 4 == 0 && ld >= C, P3_EINVAL, "p3_upsample_bilinear: bad arguments");
+    P3_CHECK(dtype_src == dtype_dst, P3_EUNSUP, "p3_upsample_bilinear: dtype");            // the kernel exists for equal types only
     hipStream_t s = (hipStream_t)stream;
     const int64_t total = (int64_t)B * H * W * (C / 4);
-    dim3 g(grid_for(total)), b(256);
-    if (dtype_src == P3_BF16 && dtype_dst == P3_BF16) hipLaunchKernelGGL((upsample_bilinear_kernel<bf16_t, bf16_t>), g, b, 0, s, (const bf16_t*)src, (bf16_t*)dst, B, h, w, C, H, W, ld, src_tok_off, src_tok_per_img);
-    else if (dtype_src == P3_F32 && dtype_dst == P3_F32) hipLaunchKernelGGL((upsample_bilinear_kernel<float, float>), g, b, 0, s, (const float*)src, (float*)dst, B, h, w, C, H, W, ld, src_tok_off, src_tok_per_img);
-    else { p3_set_error("p3_upsample_bilinear: dtype"); return P3_EUNSUP; }
-    P3_LAUNCH_CHECK();
-    return P3_OK;
+    return p3_by_dtype(dtype_src, false, "p3_upsample_bilinear", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return p3_launch<upsample_bilinear_kernel<T, T>>(nullptr, dim3(grid_for(total)), dim3(256), 0, s, (const T*)src, (T*)dst, B, h, w, C, H, W, ld, src_tok_off,
+                                                         src_tok_per_img);
+    });
 }
 
 extern "C" int p3_head1x1(const void* X, int ld, int dtype, const float* scale, const float* shift, const float* W, const float* bias, int n_out,
@@ -385,26 +385,24 @@ extern "C" int p3_head1x1(const void* X, int ld, int dtype, const float* scale, 
                           void* stream) {
     P3_CHECK(X && scale && shift && W && bias && out_nchw && R > 0 && (n_out == 1 || n_out == 4), P3_EINVAL, "p3_head1x1: bad arguments (C = 256, n_out in {1, 4})");
     hipStream_t s = (hipStream_t)stream;
-    dim3 g(grid_for(R * 64)), b(256);
-#define H1(T, N) hipLaunchKernelGGL((head1x1_kernel<T, N>), g, b, 0, s, (const T*)X, ld, scale, shift, W, bias, act, post_mul, out_nchw, (T*)copy_dst, copy_ld, R, HW)
-    if (dtype == P3_BF16) { if (n_out == 1) H1(bf16_t, 1); else H1(bf16_t, 4); }
-    else if (dtype == P3_F32) { if (n_out == 1) H1(float, 1); else H1(float, 4); }
-    else { p3_set_error("p3_head1x1: dtype"); return P3_EUNSUP; }
-#undef H1
-    P3_LAUNCH_CHECK();
-    return P3_OK;
+    return p3_by_dtype(dtype, false, "p3_head1x1", [&](auto t) {
+        using T = typename decltype(t)::type;
+        const auto go = [&](auto n) {
+            return p3_launch<head1x1_kernel<T, decltype(n)::value>>(nullptr, dim3(grid_for(R * 64)), dim3(256), 0, s, (const T*)X, ld, scale, shift, W, bias, act,
+                                                                    post_mul, out_nchw, (T*)copy_dst, copy_ld, R, HW);
+        };
+        return n_out == 1 ? go(std::integral_constant<int, 1>{}) : go(std::integral_constant<int, 4>{});
+    });
 }
 
 extern "C" int p3_nhwc_to_nchw(const void* X, int ld, int dtype, const float* scale, const float* shift, float* out, int B, int C, int64_t HW,
                                void* stream) {
     P3_CHECK(X && out && B > 0 && C > 0, P3_EINVAL, "p3_nhwc_to_nchw: bad arguments");
     hipStream_t s = (hipStream_t)stream;
-    dim3 g((unsigned)((HW + 31) / 32), (C + 31) / 32, B), b(256);
-    if (dtype == P3_BF16) hipLaunchKernelGGL((nhwc_to_nchw_kernel<bf16_t>), g, b, 0, s, (const bf16_t*)X, ld, scale, shift, out, C, HW);
-    else if (dtype == P3_F32) hipLaunchKernelGGL((nhwc_to_nchw_kernel<float>), g, b, 0, s, (const float*)X, ld, scale, shift, out, C, HW);
-    else { p3_set_error("p3_nhwc_to_nchw: dtype"); return P3_EUNSUP; }
-    P3_LAUNCH_CHECK();
-    return P3_OK;
+    return p3_by_dtype(dtype, false, "p3_nhwc_to_nchw", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return p3_launch<nhwc_to_nchw_kernel<T>>(nullptr, dim3((unsigned)((HW + 31) / 32), (C + 31) / 32, B), dim3(256), 0, s, (const T*)X, ld, scale, shift, out, C, HW);
+    });
 }
 
 extern "C" int p3_head1x1_bwd(const void* H, int dtype, const float* scale, const float* shift, const float* mean, const float* W, int n_out,
@@ -412,78 +410,72 @@ extern "C" int p3_head1x1_bwd(const void* H, int dtype, const float* scale, cons
                               void* stream) {
     P3_CHECK(H && scale && shift && mean && W && out_nchw && dout_nchw && dHd && acc && R > 0 && HW > 0, P3_EINVAL, "p3_head1x1_bwd: bad arguments");
     P3_CHECK(n_out == 1 || n_out == 4, P3_EUNSUP, "p3_head1x1_bwd: n_out must be 1 or 4");
-    P3_CHECK(dtype == P3_BF16 || dtype == P3_F32, P3_EUNSUP, "p3_head1x1_bwd: dtype");
     hipStream_t s = (hipStream_t)stream;
     int64_t gr = (R + 3) / 4; if (gr > 2048) gr = 2048;
-    dim3 g((int)gr), b(256);
     const int nv = 512 + n_out * 256 + n_out;
-    float* slab = p3_det_scratch(gr * nv, dtype);
-#define HB(T, NO) hipLaunchKernelGGL((head1x1_bwd_kernel<T, NO>), g, b, 0, s, (const T*)H, scale, shift, mean, W, out_nchw, dout_nchw, act, post_mul, (T*)dHd, acc, slab, R, HW)
-    if (dtype == P3_BF16) { if (n_out == 1) HB(bf16_t, 1); else HB(bf16_t, 4); }
-    else { if (n_out == 1) HB(float, 1); else HB(float, 4); }
-#undef HB
-    P3_LAUNCH_CHECK();
-    if (slab) return p3_det_reduce(slab, (int)gr, nv, acc, nv, 1, s);
-    return P3_OK;
+    return p3_by_dtype(dtype, false, "p3_head1x1_bwd", [&](auto t) {
+        using T = typename decltype(t)::type;
+        float* slab = p3_det_scratch(gr * nv, dtype);
+        const auto go = [&](auto n) {
+            return p3_launch<head1x1_bwd_kernel<T, decltype(n)::value>>(nullptr, dim3((int)gr), dim3(256), 0, s, (const T*)H, scale, shift, mean, W, out_nchw, dout_nchw,
+                                                                        act, post_mul, (T*)dHd, acc, slab, R, HW);
+        };
+        const int rc = n_out == 1 ? go(std::integral_constant<int, 1>{}) : go(std::integral_constant<int, 4>{});
+        if (rc != P3_OK || !slab) return rc;
+        return p3_det_reduce(slab, (int)gr, nv, acc, nv, 1, s);
+    });
 }
 
 extern "C" int p3_affine_relu_bwd256(const void* dA, const void* H, int ldh, int dtype, const float* scale, const float* shift, const float* mean,
                                      void* dHd, float* acc, int64_t R, void* stream) {
     P3_CHECK(dA && H && scale && shift && mean && dHd && acc && R > 0 && ldh >= 256 && ldh % 4 == 0, P3_EINVAL, "p3_affine_relu_bwd256: bad arguments");
-    P3_CHECK(dtype == P3_BF16 || dtype == P3_F32, P3_EUNSUP, "p3_affine_relu_bwd256: dtype");
     hipStream_t s = (hipStream_t)stream;
     int64_t gr = (R + 3) / 4; if (gr > 2048) gr = 2048;
-    float* slab = p3_det_scratch(gr * 512, dtype);
-    if (dtype == P3_BF16) hipLaunchKernelGGL((affine_relu_bwd256_kernel<bf16_t>), dim3((int)gr), dim3(256), 0, s, (const bf16_t*)dA, (const bf16_t*)H, ldh, scale, shift, mean, (bf16_t*)dHd, acc, slab, R);
-    else hipLaunchKernelGGL((affine_relu_bwd256_kernel<float>), dim3((int)gr), dim3(256), 0, s, (const float*)dA, (const float*)H, ldh, scale, shift, mean, (float*)dHd, acc, slab, R);
-    P3_LAUNCH_CHECK();
-    if (slab) return p3_det_reduce(slab, (int)gr, 512, acc, 512, 1, s);
-    return P3_OK;
+    return p3_by_dtype(dtype, false, "p3_affine_relu_bwd256", [&](auto t) {
+        using T = typename decltype(t)::type;
+        float* slab = p3_det_scratch(gr * 512, dtype);
+        const int rc = p3_launch<affine_relu_bwd256_kernel<T>>(nullptr, dim3((int)gr), dim3(256), 0, s, (const T*)dA, (const T*)H, ldh, scale, shift, mean, (T*)dHd, acc,
+                                                               slab, R);
+        if (rc != P3_OK || !slab) return rc;
+        return p3_det_reduce(slab, (int)gr, 512, acc, 512, 1, s);
+    });
 }
 
 extern "C" int p3_pad_nhwc(const void* src, int ld_src, int dtype, const float* scale, const float* shift, int c_aff, int C, int Cp, void* dst, int B, int H,
                            int W, void* stream) {
     P3_CHECK(src && dst && B > 0 && H > 0 && W > 0 && C > 0 && Cp >= C && Cp % 4 == 0 && c_aff <= C, P3_EINVAL, "p3_pad_nhwc: bad arguments");
     P3_CHECK((scale == nullptr) == (shift == nullptr), P3_EINVAL, "p3_pad_nhwc: scale and shift go together");
-    P3_CHECK(dtype == P3_BF16 || dtype == P3_F32, P3_EUNSUP, "p3_pad_nhwc: dtype");
     hipStream_t s = (hipStream_t)stream;
     if (dtype == P3_BF16 && C % 8 == 0 && c_aff % 8 == 0 && Cp % 8 == 0 && ld_src % 8 == 0 && ((uintptr_t)src % 16) == 0 && ((uintptr_t)dst % 16) == 0 &&
         (!scale || (((uintptr_t)scale % 16) == 0 && ((uintptr_t)shift % 16) == 0))) {
         const int64_t tot = (int64_t)B * (H + 2) * (W + 2) * (Cp / 8);
         int64_t g = (tot + 255) / 256; if (g > 65536) g = 65536;
-        if (p3_tracing()) p3_note_kernel("pad_nhwc_vec_kernel");
-        hipLaunchKernelGGL(pad_nhwc_vec_kernel, dim3((int)g), dim3(256), 0, s, (const bf16_t*)src, ld_src, scale, shift, c_aff, C, Cp, (bf16_t*)dst, B, H, W);
-        P3_LAUNCH_CHECK();
-        return P3_OK;
+        return p3_launch<pad_nhwc_vec_kernel>("pad_nhwc_vec_kernel", dim3((int)g), dim3(256), 0, s, (const bf16_t*)src, ld_src, scale, shift, c_aff, C, Cp, (bf16_t*)dst,
+                                              B, H, W);
     }
-    const size_t es = dtype == P3_BF16 ? 2 : 4;
-    hipError_t e = hipMemsetAsync(dst, 0, (size_t)B * (H + 2) * (W + 2) * Cp * es, s);
-    if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
-    const int64_t total = (int64_t)B * H * W * (Cp / 4);
-    int64_t gr = (total + 255) / 256; if (gr > 16384) gr = 16384;
-    if (p3_tracing()) p3_note_kernel(dtype == P3_BF16 ? "pad_nhwc_kernel<bf16>" : "pad_nhwc_kernel<float>");
-    if (dtype == P3_BF16) hipLaunchKernelGGL((pad_nhwc_kernel<bf16_t>), dim3((int)gr), dim3(256), 0, s, (const bf16_t*)src, ld_src, scale, shift, c_aff, C, Cp, (bf16_t*)dst, B, H, W);
-    else hipLaunchKernelGGL((pad_nhwc_kernel<float>), dim3((int)gr), dim3(256), 0, s, (const float*)src, ld_src, scale, shift, c_aff, C, Cp, (float*)dst, B, H, W);
-    P3_LAUNCH_CHECK();
-    return P3_OK;
+    return p3_by_dtype(dtype, false, "p3_pad_nhwc", [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipError_t e = hipMemsetAsync(dst, 0, (size_t)B * (H + 2) * (W + 2) * Cp * sizeof(T), s);
+        if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
+        const int64_t total = (int64_t)B * H * W * (Cp / 4);
+        int64_t gr = (total + 255) / 256; if (gr > 16384) gr = 16384;
+        return p3_launch<pad_nhwc_kernel<T>>(p3_kname<T>("pad_nhwc_kernel"), dim3((int)gr), dim3(256), 0, s, (const T*)src, ld_src, scale, shift, c_aff, C, Cp, (T*)dst, B,
+                                             H, W);
+    });
 }
 
 extern "C" int p3_upsample_bilinear_bwd(const void* dUp, int dtype, float* tmp, void* dtok, int B, int h, int w, int C, int H, int W, int tok_off,
                                         int tok_per_img, void* stream) {
     P3_CHECK(dUp && tmp && dtok && B > 0 && C % 4 == 0 && H >= h && W >= w, P3_EINVAL, "p3_upsample_bilinear_bwd: bad arguments");
-    P3_CHECK(dtype == P3_BF16 || dtype == P3_F32, P3_EUNSUP, "p3_upsample_bilinear_bwd: dtype");
     hipStream_t s = (hipStream_t)stream;
     const int64_t t1 = (int64_t)B * H * w * (C / 4), t2 = (int64_t)B * h * w * (C / 4);
     int64_t g1 = (t1 + 255) / 256, g2 = (t2 + 255) / 256;
     if (g1 > 16384) g1 = 16384;
     if (g2 > 16384) g2 = 16384;
-    if (dtype == P3_BF16) {
-        hipLaunchKernelGGL((upsample_bwd_x_kernel<bf16_t>), dim3((int)g1), dim3(256), 0, s, (const bf16_t*)dUp, tmp, B, H, W, w, C);
-        hipLaunchKernelGGL((upsample_bwd_y_kernel<bf16_t>), dim3((int)g2), dim3(256), 0, s, tmp, (bf16_t*)dtok, B, H, h, w, C, tok_off, tok_per_img);
-    } else {
-        hipLaunchKernelGGL((upsample_bwd_x_kernel<float>), dim3((int)g1), dim3(256), 0, s, (const float*)dUp, tmp, B, H, W, w, C);
-        hipLaunchKernelGGL((upsample_bwd_y_kernel<float>), dim3((int)g2), dim3(256), 0, s, tmp, (float*)dtok, B, H, h, w, C, tok_off, tok_per_img);
-    }
-    P3_LAUNCH_CHECK();
-    return P3_OK;
+    return p3_by_dtype(dtype, false, "p3_upsample_bilinear_bwd", [&](auto t) {
+        using T = typename decltype(t)::type;
+        const int rc = p3_launch<upsample_bwd_x_kernel<T>>(nullptr, dim3((int)g1), dim3(256), 0, s, (const T*)dUp, tmp, B, H, W, w, C);
+        if (rc != P3_OK) return rc;
+        return p3_launch<upsample_bwd_y_kernel<T>>(nullptr, dim3((int)g2), dim3(256), 0, s, tmp, (T*)dtok, B, H, h, w, C, tok_off, tok_per_img);
+    });
 }

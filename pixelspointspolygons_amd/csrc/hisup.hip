@@ -85,13 +85,11 @@ __global__ void eca_gate_kernel(const float* __restrict__ y, const float* __rest
 
 extern "C" int p3_nchw_to_nhwc(const float* X, void* out, int ld, int dtype, int B, int C, int64_t HW, void* stream) {
     P3_CHECK(X && out && B > 0 && C > 0 && HW > 0 && ld >= C, P3_EINVAL, "p3_nchw_to_nhwc: bad arguments");
-    dim3 g((unsigned)((HW + 31) / 32), (C + 31) / 32, B), b(256);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == P3_BF16) hipLaunchKernelGGL((nchw_to_nhwc_kernel<bf16_t>), g, b, 0, s, X, (bf16_t*)out, ld, C, HW);
-    else if (dtype == P3_F32) hipLaunchKernelGGL((nchw_to_nhwc_kernel<float>), g, b, 0, s, X, (float*)out, ld, C, HW);
-    else { p3_set_error("p3_nchw_to_nhwc: dtype"); return P3_EUNSUP; }
-    P3_LAUNCH_CHECK();
-    return P3_OK;
+    return p3_by_dtype(dtype, false, "p3_nchw_to_nhwc", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return p3_launch<nchw_to_nhwc_kernel<T>>(nullptr, dim3((unsigned)((HW + 31) / 32), (C + 31) / 32, B), dim3(256), 0, s, X, (T*)out, ld, C, HW);
+    });
 }
 
 extern "C" int p3_affine_relu_mix(void* out, int ld_out, const void* a, int ld_a, const float* scale_a, const float* shift_a, const float* gate,
@@ -101,12 +99,11 @@ extern "C" int p3_affine_relu_mix(void* out, int ld_out, const void* a, int ld_a
     P3_CHECK((scale_a == nullptr) == (shift_a == nullptr) && (scale_b == nullptr) == (shift_b == nullptr), P3_EINVAL, "p3_affine_relu_mix: scale and shift go together");
     P3_CHECK(b || (!scale_b && ld_b == 0), P3_EINVAL, "p3_affine_relu_mix: second source missing");
     hipStream_t s = (hipStream_t)stream;
-    const int g = hs_grid(R * C);
-    if (dtype == P3_BF16) hipLaunchKernelGGL((mix_kernel<bf16_t>), dim3(g), dim3(256), 0, s, (bf16_t*)out, ld_out, (const bf16_t*)a, ld_a, scale_a, shift_a, gate, (const bf16_t*)b, ld_b, scale_b, shift_b, R, C, HW);
-    else if (dtype == P3_F32) hipLaunchKernelGGL((mix_kernel<float>), dim3(g), dim3(256), 0, s, (float*)out, ld_out, (const float*)a, ld_a, scale_a, shift_a, gate, (const float*)b, ld_b, scale_b, shift_b, R, C, HW);
-    else { p3_set_error("p3_affine_relu_mix: dtype"); return P3_EUNSUP; }
-    P3_LAUNCH_CHECK();
-    return P3_OK;
+    return p3_by_dtype(dtype, false, "p3_affine_relu_mix", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return p3_launch<mix_kernel<T>>(nullptr, dim3(hs_grid(R * C)), dim3(256), 0, s, (T*)out, ld_out, (const T*)a, ld_a, scale_a, shift_a, gate, (const T*)b, ld_b,
+                                        scale_b, shift_b, R, C, HW);
+    });
 }
 
 extern "C" int p3_eca_gate(const void* a1, int ld1, const float* scale1, const float* shift1, const void* a2, int ld2, const float* scale2,
@@ -114,12 +111,11 @@ extern "C" int p3_eca_gate(const void* a1, int ld1, const float* scale1, const f
     P3_CHECK(a1 && a2 && scale1 && shift1 && scale2 && shift2 && conv_w && pooled && gate && B > 0 && HW > 0 && C > 0 && k > 0 && (k & 1), P3_EINVAL,
              "p3_eca_gate: bad arguments (odd kernel size)");
     hipStream_t s = (hipStream_t)stream;
-    dim3 g(B, (C + 63) / 64), b(256);
-    if (dtype == P3_BF16) hipLaunchKernelGGL((eca_pool_kernel<bf16_t>), g, b, 0, s, (const bf16_t*)a1, ld1, scale1, shift1, (const bf16_t*)a2, ld2, scale2, shift2, pooled, HW, C);
-    else if (dtype == P3_F32) hipLaunchKernelGGL((eca_pool_kernel<float>), g, b, 0, s, (const float*)a1, ld1, scale1, shift1, (const float*)a2, ld2, scale2, shift2, pooled, HW, C);
-    else { p3_set_error("p3_eca_gate: dtype"); return P3_EUNSUP; }
-    P3_LAUNCH_CHECK();
-    hipLaunchKernelGGL(eca_gate_kernel, dim3((B * C + 255) / 256), dim3(256), 0, s, pooled, conv_w, k, gate, B, C);
-    P3_LAUNCH_CHECK();
-    return P3_OK;
+    return p3_by_dtype(dtype, false, "p3_eca_gate", [&](auto t) {
+        using T = typename decltype(t)::type;
+        const int rc = p3_launch<eca_pool_kernel<T>>(nullptr, dim3(B, (C + 63) / 64), dim3(256), 0, s, (const T*)a1, ld1, scale1, shift1, (const T*)a2, ld2, scale2,
+                                                     shift2, pooled, HW, C);
+        if (rc != P3_OK) return rc;
+        return p3_launch<eca_gate_kernel>(nullptr, dim3((B * C + 255) / 256), dim3(256), 0, s, pooled, conv_w, k, gate, B, C);
+    });
 }

@@ -2,7 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <string.h>
+#include <type_traits>
 
 #include "../../include/p3hip.h"
 #include "gfx950_asm.h"          // LDS-DMA, waits, lds_barrier(), the transposing LDS read: all shared inline asm
@@ -197,7 +199,32 @@ int p3_det_reduce2(const float* parts, int nparts, int64_t stride, float* tmp, f
         }                                              \
     } while (0)
 
-// ---- one launch path for the kernels with more than the default dynamic LDS ---------------------------------------------------------------------
+// ---- dtype code -> template argument ---------------------------------------------------------------------------------------------------------------
+// p3_by_dtype(dtype, x3_is_f32, "p3_entry", [&](auto t) { using T = typename decltype(t)::type; ... return status; }): calls f(p3_type<bf16_t>{}) or
+// f(p3_type<float>{}) by the STORAGE type of the code and returns f's int.  P3_F32X3 is fp32 storage and is taken only where `x3_is_f32` says the entry
+// accepts it.  Any other code: "<who>: dtype", P3_EUNSUP, f is not called - so nothing launches.  Two dtypes nest two calls.
+template <typename T> struct p3_type { using type = T; };
+template <typename F>
+static inline int p3_by_dtype(int dtype, bool x3_is_f32, const char* who, F&& f) {
+    if (dtype == P3_BF16) return f(p3_type<bf16_t>{});
+    if (dtype == P3_F32 || (dtype == P3_F32X3 && x3_is_f32)) return f(p3_type<float>{});
+    char msg[96];
+    snprintf(msg, sizeof(msg), "%s: dtype", who);
+    p3_set_error(msg);
+    return P3_EUNSUP;
+}
+template <typename T> constexpr const char* p3_dtype_name() { return sizeof(T) == sizeof(bf16_t) ? "bf16" : "float"; }
+// the name a typed launch records while tracing, "kernel<bf16>" or "kernel<float, bf16>"; NULL (p3_launch records nothing) when nobody traces
+template <typename T, typename T2 = void>
+static inline const char* p3_kname(const char* kernel) {
+    if (!p3_tracing()) return nullptr;
+    static thread_local char s[96];
+    if constexpr (!__is_same(T2, void)) snprintf(s, sizeof(s), "%s<%s, %s>", kernel, p3_dtype_name<T>(), p3_dtype_name<T2>());
+    else snprintf(s, sizeof(s), "%s<%s>", kernel, p3_dtype_name<T>());
+    return s;
+}
+
+// ---- one launch path for the kernels with more than the default dynamic LDS---------------------------------------------------------------------
 // p3_launch<kernel>(name, grid, block, lds, stream, args...): raises the kernel's dynamic-LDS limit when the launch asks for more than the 64 KB every kernel
 // may have and more than this helper already set for THIS kernel on the CURRENT device, records `name` while tracing (NULL: a site that records none),
 // launches, and returns P3_OK or the hipError_t (message in p3_set_error).  Each kernel - every template instantiation - has its own table through the

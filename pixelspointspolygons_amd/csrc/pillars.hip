@@ -1242,7 +1242,7 @@ Ws carve(void* base, const p3_pillar_desc* d) {
     w.totals = (int*)take(256);
     w.sums1 = (float*)take(2 * C1 * 4);
     w.sums2 = (float*)take(2 * (size_t)d->C * 4);
-    const size_t zero_end = off;   // [0, zero_end) is cleared every call
+    // [totals, sc1) is cleared every call
     w.sc1 = (float*)take(C1 * 4); w.sh1 = (float*)take(C1 * 4);
     w.sc2 = (float*)take((size_t)d->C * 4); w.sh2 = (float*)take((size_t)d->C * 4);
     w.m1 = (float*)take(C1 * 4); w.r1 = (float*)take(C1 * 4);
@@ -1257,8 +1257,58 @@ Ws carve(void* base, const p3_pillar_desc* d) {
     w.H2 = take(rows * (size_t)d->C * es);
     w.sort_tmp = (unsigned*)take((size_t)d->B * (SORT_SPLIT + 1) * (size_t)(d->nx + 1) * (d->ny + 1) * 2 * 4);   // the split sort's chunk histograms + cell starts
     w.bytes = off;
-    (void)zero_end;
     return w;
+}
+
+// what both directions derive from the descriptor and the workspace
+struct Stem {
+    Ws w;
+    VoxTab t;
+    int nslots, vgrid, kdt;      // pillar slots | workgroups of the per-pillar kernels (4 pillars each, <= 2048) | the dtype p3_det_scratch decides by (P3_F32X3 is fp32 storage)
+    size_t rows, es;             // rows of X2 / H2 (the points + one per slot) | bytes per stored element
+    bool lane8;                  // C <= 512: the kernels whose lanes own 8 channels (*8_kernel), else the column-group kernels (C % 64 == 0 is checked on entry)
+};
+
+Stem stem_of(void* workspace, const p3_pillar_desc* d) {
+    Stem c;
+    c.w = carve(workspace, d);
+    c.t = VoxTab{c.w.sorted, c.w.vox_xy, c.w.vox_start, c.w.vox_cnt, c.w.vox_row, c.w.nvox};
+    c.nslots = d->B * d->max_voxels;
+    c.vgrid = (c.nslots + 3) / 4 < 2048 ? (c.nslots + 3) / 4 : 2048;
+    c.kdt = d->dtype == P3_BF16 ? P3_BF16 : P3_F32;
+    c.rows = (size_t)d->total_points + (size_t)c.nslots;
+    c.es = d->dtype == P3_BF16 ? 2 : 4;
+    c.lane8 = d->C <= 512;
+    return c;
+}
+
+// the plain product [M, K] x [N, K]^T of the PFN in the stem's precision (P3_F32X3: the products as bf16 x 3, storage fp32)
+p3_gemm_desc pfn_gemm_desc(const p3_pillar_desc* d, int M, int N, int K) {
+    p3_gemm_desc gd;
+    memset(&gd, 0, sizeof(gd));
+    gd.M = M; gd.N = N; gd.K = K; gd.lda = K; gd.ldb = K; gd.ldc = N;
+    gd.dtype_in = d->dtype; gd.dtype_out = d->dtype == P3_F32X3 ? P3_F32 : d->dtype; gd.act = P3_ACT_NONE; gd.a_mode = P3_A_PLAIN;
+    return gd;
+}
+
+// The sums over workgroups: launch(slab) with a scratch slab [parts][n] when `want` and the deterministic level covers the stem's dtype - the workgroups store their
+// partials and p3_det_reduce adds them in workgroup order in float64 onto out (out2: the slab rows are [out (n / 2) | out2 (n / 2)]) - else launch(NULL): fp32 atomics.
+template <typename L>
+int pfn_partials(bool want, int parts, int n, const Stem& c, float* out, float* out2, hipStream_t s, L&& launch) {
+    float* slab = want ? p3_det_scratch((int64_t)parts * n, c.kdt) : nullptr;
+    int rc = launch(slab);
+    if (rc != P3_OK || !slab) return rc;
+    if (!out2) return p3_det_reduce(slab, parts, n, out, n, 1, s);
+    rc = p3_det_reduce(slab, parts, n, out, n / 2, 1, s);
+    return rc != P3_OK ? rc : p3_det_reduce(slab + n / 2, parts, n, out2, n / 2, 1, s);
+}
+
+// f(std::true_type{}) or f(std::false_type{}): a runtime flag as a template argument
+template <typename F> int by_flag(bool v, F&& f) { return v ? f(std::true_type{}) : f(std::false_type{}); }
+
+int hip_status(hipError_t e) {
+    if (e != hipSuccess) p3_set_error(hipGetErrorString(e));
+    return (int)e;
 }
 
 }  // namespace
@@ -1283,6 +1333,58 @@ extern "C" int64_t p3_pillar_stem_workspace_bytes(const p3_pillar_desc* d) {
     return (int64_t)carve(nullptr, d).bytes;
 }
 
+// phase 1 of the forward: clear the workspace and the canvas columns, sort the points into pillars, layer-0 BatchNorm sums (training)
+static int pfn_pillarize(const float* values, const int64_t* offsets, const float* w1, const void* w2, void* out, const p3_pillar_desc* d, const PillarGeom& g,
+                         const Stem& c, hipStream_t s) {
+    const Ws& w = c.w;
+    hipError_t e = hipMemsetAsync(w.totals, 0, (char*)w.sc1 - (char*)w.totals, s);
+    // the one-launch layer 1 without a backward reads the rows of kept pillars only: the rows of no pillar need no defined content then (0.67 GB of memset at 40 k
+    // points per tile); every other path multiplies ALL rows (the GEMM, the backward's products) and needs them finite / zero
+    const bool lean_rows = d->no_backward && pfn_layer1_fused(d, w2);
+    if (e == hipSuccess && !lean_rows) {
+        e = hipMemsetAsync(w.X2, 0, c.rows * K2 * c.es, s);   // unused rows must be finite for the GEMM
+        if (e == hipSuccess) e = hipMemsetAsync(w.F8, 0, (char*)w.row_vox - (char*)w.F8, s);
+    }
+    if (e == hipSuccess) e = hipMemsetAsync(w.row_vox, 0xFF, c.rows * 4, s);   // -1 = unused row
+    if (e != hipSuccess) return hip_status(e);
+    // zero canvas columns [col_off, col_off + C) of every token row (empty pillars stay exactly 0)
+    const size_t rowb = (size_t)d->C * c.es, ldb = (size_t)d->out_ld * c.es, offb = (size_t)d->out_col_off * c.es;
+    const int64_t nrows = (int64_t)d->B * d->nx * d->ny;
+    int rc;
+    if (rowb % 16 == 0 && ldb % 16 == 0 && offb % 16 == 0 && ((uintptr_t)out % 16) == 0) {   // 16-byte stores (the 2-D memset runs at < 1 TB/s)
+        const int per_row = (int)(rowb / 16);
+        const int64_t tot = nrows * per_row;
+        rc = p3_launch<zero_cols16_kernel>(nullptr, dim3((unsigned)((tot + 255) / 256 < 16384 ? (tot + 255) / 256 : 16384)), dim3(256), 0, s, (char*)out + offb,
+                                           (int64_t)ldb, per_row, tot);
+    } else {
+        rc = hip_status(hipMemset2DAsync((char*)out + offb, ldb, 0, rowb, (size_t)nrows, s));
+    }
+    if (rc != P3_OK) return rc;
+
+    SortOut so{w.sorted, w.vox_xy, w.vox_start, w.vox_cnt, w.vox_row, w.nvox, w.totals};
+    if (d->total_points >= 16 * (int64_t)c.nslots) {
+        // dense clouds: a tile's points over SORT_SPLIT workgroups (count / tables / fill)
+        unsigned* ghist = w.sort_tmp;
+        unsigned* gstart = w.sort_tmp + (size_t)d->B * SORT_SPLIT * g.nc;
+        const size_t lds_h = (size_t)SORT_WAVES * g.nc * 4, lds_t = (size_t)5 * g.nc * 4 + 32 * 4;
+        rc = p3_launch<pillar_sort_count_kernel>(nullptr, dim3(SORT_SPLIT, d->B), dim3(SORT_THREADS), lds_h, s, values, offsets, g, ghist);
+        if (rc != P3_OK) return rc;
+        rc = p3_launch<pillar_sort_tables_kernel>(nullptr, dim3(d->B), dim3(SORT_THREADS), lds_t, s, offsets, g, d->max_points, d->max_voxels, so, ghist, gstart);
+        if (rc != P3_OK) return rc;
+        rc = p3_launch<pillar_sort_fill_kernel>(nullptr, dim3(SORT_SPLIT, d->B), dim3(SORT_THREADS), lds_h, s, values, offsets, g, ghist, gstart, w.sorted);
+    } else {
+        const size_t lds = (size_t)(SORT_WAVES + 5) * g.nc * 4 + 32 * 4;
+        rc = p3_launch<pillar_sort_kernel>(nullptr, dim3(d->B), dim3(SORT_THREADS), lds, s, values, offsets, g, d->max_points, d->max_voxels, so);
+    }
+    if (rc != P3_OK || !d->training) return rc;
+    const int g1 = c.vgrid < 512 ? c.vgrid : 512;
+    return pfn_partials(true, g1, 2 * C1, c, w.sums1, nullptr, s, [&](float* slab) {
+        return by_flag(d->max_points > 64, [&](auto multi) {
+            return p3_launch<pfn_l1_stats_kernel<decltype(multi)::value>>(nullptr, dim3(g1), dim3(256), 0, s, values, c.t, g, d->max_voxels, c.nslots, w1, w.sums1, slab);
+        });
+    });
+}
+
 // phases (bit mask): 1 = pillarize + layer-0 BatchNorm sums | 2 = layer 0 apply, layer-1 GEMM, reduce + BatchNorm sums |
 // 4 = finalize + scatter.  SyncBatchNorm all-reduces the workspace's `totals`/`sums1` after phase 1 and `sums2` after phase 2.
 extern "C" int p3_pillar_stem_phased(const float* values, const int64_t* offsets, const float* w1, const float* bn1_gamma,
@@ -1300,137 +1402,71 @@ extern "C" int p3_pillar_stem_phased(const float* values, const int64_t* offsets
     g.invx = 1.0f / d->vx; g.invy = 1.0f / d->vy; g.invz = 1.0f / d->vz;
     g.xmax = d->nx * d->vx; g.ymax = d->ny * d->vy; g.zmax = d->zmax; g.vx = d->vx; g.vy = d->vy;
     hipStream_t s = (hipStream_t)stream;
-    const int kdt = d->dtype == P3_BF16 ? P3_BF16 : P3_F32;       // the dtype p3_det_scratch decides by (P3_F32X3 is fp32 storage)
-    Ws w = carve(workspace, d);
-    const int nslots = d->B * d->max_voxels;
-    const size_t es = d->dtype == P3_BF16 ? 2 : 4;
-    const size_t rows = (size_t)d->total_points + (size_t)nslots;
-    hipError_t e;
-    VoxTab t{w.sorted, w.vox_xy, w.vox_start, w.vox_cnt, w.vox_row, w.nvox};
-    const int vgrid = (nslots + 3) / 4 < 2048 ? (nslots + 3) / 4 : 2048;
+    const Stem c = stem_of(workspace, d);
+    const Ws& w = c.w;
+    const int C = d->C, nslots = c.nslots, vgrid = c.vgrid;
     if (phases & 1) {
-    e = hipMemsetAsync(w.totals, 0, (char*)w.sc1 - (char*)w.totals, s);
-    if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
-    // the one-launch layer 1 without a backward reads the rows of kept pillars only: the rows of no pillar need no defined content then (0.67 GB of memset at 40 k
-    // points per tile); every other path multiplies ALL rows (the GEMM, the backward's products) and needs them finite / zero
-    const bool lean_rows = d->no_backward && pfn_layer1_fused(d, w2);
-    if (!lean_rows) {
-        e = hipMemsetAsync(w.X2, 0, rows * K2 * es, s);   // unused rows must be finite for the GEMM
-        if (e == hipSuccess) e = hipMemsetAsync(w.F8, 0, (char*)w.row_vox - (char*)w.F8, s);
+        const int rc = pfn_pillarize(values, offsets, w1, w2, out, d, g, c, s);
+        if (rc != P3_OK) return rc;
     }
-    if (e == hipSuccess) e = hipMemsetAsync(w.row_vox, 0xFF, rows * 4, s);   // -1 = unused row
-    if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
-    // zero canvas columns [col_off, col_off + C) of every token row (empty pillars stay exactly 0)
-    {
-        const size_t rowb = (size_t)d->C * es, ldb = (size_t)d->out_ld * es, offb = (size_t)d->out_col_off * es;
-        const int64_t nrows = (int64_t)d->B * d->nx * d->ny;
-        if (rowb % 16 == 0 && ldb % 16 == 0 && offb % 16 == 0 && ((uintptr_t)out % 16) == 0) {   // 16-byte stores (the 2-D memset runs at < 1 TB/s)
-            const int per_row = (int)(rowb / 16);
-            const int64_t tot = nrows * per_row;
-            hipLaunchKernelGGL(zero_cols16_kernel, dim3((unsigned)((tot + 255) / 256 < 16384 ? (tot + 255) / 256 : 16384)), dim3(256), 0, s,
-                               (char*)out + offb, (int64_t)ldb, per_row, tot);
-            P3_LAUNCH_CHECK();
-        } else {
-            e = hipMemset2DAsync((char*)out + offb, ldb, 0, rowb, (size_t)nrows, s);
-            if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
+    return p3_by_dtype(d->dtype, true, "p3_pillar_stem", [&](auto ty) {
+        using T = typename decltype(ty)::type;
+        int rc = P3_OK;
+        if (phases & 2) {
+            rc = p3_launch<bn_finalize_kernel>(nullptr, dim3(1), dim3(64), 0, s, w.sums1, C1, w.totals, (float)d->max_points, 0.f, bn1_gamma, bn1_beta, bn1_rmean, bn1_rvar,
+                                               d->bn_eps, d->bn_momentum, d->training, w.sc1, w.sh1, w.m1, w.r1);
+            if (rc != P3_OK) return rc;
+            rc = by_flag(d->max_points > 64, [&](auto multi) {
+                return p3_launch<pfn_l1_apply_kernel<T, decltype(multi)::value>>(nullptr, dim3(vgrid), dim3(256), 0, s, values, c.t, g, d->max_voxels, d->max_points, nslots, w1,
+                                                                                 w.sc1, w.sh1, (T*)w.X2, w.F8, w.row_vox, w.row_w);
+            });
+            if (rc != P3_OK) return rc;
+            float* sums2 = d->training ? w.sums2 : nullptr;
+            if (pfn_layer1_fused(d, w2)) {
+                // layer 1 in one launch: product, per-pillar max / min, BatchNorm sums (pfn_l2_fused_kernel); H2 is written only when a backward pass will read it
+                const int ns = C == 128 ? 2 : 1;                          // pillars in flight per workgroup
+                const int gf = (nslots + ns - 1) / ns < 1024 ? (nslots + ns - 1) / ns : 1024;
+                const bool keep = !d->no_backward;
+                rc = pfn_partials(sums2 != nullptr, gf, 2 * C, c, sums2, nullptr, s, [&](float* slab) {
+                    const int rf = by_flag(keep, [&](auto store) {
+                        constexpr bool ST = decltype(store)::value;
+                        const char* name = ST ? "pfn_l2_fused_kernel<store>" : "pfn_l2_fused_kernel";
+                        const auto go = [&](auto nbw, auto wpp) {
+                            return p3_launch<pfn_l2_fused_kernel<T, ST, decltype(nbw)::value, decltype(wpp)::value>>(name, dim3(gf), dim3(256), 0, s, (const T*)w.X2, (const T*)w2, c.t,
+                                                                                                                    d->max_voxels, d->max_points, nslots, (T*)w.H2, w.hmax, w.hmin, sums2,
+                                                                                                                    slab);
+                        };
+                        using std::integral_constant;
+                        return C == 128 ? go(integral_constant<int, 2>{}, integral_constant<int, 2>{}) : go(integral_constant<int, 3>{}, integral_constant<int, 4>{});
+                    });
+                    if (rf != P3_OK || !keep) return rf;
+                    const int gz = (int)((c.rows + 255) / 256 < 1024 ? (c.rows + 255) / 256 : 1024);
+                    return p3_launch<pfn_zero_unused_rows_kernel<T>>(nullptr, dim3(gz), dim3(256), 0, s, (T*)w.H2, w.row_vox, (int64_t)c.rows, C);
+                });
+            } else {
+                const p3_gemm_desc gd = pfn_gemm_desc(d, (int)c.rows, C, K2);
+                rc = p3_gemm(w.X2, w2, w.H2, &gd, stream);
+                if (rc != P3_OK) return rc;
+                const int g2 = vgrid < L2R_BLOCKS ? vgrid : L2R_BLOCKS;
+                rc = pfn_partials(sums2 != nullptr, g2, 2 * C, c, sums2, nullptr, s, [&](float* slab) {
+                    if (c.lane8)
+                        return p3_launch<pfn_l2_reduce8_kernel<T>>(nullptr, dim3(g2), dim3(256), 0, s, (const T*)w.H2, c.t, d->max_voxels, d->max_points, nslots, C, w.hmax, w.hmin,
+                                                                   sums2, slab);
+                    return p3_launch<pfn_l2_reduce_kernel<T>>(nullptr, dim3(g2), dim3(256), 0, s, (const T*)w.H2, c.t, d->max_voxels, d->max_points, nslots, C, w.hmax, w.hmin, sums2,
+                                                              slab);
+                });
+            }
+            if (rc != P3_OK) return rc;
         }
-    }
-
-    SortOut so{w.sorted, w.vox_xy, w.vox_start, w.vox_cnt, w.vox_row, w.nvox, w.totals};
-    const size_t lds = (size_t)(SORT_WAVES + 5) * g.nc * 4 + 32 * 4;
-    if (d->total_points >= 16 * (int64_t)nslots) {
-        // dense clouds: a tile's points over SORT_SPLIT workgroups (count / tables / fill)
-        unsigned* ghist = w.sort_tmp;
-        unsigned* gstart = w.sort_tmp + (size_t)d->B * SORT_SPLIT * g.nc;
-        const size_t lds_h = (size_t)SORT_WAVES * g.nc * 4, lds_t = (size_t)5 * g.nc * 4 + 32 * 4;
-        int rc = p3_launch<pillar_sort_count_kernel>(nullptr, dim3(SORT_SPLIT, d->B), dim3(SORT_THREADS), lds_h, s, values, offsets, g, ghist);
-        if (rc != P3_OK) return rc;
-        hipLaunchKernelGGL(pillar_sort_tables_kernel, dim3(d->B), dim3(SORT_THREADS), lds_t, s, offsets, g, d->max_points, d->max_voxels, so, ghist, gstart);
-        P3_LAUNCH_CHECK();
-        rc = p3_launch<pillar_sort_fill_kernel>(nullptr, dim3(SORT_SPLIT, d->B), dim3(SORT_THREADS), lds_h, s, values, offsets, g, ghist, gstart, w.sorted);
-        if (rc != P3_OK) return rc;
-    } else {
-        const int rc = p3_launch<pillar_sort_kernel>(nullptr, dim3(d->B), dim3(SORT_THREADS), lds, s, values, offsets, g, d->max_points, d->max_voxels, so);
-        if (rc != P3_OK) return rc;
-    }
-    if (d->training) {
-        // deterministic mode (p3_set_deterministic covers this dtype): the workgroups' partial sums go to the scratch and are added in workgroup order in float64
-        const int g1 = vgrid < 512 ? vgrid : 512;
-        float* slab1 = p3_det_scratch((int64_t)g1 * 2 * C1, kdt);
-        if (d->max_points > 64) hipLaunchKernelGGL(pfn_l1_stats_kernel<true>, dim3(g1), dim3(256), 0, s, values, t, g, d->max_voxels, nslots, w1, w.sums1, slab1);
-        else hipLaunchKernelGGL(pfn_l1_stats_kernel<false>, dim3(g1), dim3(256), 0, s, values, t, g, d->max_voxels, nslots, w1, w.sums1, slab1);
-        P3_LAUNCH_CHECK();
-        if (slab1) { int rc1 = p3_det_reduce(slab1, g1, 2 * C1, w.sums1, 2 * C1, 1, s); if (rc1 != P3_OK) return rc1; }
-    }
-    }
-    if (phases & 2) {
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(1), dim3(64), 0, s, w.sums1, C1, w.totals, (float)d->max_points, 0.f, bn1_gamma, bn1_beta,
-                       bn1_rmean, bn1_rvar, d->bn_eps, d->bn_momentum, d->training, w.sc1, w.sh1, w.m1, w.r1);
-    P3_LAUNCH_CHECK();
-#define P3_L1_APPLY(T, MULTI) hipLaunchKernelGGL((pfn_l1_apply_kernel<T, MULTI>), dim3(vgrid), dim3(256), 0, s, values, t, g, d->max_voxels, d->max_points, nslots, w1, w.sc1, w.sh1, (T*)w.X2, w.F8, w.row_vox, w.row_w)
-    if (d->dtype == P3_BF16) { if (d->max_points > 64) P3_L1_APPLY(bf16_t, true); else P3_L1_APPLY(bf16_t, false); }
-    else { if (d->max_points > 64) P3_L1_APPLY(float, true); else P3_L1_APPLY(float, false); }
-#undef P3_L1_APPLY
-    P3_LAUNCH_CHECK();
-    float* sums2 = d->training ? w.sums2 : nullptr;
-    const bool fused2 = pfn_layer1_fused(d, w2);
-    if (fused2) {
-        // layer 1 in one launch: product, per-pillar max / min, BatchNorm sums (pfn_l2_fused_kernel); H2 is written only when a backward pass will read it
-        const int ns = d->C == 128 ? 2 : 1;                          // pillars in flight per workgroup
-        const int gf = (nslots + ns - 1) / ns < 1024 ? (nslots + ns - 1) / ns : 1024;
-        float* slab2 = sums2 ? p3_det_scratch((int64_t)gf * 2 * d->C, kdt) : nullptr;
-        const bool keep = !d->no_backward;
-#define P3_L2_FUSED(T, ST) do { if (d->C == 128) hipLaunchKernelGGL((pfn_l2_fused_kernel<T, ST, 2, 2>), dim3(gf), dim3(256), 0, s, (const T*)w.X2, (const T*)w2, t, d->max_voxels, d->max_points, nslots, (T*)w.H2, w.hmax, w.hmin, sums2, slab2); \
-        else hipLaunchKernelGGL((pfn_l2_fused_kernel<T, ST, 3, 4>), dim3(gf), dim3(256), 0, s, (const T*)w.X2, (const T*)w2, t, d->max_voxels, d->max_points, nslots, (T*)w.H2, w.hmax, w.hmin, sums2, slab2); } while (0)
-        if (d->dtype == P3_BF16) { if (keep) P3_L2_FUSED(bf16_t, true); else P3_L2_FUSED(bf16_t, false); }
-        else { if (keep) P3_L2_FUSED(float, true); else P3_L2_FUSED(float, false); }
-#undef P3_L2_FUSED
-        P3_LAUNCH_CHECK();
-        if (p3_tracing()) p3_note_kernel(keep ? "pfn_l2_fused_kernel<store>" : "pfn_l2_fused_kernel");
-        if (keep) {
-            const int gz = (int)((rows + 255) / 256 < 1024 ? (rows + 255) / 256 : 1024);
-            if (d->dtype == P3_BF16) hipLaunchKernelGGL((pfn_zero_unused_rows_kernel<bf16_t>), dim3(gz), dim3(256), 0, s, (bf16_t*)w.H2, w.row_vox, (int64_t)rows, d->C);
-            else hipLaunchKernelGGL((pfn_zero_unused_rows_kernel<float>), dim3(gz), dim3(256), 0, s, (float*)w.H2, w.row_vox, (int64_t)rows, d->C);
-            P3_LAUNCH_CHECK();
+        if (phases & 4) {
+            rc = p3_launch<bn_finalize_kernel>(nullptr, dim3((C + 63) / 64), dim3(64), 0, s, w.sums2, C, w.totals, (float)d->max_points, 0.f, bn2_gamma, bn2_beta, bn2_rmean,
+                                               bn2_rvar, d->bn_eps, d->bn_momentum, d->training, w.sc2, w.sh2, w.m2, w.r2);
+            if (rc != P3_OK) return rc;
+            rc = p3_launch<pfn_scatter_kernel<T>>(nullptr, dim3(vgrid), dim3(256), 0, s, c.t, d->max_voxels, nslots, C, d->nx * d->ny, w.hmax, w.hmin, w.sc2, w.sh2,
+                                                  (T*)out + d->out_col_off, d->out_ld);
         }
-        if (slab2) { int rc2 = p3_det_reduce(slab2, gf, 2 * d->C, sums2, 2 * d->C, 1, s); if (rc2 != P3_OK) return rc2; }
-    } else {
-    p3_gemm_desc gd;
-    memset(&gd, 0, sizeof(gd));
-    gd.M = (int)rows; gd.N = d->C; gd.K = K2; gd.lda = K2; gd.ldb = K2; gd.ldc = d->C;
-    gd.dtype_in = d->dtype; gd.dtype_out = d->dtype == P3_F32X3 ? P3_F32 : d->dtype; gd.act = P3_ACT_NONE; gd.a_mode = P3_A_PLAIN;    // P3_F32X3: the PFN products as bf16 x 3, storage fp32
-    int rc = p3_gemm(w.X2, w2, w.H2, &gd, stream);
-    if (rc != P3_OK) return rc;
-    if (d->C % 8 == 0 && d->C <= 512) {
-        const int g2 = vgrid < L2R_BLOCKS ? vgrid : L2R_BLOCKS;
-        float* slab2 = sums2 ? p3_det_scratch((int64_t)g2 * 2 * d->C, kdt) : nullptr;
-        if (d->dtype == P3_BF16) hipLaunchKernelGGL((pfn_l2_reduce8_kernel<bf16_t>), dim3(g2), dim3(256), 0, s, (const bf16_t*)w.H2, t, d->max_voxels, d->max_points, nslots, d->C, w.hmax, w.hmin, sums2, slab2);
-        else hipLaunchKernelGGL((pfn_l2_reduce8_kernel<float>), dim3(g2), dim3(256), 0, s, (const float*)w.H2, t, d->max_voxels, d->max_points, nslots, d->C, w.hmax, w.hmin, sums2, slab2);
-        P3_LAUNCH_CHECK();
-        if (slab2) { int rc2 = p3_det_reduce(slab2, g2, 2 * d->C, sums2, 2 * d->C, 1, s); if (rc2 != P3_OK) return rc2; }
-    } else if (d->dtype == P3_BF16)
-        hipLaunchKernelGGL((pfn_l2_reduce_kernel<bf16_t>), dim3(vgrid < L2R_BLOCKS ? vgrid : L2R_BLOCKS), dim3(256), 0, s, (const bf16_t*)w.H2, t, d->max_voxels, d->max_points, nslots, d->C, w.hmax, w.hmin, sums2);
-    else {
-        const int g2 = vgrid < L2R_BLOCKS ? vgrid : L2R_BLOCKS;
-        float* slab2 = sums2 ? p3_det_scratch((int64_t)g2 * 2 * d->C, kdt) : nullptr;
-        hipLaunchKernelGGL((pfn_l2_reduce_kernel<float>), dim3(g2), dim3(256), 0, s, (const float*)w.H2, t, d->max_voxels, d->max_points, nslots, d->C, w.hmax, w.hmin, sums2, slab2);
-        P3_LAUNCH_CHECK();
-        if (slab2) { int rc2 = p3_det_reduce(slab2, g2, 2 * d->C, sums2, 2 * d->C, 1, s); if (rc2 != P3_OK) return rc2; }
-    }
-    }
-    P3_LAUNCH_CHECK();
-    }
-    if (phases & 4) {
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3((d->C + 63) / 64), dim3(64), 0, s, w.sums2, d->C, w.totals, (float)d->max_points, 0.f, bn2_gamma,
-                       bn2_beta, bn2_rmean, bn2_rvar, d->bn_eps, d->bn_momentum, d->training, w.sc2, w.sh2, w.m2, w.r2);
-    P3_LAUNCH_CHECK();
-    if (d->dtype == P3_BF16)
-        hipLaunchKernelGGL((pfn_scatter_kernel<bf16_t>), dim3(vgrid), dim3(256), 0, s, t, d->max_voxels, nslots, d->C, d->nx * d->ny, w.hmax, w.hmin, w.sc2, w.sh2, (bf16_t*)out + d->out_col_off, d->out_ld);
-    else
-        hipLaunchKernelGGL((pfn_scatter_kernel<float>), dim3(vgrid), dim3(256), 0, s, t, d->max_voxels, nslots, d->C, d->nx * d->ny, w.hmax, w.hmin, w.sc2, w.sh2, (float*)out + d->out_col_off, d->out_ld);
-    P3_LAUNCH_CHECK();
-    }
-    return P3_OK;
+        return rc;
+    });
 }
 
 extern "C" int p3_pillar_stem(const float* values, const int64_t* offsets, const float* w1, const float* bn1_gamma,
@@ -1441,12 +1477,11 @@ extern "C" int p3_pillar_stem(const float* values, const int64_t* offsets, const
                                  out, workspace, d, 7, stream);
 }
 
-
-
 // Backward of p3_pillar_stem w.r.t. the PFN parameters.  `workspace` is the buffer the matching forward call filled; it is consumed.
 // phases: 1 = layer-1 arg-max gradients + local dgamma2 / dbeta2 | 2 = dH2 rows, both GEMMs, layer-0 accumulation | 4 = layer-0 finalize.
 // stat2 = [dbeta2 (C) | dgamma2 (C)] and stat1 = [dbeta1 (32) | dgamma1 (32)] are the sums the BatchNorm input gradients use: NULL =
 // this rank's own (plain BatchNorm); SyncBatchNorm passes their all-reduced copies (the parameter gradients stay local, like torch).
+// The partial sums of the bf16 backward kernels are added with atomics at every deterministic level; the fp32 ones take a slab.
 extern "C" int p3_pillar_stem_bwd_phased(const void* dcanvas, int dcanvas_ld, const float* w1, const float* bn1_gamma, const void* w2t,
                                          const float* bn2_gamma, void* workspace, const p3_pillar_desc* d, float* dw1, float* dg1,
                                          float* db1, float* dw2, float* dg2, float* db2, const float* stat2, const float* stat1, int phases,
@@ -1454,87 +1489,65 @@ extern "C" int p3_pillar_stem_bwd_phased(const void* dcanvas, int dcanvas_ld, co
     P3_CHECK(dcanvas && w1 && bn1_gamma && w2t && bn2_gamma && workspace && d && dw1 && dg1 && db1 && dw2 && dg2 && db2, P3_EINVAL,
              "p3_pillar_stem_bwd: null pointer");
     P3_CHECK(d->C % 64 == 0 && d->C <= 768 && d->max_points > 0 && d->max_points <= 4096, P3_ESHAPE, "p3_pillar_stem_bwd: shape");
+    P3_CHECK(d->dtype == P3_F32 || d->dtype == P3_BF16 || d->dtype == P3_F32X3, P3_EUNSUP, "p3_pillar_stem_bwd: dtype");
     P3_CHECK(!d->no_backward, P3_EINVAL, "p3_pillar_stem_bwd: the forward ran with no_backward set - its workspace holds no layer-1 activations");
     hipStream_t s = (hipStream_t)stream;
-    const int kdt = d->dtype == P3_BF16 ? P3_BF16 : P3_F32;       // the dtype p3_det_scratch decides by (P3_F32X3 is fp32 storage)
-    Ws w = carve(workspace, d);
-    const int nslots = d->B * d->max_voxels;
-    const size_t rows = (size_t)d->total_points + (size_t)nslots;
-    const int C = d->C;
-    if (phases & 1) {
-        hipError_t e = hipMemsetAsync(w.acc1, 0, ACC1_FLOATS * 4, s);
-        if (e == hipSuccess) e = hipMemsetAsync(dg2, 0, (size_t)C * 4, s);
-        if (e == hipSuccess) e = hipMemsetAsync(db2, 0, (size_t)C * 4, s);
-        if (e == hipSuccess) e = hipMemsetAsync(dw2, 0, (size_t)C * K2 * 4, s);
-        if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
-    }
+    const Stem c = stem_of(workspace, d);
+    const Ws& w = c.w;
+    const int C = d->C, nslots = c.nslots, vgrid = c.vgrid;
     const float* s2_db = stat2 ? stat2 : db2;
     const float* s2_dg = stat2 ? stat2 + C : dg2;
-    VoxTab t{w.sorted, w.vox_xy, w.vox_start, w.vox_cnt, w.vox_row, w.nvox};
-    const int vgrid = (nslots + 3) / 4 < 2048 ? (nslots + 3) / 4 : 2048;
-    const int sgrid = vgrid < 512 ? vgrid : 512;
-    const int ncell = d->nx * d->ny;
-    const bool bf = d->dtype == P3_BF16;
-    if (phases & 1) {
-    if (bf)
-        if (C % 8 == 0 && C <= 512 && d->out_col_off % 8 == 0 && dcanvas_ld % 8 == 0 && ((uintptr_t)dcanvas % 16) == 0)
-            hipLaunchKernelGGL(pfn_bwd_l2_stats8_kernel<bf16_t>, dim3(vgrid < L2S_BLOCKS ? vgrid : L2S_BLOCKS), dim3(256), 0, s, t, d->max_voxels, nslots, C, ncell, (const bf16_t*)dcanvas + d->out_col_off, dcanvas_ld, w.sc2, w.sh2, w.m2, w.r2, w.hmax, w.hmin, db2, dg2, (float*)nullptr);
-        else
-        hipLaunchKernelGGL((pfn_bwd_l2_stats_kernel<bf16_t>), dim3(vgrid < L2S_BLOCKS ? vgrid : L2S_BLOCKS), dim3(256), 0, s, t, d->max_voxels, nslots, C, ncell, (const bf16_t*)dcanvas + d->out_col_off, dcanvas_ld, w.sc2, w.sh2, w.m2, w.r2, w.hmax, w.hmin, db2, dg2);
-    else {
-        const int g3 = vgrid < L2S_BLOCKS ? vgrid : L2S_BLOCKS;
-        float* slab3 = p3_det_scratch((int64_t)g3 * 2 * C, kdt);
-        if (C % 8 == 0 && C <= 512 && d->out_col_off % 4 == 0 && dcanvas_ld % 4 == 0 && ((uintptr_t)dcanvas % 16) == 0)
-            hipLaunchKernelGGL(pfn_bwd_l2_stats8_kernel<float>, dim3(g3), dim3(256), 0, s, t, d->max_voxels, nslots, C, ncell, (const float*)dcanvas + d->out_col_off, dcanvas_ld, w.sc2, w.sh2, w.m2, w.r2, w.hmax, w.hmin, db2, dg2, slab3);
-        else
-        hipLaunchKernelGGL((pfn_bwd_l2_stats_kernel<float>), dim3(g3), dim3(256), 0, s, t, d->max_voxels, nslots, C, ncell, (const float*)dcanvas + d->out_col_off, dcanvas_ld, w.sc2, w.sh2, w.m2, w.r2, w.hmax, w.hmin, db2, dg2, slab3);
-        P3_LAUNCH_CHECK();
-        if (slab3) {
-            int rc3 = p3_det_reduce(slab3, g3, 2 * C, db2, C, 1, s);
-            if (rc3 == P3_OK) rc3 = p3_det_reduce(slab3 + C, g3, 2 * C, dg2, C, 1, s);
-            if (rc3 != P3_OK) return rc3;
+    return p3_by_dtype(d->dtype, true, "p3_pillar_stem_bwd", [&](auto ty) {
+        using T = typename decltype(ty)::type;
+        constexpr bool f32 = sizeof(T) == sizeof(float);
+        int rc = P3_OK;
+        if (phases & 1) {
+            hipError_t e = hipMemsetAsync(w.acc1, 0, ACC1_FLOATS * 4, s);
+            if (e == hipSuccess) e = hipMemsetAsync(dg2, 0, (size_t)C * 4, s);
+            if (e == hipSuccess) e = hipMemsetAsync(db2, 0, (size_t)C * 4, s);
+            if (e == hipSuccess) e = hipMemsetAsync(dw2, 0, (size_t)C * K2 * 4, s);
+            if (e != hipSuccess) return hip_status(e);
+            const int g3 = vgrid < L2S_BLOCKS ? vgrid : L2S_BLOCKS, ncell = d->nx * d->ny;
+            const T* dcv = (const T*)dcanvas + d->out_col_off;
+            constexpr int per16 = 16 / (int)sizeof(T);       // the lane-owns-8 form reads the canvas gradient in 16-byte pieces
+            const bool aligned = d->out_col_off % per16 == 0 && dcanvas_ld % per16 == 0 && ((uintptr_t)dcanvas % 16) == 0;
+            rc = pfn_partials(f32, g3, 2 * C, c, db2, dg2, s, [&](float* slab) {
+                if (c.lane8 && aligned)
+                    return p3_launch<pfn_bwd_l2_stats8_kernel<T>>(nullptr, dim3(g3), dim3(256), 0, s, c.t, d->max_voxels, nslots, C, ncell, dcv, dcanvas_ld, w.sc2, w.sh2, w.m2, w.r2,
+                                                                  w.hmax, w.hmin, db2, dg2, slab);
+                return p3_launch<pfn_bwd_l2_stats_kernel<T>>(nullptr, dim3(g3), dim3(256), 0, s, c.t, d->max_voxels, nslots, C, ncell, dcv, dcanvas_ld, w.sc2, w.sh2, w.m2, w.r2,
+                                                             w.hmax, w.hmin, db2, dg2, slab);
+            });
+            if (rc != P3_OK) return rc;
         }
-    }
-    P3_LAUNCH_CHECK();
-    }
-    if (phases & 2) {
-    if (C % 8 == 0 && C <= 512) {
-        if (bf) hipLaunchKernelGGL((pfn_bwd_l2_rows8_kernel<bf16_t>), dim3(vgrid), dim3(256), 0, s, t, d->max_voxels, d->max_points, nslots, C, (bf16_t*)w.H2, w.hmax, w.hmin, bn2_gamma, w.m2, w.r2, s2_db, s2_dg, w.totals, d->training);
-        else hipLaunchKernelGGL((pfn_bwd_l2_rows8_kernel<float>), dim3(vgrid), dim3(256), 0, s, t, d->max_voxels, d->max_points, nslots, C, (float*)w.H2, w.hmax, w.hmin, bn2_gamma, w.m2, w.r2, s2_db, s2_dg, w.totals, d->training);
-    } else if (bf)
-        hipLaunchKernelGGL((pfn_bwd_l2_rows_kernel<bf16_t>), dim3(vgrid), dim3(256), 0, s, t, d->max_voxels, d->max_points, nslots, C, (bf16_t*)w.H2, w.hmax, w.hmin, bn2_gamma, w.m2, w.r2, s2_db, s2_dg, w.totals, d->training);
-    else
-        hipLaunchKernelGGL((pfn_bwd_l2_rows_kernel<float>), dim3(vgrid), dim3(256), 0, s, t, d->max_voxels, d->max_points, nslots, C, (float*)w.H2, w.hmax, w.hmin, bn2_gamma, w.m2, w.r2, s2_db, s2_dg, w.totals, d->training);
-    P3_LAUNCH_CHECK();
-    // dW2[C, 64] = dH2^T . X2
-    // deterministic mode: the split-M partial tiles go through the scratch and are added in split order (the host wrappers of p3_gemm_tn hand their own slabs in)
-    const int tn_slabs = 64;
-    float* tslab = p3_det_scratch((int64_t)tn_slabs * C * K2, kdt);
-    int rc = p3_gemm_tn_ex(w.H2, w.X2, dw2, (int)rows, C, K2, C, K2, K2, d->dtype, 0, nullptr, nullptr, nullptr, 0, nullptr, tslab, tslab ? tn_slabs : 0, stream);
-    if (rc != P3_OK) return rc;
-    // dX2[rows, 64] = dH2 . W2  (written over X2, which the weight-gradient GEMM above has finished with)
-    p3_gemm_desc gd;
-    memset(&gd, 0, sizeof(gd));
-    gd.M = (int)rows; gd.N = K2; gd.K = C; gd.lda = C; gd.ldb = C; gd.ldc = K2;
-    gd.dtype_in = d->dtype; gd.dtype_out = d->dtype == P3_F32X3 ? P3_F32 : d->dtype; gd.act = P3_ACT_NONE; gd.a_mode = P3_A_PLAIN;    // P3_F32X3: the PFN products as bf16 x 3, storage fp32
-    rc = p3_gemm(w.H2, w2t, w.X2, &gd, stream);
-    if (rc != P3_OK) return rc;
-    if (bf)
-        hipLaunchKernelGGL((pfn_bwd_l1_kernel<bf16_t>), dim3(sgrid), dim3(256), 0, s, t, d->max_voxels, d->max_points, nslots, w.F8, (const bf16_t*)w.X2, w1, w.sc1, w.sh1, w.m1, w.r1, w.acc1);
-    else {
-        float* slab4 = p3_det_scratch((int64_t)sgrid * ACC1_FLOATS, kdt);
-        hipLaunchKernelGGL((pfn_bwd_l1_kernel<float>), dim3(sgrid), dim3(256), 0, s, t, d->max_voxels, d->max_points, nslots, w.F8, (const float*)w.X2, w1, w.sc1, w.sh1, w.m1, w.r1, w.acc1, slab4);
-        P3_LAUNCH_CHECK();
-        if (slab4) { int rc4 = p3_det_reduce(slab4, sgrid, ACC1_FLOATS, w.acc1, ACC1_FLOATS, 1, s); if (rc4 != P3_OK) return rc4; }
-    }
-    P3_LAUNCH_CHECK();
-    }
-    if (phases & 4) {
-    hipLaunchKernelGGL(pfn_bwd_l1_finalize_kernel, dim3(1), dim3(256), 0, s, w.acc1, stat1 ? stat1 : w.acc1 + ACC_DB, bn1_gamma, w.r1, w.totals,
-                       d->max_points, d->training, dw1, dg1, db1);
-    P3_LAUNCH_CHECK();
-    }
-    return P3_OK;
+        if (phases & 2) {
+            rc = c.lane8 ? p3_launch<pfn_bwd_l2_rows8_kernel<T>>(nullptr, dim3(vgrid), dim3(256), 0, s, c.t, d->max_voxels, d->max_points, nslots, C, (T*)w.H2, w.hmax, w.hmin,
+                                                                 bn2_gamma, w.m2, w.r2, s2_db, s2_dg, w.totals, d->training)
+                         : p3_launch<pfn_bwd_l2_rows_kernel<T>>(nullptr, dim3(vgrid), dim3(256), 0, s, c.t, d->max_voxels, d->max_points, nslots, C, (T*)w.H2, w.hmax, w.hmin,
+                                                                bn2_gamma, w.m2, w.r2, s2_db, s2_dg, w.totals, d->training);
+            if (rc != P3_OK) return rc;
+            // dW2[C, 64] = dH2^T . X2
+            // deterministic mode: the split-M partial tiles go through the scratch and are added in split order (the host wrappers of p3_gemm_tn hand their own slabs in)
+            const int tn_slabs = 64;
+            float* tslab = p3_det_scratch((int64_t)tn_slabs * C * K2, c.kdt);
+            rc = p3_gemm_tn_ex(w.H2, w.X2, dw2, (int)c.rows, C, K2, C, K2, K2, d->dtype, 0, nullptr, nullptr, nullptr, 0, nullptr, tslab, tslab ? tn_slabs : 0, stream);
+            if (rc != P3_OK) return rc;
+            // dX2[rows, 64] = dH2 . W2  (written over X2, which the weight-gradient GEMM above has finished with)
+            const p3_gemm_desc gd = pfn_gemm_desc(d, (int)c.rows, K2, C);
+            rc = p3_gemm(w.H2, w2t, w.X2, &gd, stream);
+            if (rc != P3_OK) return rc;
+            const int sgrid = vgrid < 512 ? vgrid : 512;
+            rc = pfn_partials(f32, sgrid, ACC1_FLOATS, c, w.acc1, nullptr, s, [&](float* slab) {
+                return p3_launch<pfn_bwd_l1_kernel<T>>(nullptr, dim3(sgrid), dim3(256), 0, s, c.t, d->max_voxels, d->max_points, nslots, w.F8, (const T*)w.X2, w1, w.sc1, w.sh1, w.m1,
+                                                       w.r1, w.acc1, slab);
+            });
+            if (rc != P3_OK) return rc;
+        }
+        if (phases & 4)
+            rc = p3_launch<pfn_bwd_l1_finalize_kernel>(nullptr, dim3(1), dim3(256), 0, s, w.acc1, stat1 ? stat1 : w.acc1 + ACC_DB, bn1_gamma, w.r1, w.totals, d->max_points,
+                                                       d->training, dw1, dg1, db1);
+        return rc;
+    });
 }
 
 extern "C" int p3_pillar_stem_bwd(const void* dcanvas, int dcanvas_ld, const float* w1, const float* bn1_gamma, const void* w2t,
@@ -1544,15 +1557,15 @@ extern "C" int p3_pillar_stem_bwd(const void* dcanvas, int dcanvas_ld, const flo
                                      nullptr, 7, stream);
 }
 
-// byte offsets of the workspace sections (for the training path, which re-reads the pillar tables in backward)
-extern "C" int p3_pillar_stem_layout(const p3_pillar_desc* d, int64_t* off /*[17]*/) {
+// byte offsets of the workspace sections in the order include/p3hip.h names them (for the training path, which re-reads the pillar tables in backward);
+// the last entry is where [dbeta1 (32) | dgamma1 (32)] sit inside acc1
+extern "C" int p3_pillar_stem_layout(const p3_pillar_desc* d, int64_t* off /*[18]*/) {
     P3_CHECK(d && off, P3_EINVAL, "p3_pillar_stem_layout: null pointer");
     char* base = (char*)256;   // any non-null base: only differences are used
-    Ws w = carve(base, d);
-    off[0] = (char*)w.sorted - base; off[1] = (char*)w.vox_xy - base; off[2] = (char*)w.vox_start - base;
-    off[3] = (char*)w.vox_cnt - base; off[4] = (char*)w.vox_row - base; off[5] = (char*)w.nvox - base;
-    off[6] = (char*)w.X2 - base; off[7] = (char*)w.H2 - base; off[8] = (char*)w.hmax - base; off[9] = (char*)w.hmin - base;
-    off[10] = (char*)w.F8 - base; off[11] = (char*)w.row_vox - base; off[12] = (char*)w.row_w - base;
-    off[13] = (char*)w.totals - base; off[14] = (char*)w.sums1 - base; off[15] = (char*)w.sums2 - base; off[16] = (char*)w.acc1 - base;
+    const Ws w = carve(base, d);
+    const void* const sect[17] = {w.sorted, w.vox_xy, w.vox_start, w.vox_cnt, w.vox_row, w.nvox, w.X2,     w.H2,    w.hmax,
+                                  w.hmin,   w.F8,     w.row_vox,   w.row_w,   w.totals,  w.sums1, w.sums2, w.acc1};
+    for (int i = 0; i < 17; ++i) off[i] = (const char*)sect[i] - base;
+    off[17] = off[16] + ACC_DB * 4;
     return P3_OK;
 }

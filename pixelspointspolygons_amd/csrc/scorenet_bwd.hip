@@ -382,6 +382,13 @@ __global__ void pair_stats_bwd_kernel(const T* __restrict__ U, const T* __restri
     }
 }
 
+// The bf16 instantiations of the plain pair form: bf16 runs pair_bwd_kernel16, so no host path launches them; they stay in the library's kernel set as they were.
+#define P3_PAIR_BWD_BF16(IC)                                                                                                                                  \
+    template __global__ void pair_bwd_kernel<bf16_t, IC>(const bf16_t*, const bf16_t*, const bf16_t*, const float*, const float*, const float*, float*, float*, \
+                                                         float*, int, int, float*, float*)
+P3_PAIR_BWD_BF16(4); P3_PAIR_BWD_BF16(8); P3_PAIR_BWD_BF16(12); P3_PAIR_BWD_BF16(16);
+#undef P3_PAIR_BWD_BF16
+
 inline int grid_rows(int64_t rows, int rows_per_block) {
     constexpr int cap = 1024;                        // workgroup cap of the grid-stride row kernels; r03 sweep: 1024 -> 288 / 102 us, 2048 -> 297 / 108, 3072 -> 306 / 105, 4096 -> 315 / 127
     int64_t g = (rows + rows_per_block - 1) / rows_per_block;
@@ -403,19 +410,18 @@ extern "C" int p3_row_affine_bwd2(const void* dA, const float* dS, const void* H
     P3_CHECK((dS != nullptr) != (dA != nullptr), P3_EINVAL, "p3_row_affine_bwd: exactly one of dS (tail) / dA (matrix)");
     P3_CHECK(dS ? (C == 64 && w4) : (C == 128), P3_EUNSUP, "p3_row_affine_bwd: tail needs C = 64, matrix mode C = 128");
     hipStream_t s = (hipStream_t)stream;
-    dim3 g(grid_rows(R, 64)), b(256);
+    const dim3 g(grid_rows(R, 64)), b(256);
     const int nvals = dS ? 3 * 64 + 1 : 2 * 128;
-    float* slab = acc ? p3_det_scratch((int64_t)g.x * nvals, dtype) : nullptr;
-    if (dS) {
-        if (dtype == P3_BF16) hipLaunchKernelGGL((row_affine_bwd_kernel<bf16_t, 64, true>), g, b, 0, s, nullptr, dS, (const bf16_t*)H, scale, shift, mean, w4, (bf16_t*)dHd, acc, R, N, transpose, fix_a, fix_b, slab);
-        else hipLaunchKernelGGL((row_affine_bwd_kernel<float, 64, true>), g, b, 0, s, nullptr, dS, (const float*)H, scale, shift, mean, w4, (float*)dHd, acc, R, N, transpose, fix_a, fix_b, slab);
-    } else {
-        if (dtype == P3_BF16) hipLaunchKernelGGL((row_affine_bwd_kernel<bf16_t, 128, false>), g, b, 0, s, (const bf16_t*)dA, nullptr, (const bf16_t*)H, scale, shift, mean, nullptr, (bf16_t*)dHd, acc, R, N, 0, fix_a, fix_b, slab);
-        else hipLaunchKernelGGL((row_affine_bwd_kernel<float, 128, false>), g, b, 0, s, (const float*)dA, nullptr, (const float*)H, scale, shift, mean, nullptr, (float*)dHd, acc, R, N, 0, fix_a, fix_b, slab);
-    }
-    P3_LAUNCH_CHECK();
-    if (slab) return p3_det_reduce(slab, (int)g.x, nvals, acc, nvals, 1, s);
-    return P3_OK;
+    return p3_by_dtype(dtype, false, "p3_row_affine_bwd", [&](auto t) {
+        using T = typename decltype(t)::type;
+        float* slab = acc ? p3_det_scratch((int64_t)g.x * nvals, dtype) : nullptr;
+        const int rc = dS ? p3_launch<row_affine_bwd_kernel<T, 64, true>>(nullptr, g, b, 0, s, nullptr, dS, (const T*)H, scale, shift, mean, w4, (T*)dHd, acc, R, N,
+                                                                          transpose, fix_a, fix_b, slab)
+                          : p3_launch<row_affine_bwd_kernel<T, 128, false>>(nullptr, g, b, 0, s, (const T*)dA, nullptr, (const T*)H, scale, shift, mean, nullptr, (T*)dHd,
+                                                                            acc, R, N, 0, fix_a, fix_b, slab);
+        if (rc != P3_OK || !slab) return rc;
+        return p3_det_reduce(slab, (int)g.x, nvals, acc, nvals, 1, s);
+    });
 }
 
 // G = A^T [y > 0], G2 = A^T ([y > 0] H) from p3_gemm_tn_ex(P3_A_AFFINE_MASK2) -> the weight gradient of the layer behind the BatchNorm / ReLU
@@ -474,10 +480,10 @@ extern "C" int p3_affine_fix_ld(void* dH, const void* H, int ldh, const float* a
     const int64_t n4 = R * C / 4;
     int64_t g = (n4 + 255) / 256; if (g > 8192) g = 8192;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == P3_BF16) hipLaunchKernelGGL((affine_fix_kernel<bf16_t>), dim3((int)g), dim3(256), 0, s, (bf16_t*)dH, (const bf16_t*)H, a, b, n4, C, ldh);
-    else hipLaunchKernelGGL((affine_fix_kernel<float>), dim3((int)g), dim3(256), 0, s, (float*)dH, (const float*)H, a, b, n4, C, ldh);
-    P3_LAUNCH_CHECK();
-    return P3_OK;
+    return p3_by_dtype(dtype, false, "p3_affine_fix", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return p3_launch<affine_fix_kernel<T>>(nullptr, dim3((int)g), dim3(256), 0, s, (T*)dH, (const T*)H, a, b, n4, C, ldh);
+    });
 }
 
 void p3_pair_dv_reduce_launch(const float* slab, float* dV, int nblk, int B, int N, int C, hipStream_t s) {
@@ -509,41 +515,28 @@ static int pair_bwd_impl(const void* dA, const void* U, const void* V, const flo
                          int B, int N, int C, int dtype, float* slab, void* stream) {
     P3_CHECK(dA && U && V && scale && shift && mean && dU && dV && acc && B > 0, P3_EINVAL, "p3_pair_bwd: bad arguments");
     P3_CHECK(C == 256, P3_EUNSUP, "p3_pair_bwd: ScoreNet conv1 width must be 256 (model_pix2poly.py:74)");
+    P3_CHECK(dtype == P3_BF16 || dtype == P3_F32, P3_EUNSUP, "p3_pair_bwd: dtype");      // the two types run different kernels: no common template to dispatch
     hipStream_t s = (hipStream_t)stream;
-    const int ic = 16;     // rows i per block: dV gets N/IC atomic adds per element (same-box sweep r01: 4 -> 60.2 ms, 8 -> 58.0, 12 -> 57.7, 16 -> 57.6)
-#define PB(T, IC) do { nblk = (N + IC - 1) / IC; acc_slab = p3_det_scratch((int64_t)B * nblk * 2 * C, dtype); if (!acc_slab) dslab = nullptr; \
-                       hipLaunchKernelGGL((pair_bwd_kernel<T, IC>), dim3(nblk, B), dim3(256), 0, s, (const T*)dA, (const T*)U, (const T*)V, scale, shift, mean, dU, dV, acc, N, C, dslab, acc_slab); } while (0)
-    int nblk = 0;
-    float* acc_slab = nullptr;
-    float* dslab = slab;          // the plain forms use the dV slab only together with the deterministic (dscale, dshift) partials
+    // rows i per block: dV gets N / IC atomic adds per element.  fp32: 8.  bf16: 8 rows (4 per half-wave) with the next step's rows prefetched when the caller gives a
+    // dV slab - 238 VGPRs, no spills; rocprofv3 A/B (r03): 592 -> 348 us per launch, the dV slab sum 44 -> 68 us - else the 12-row form (6 per half-wave: the register
+    // budget of two waves per SIMD; it needs 256 + 35 spilled and cannot hold a second register set).
+    const int ic = dtype == P3_BF16 && !slab ? 12 : 8, nblk = (N + ic - 1) / ic;
+    float* acc_slab = p3_det_scratch((int64_t)B * nblk * 2 * C, dtype);
+    float* dslab = slab;
+    const dim3 g(nblk, B), b(256);
+    int rc;
     if (dtype == P3_BF16) {
-        // IC = 12 rows i per block (6 per half-wave): the register budget of two waves per SIMD without spills (IC = 16 spills 270 B / lane)
-        // 8 rows i per block (4 per half-wave) with the next step's rows prefetched: 238 VGPRs, no spills (the 12-row form needs 256 + 35
-        // spilled and cannot hold a second register set).  rocprofv3 A/B (r03): 592 -> 348 us per launch, the dV slab sum 44 -> 68 us.
-        // Without a dV slab (caller's choice) the 12-row form runs.
-        const int icb = slab ? 8 : 12;
-        nblk = (N + icb - 1) / icb;
-        acc_slab = p3_det_scratch((int64_t)B * nblk * 2 * C, dtype);
-        if (icb == 8) hipLaunchKernelGGL((pair_bwd_kernel16<8, true>), dim3(nblk, B), dim3(256), 0, s, (const bf16_t*)dA, (const bf16_t*)U, (const bf16_t*)V, scale, shift,
-                                         mean, dU, dV, acc, N, C, slab, acc_slab);
-        else hipLaunchKernelGGL((pair_bwd_kernel16<12, false>), dim3(nblk, B), dim3(256), 0, s, (const bf16_t*)dA, (const bf16_t*)U, (const bf16_t*)V, scale, shift,
-                           mean, dU, dV, acc, N, C, slab, acc_slab);
-        P3_LAUNCH_CHECK();
-        if (slab) {
-            const int64_t per = (int64_t)N * C / 4, total = (int64_t)B * per;
-            hipLaunchKernelGGL(pair_dv_reduce_kernel, dim3((unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096)), dim3(256), 0, s, slab, dV, nblk, per, total);
-            P3_LAUNCH_CHECK();
-        }
-        if (acc_slab) return p3_det_reduce(acc_slab, B * nblk, 2 * (int64_t)C, acc, 2 * C, 1, s);
-        return P3_OK;
+        const bf16_t *a16 = (const bf16_t*)dA, *u16 = (const bf16_t*)U, *v16 = (const bf16_t*)V;
+        rc = slab ? p3_launch<pair_bwd_kernel16<8, true>>(nullptr, g, b, 0, s, a16, u16, v16, scale, shift, mean, dU, dV, acc, N, C, slab, acc_slab)
+                  : p3_launch<pair_bwd_kernel16<12, false>>(nullptr, g, b, 0, s, a16, u16, v16, scale, shift, mean, dU, dV, acc, N, C, slab, acc_slab);
+    } else {
+        if (!acc_slab) dslab = nullptr;          // the plain form uses the dV slab only together with the deterministic (dscale, dshift) partials
+        rc = p3_launch<pair_bwd_kernel<float, 8>>(nullptr, g, b, 0, s, (const float*)dA, (const float*)U, (const float*)V, scale, shift, mean, dU, dV, acc, N, C, dslab,
+                                                  acc_slab);
     }
-    if (dtype == P3_BF16) { dslab = nullptr; if (ic == 16) PB(bf16_t, 16); else if (ic == 12) PB(bf16_t, 12); else if (ic == 4) PB(bf16_t, 4); else PB(bf16_t, 8); }
-    else PB(float, 8);
-#undef PB
-    P3_LAUNCH_CHECK();
+    if (rc != P3_OK) return rc;
     if (dslab) {
-        const int64_t per = (int64_t)N * C / 4, total = (int64_t)B * per;
-        hipLaunchKernelGGL(pair_dv_reduce_kernel, dim3((unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096)), dim3(256), 0, s, dslab, dV, nblk, per, total);
+        p3_pair_dv_reduce_launch(dslab, dV, nblk, B, N, C, s);
         P3_LAUNCH_CHECK();
     }
     if (acc_slab) return p3_det_reduce(acc_slab, B * nblk, 2 * (int64_t)C, acc, 2 * C, 1, s);
@@ -554,8 +547,8 @@ extern "C" int p3_pair_stats_bwd(const void* U, const void* V, const float* a, c
                                  void* stream) {
     P3_CHECK(U && V && a && b && dU && dV && B > 0, P3_EINVAL, "p3_pair_stats_bwd: bad arguments");
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == P3_BF16) hipLaunchKernelGGL((pair_stats_bwd_kernel<bf16_t>), dim3(B, 8), dim3(256), 0, s, (const bf16_t*)U, (const bf16_t*)V, a, b, dU, dV, N, C);
-    else hipLaunchKernelGGL((pair_stats_bwd_kernel<float>), dim3(B, 8), dim3(256), 0, s, (const float*)U, (const float*)V, a, b, dU, dV, N, C);
-    P3_LAUNCH_CHECK();
-    return P3_OK;
+    return p3_by_dtype(dtype, false, "p3_pair_stats_bwd", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return p3_launch<pair_stats_bwd_kernel<T>>(nullptr, dim3(B, 8), dim3(256), 0, s, (const T*)U, (const T*)V, a, b, dU, dV, N, C);
+    });
 }

@@ -619,11 +619,11 @@ extern "C" int p3_ce_loss_bwd(const float* logits, int ld, const int64_t* target
     P3_CHECK(logits && targets && row_lse && acc && gscale && dlogits && Vpad >= V && ld_out >= Vpad, P3_EINVAL, "p3_ce_loss_bwd: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     const int64_t total = (int64_t)R * Vpad;
-    if (dtype_out == P3_BF16) hipLaunchKernelGGL((ce_bwd_kernel<bf16_t>), dim3(grid_for(total)), dim3(256), 0, s, logits, ld, targets, R, V, ignore_index, row_lse, acc, gscale, (bf16_t*)dlogits, ld_out, Vpad);
-    else if (dtype_out == P3_F32) hipLaunchKernelGGL((ce_bwd_kernel<float>), dim3(grid_for(total)), dim3(256), 0, s, logits, ld, targets, R, V, ignore_index, row_lse, acc, gscale, (float*)dlogits, ld_out, Vpad);
-    else { p3_set_error("p3_ce_loss_bwd: dtype"); return P3_EUNSUP; }
-    P3_LAUNCH_CHECK();
-    return P3_OK;
+    return p3_by_dtype(dtype_out, false, "p3_ce_loss_bwd", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return p3_launch<ce_bwd_kernel<T>>(nullptr, dim3(grid_for(total)), dim3(256), 0, s, logits, ld, targets, R, V, ignore_index, row_lse, acc, gscale, (T*)dlogits,
+                                           ld_out, Vpad);
+    });
 }
 
 extern "C" int p3_bce_loss_fwd(const float* p, const float* y, int64_t n, float* acc, void* stream) {

@@ -615,18 +615,27 @@ def pillar_stem(values, offsets, w1, bn1, w2, bn2, out, *, B, grid, voxel, zmax,
     return (out, ws, d) if keep_workspace else out
 
 
+# the sections of a stem workspace in the order p3_pillar_stem_layout returns their byte offsets (include/p3hip.h)
+_PILLAR_SECTIONS = ("sorted", "vox_xy", "vox_start", "vox_cnt", "vox_row", "nvox", "X2", "H2", "hmax", "hmin", "F8", "row_vox", "row_w",
+                    "totals", "sums1", "sums2", "acc1", "acc1_stat")
+
+
 def _pillar_layout(d):
-    """byte offsets of the 17 sections of a stem workspace (p3_pillar_stem_layout)"""
-    off = (c_int64 * 17)()
+    """section name -> byte offset in a stem workspace (p3_pillar_stem_layout)"""
+    off = (c_int64 * len(_PILLAR_SECTIONS))()
     check(lib().p3_pillar_stem_layout(byref(d), off), "p3_pillar_stem_layout")
-    return off
+    return dict(zip(_PILLAR_SECTIONS, off))
+
+
+def _pillar_views(ws, d, sizes, dtypes=None):
+    """{name: view of `ws`} for sizes = {name: elements of 4 bytes}; int32 unless dtypes names another type"""
+    off = _pillar_layout(d)
+    return {k: ws[off[k]:off[k] + 4 * n].view((dtypes or {}).get(k, torch.int32)) for k, n in sizes.items()}
 
 
 def _pillar_sections(ws, d):
-    off = _pillar_layout(d)
-    sect = lambda o, n, dtype: ws[o:o + 4 * n].view(dtype)
-    return dict(totals=sect(off[13], 1, torch.int32), sums1=sect(off[14], 64, torch.float32), sums2=sect(off[15], 2 * d.C, torch.float32),
-                acc1_stat=sect(off[16] + 4 * 520, 64, torch.float32))
+    f32 = torch.float32
+    return _pillar_views(ws, d, dict(totals=1, sums1=64, sums2=2 * d.C, acc1_stat=64), dict(sums1=f32, sums2=f32, acc1_stat=f32))
 
 
 def pillar_tables(ws, d):
@@ -634,11 +643,8 @@ def pillar_tables(ws, d):
     sorted [total_points] global point ids grouped by pillar (ascending id inside a pillar), and per pillar slot b * max_voxels + s
     (s = rank of the kept pillar in ascending hash order): vox_xy (cy * nx + cx, bit 30 = the scatter skips it because the top-z pillar
     of the same (x, y) overwrites it), vox_start (first position in `sorted`), vox_cnt (= num_points, capped), vox_row; nvox [B]."""
-    off = _pillar_layout(d)
     nv = d.B * d.max_voxels
-    sect = lambda o, n: ws[o:o + 4 * n].view(torch.int32)
-    return dict(sorted=sect(off[0], max(int(d.total_points), 1)), vox_xy=sect(off[1], nv), vox_start=sect(off[2], nv), vox_cnt=sect(off[3], nv),
-                vox_row=sect(off[4], nv), nvox=sect(off[5], d.B))
+    return _pillar_views(ws, d, dict(sorted=max(int(d.total_points), 1), vox_xy=nv, vox_start=nv, vox_cnt=nv, vox_row=nv, nvox=d.B))
 
 
 def pillar_stem_bwd(dcanvas, w1, g1, w2t, g2, ws, d, sync=None):

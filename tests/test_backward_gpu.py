@@ -1,4 +1,5 @@
 """Backward / training-step parity on the GPU: HIP backward kernels vs torch autograd of the same fp32 math on the CPU."""
+import functools
 import math
 
 import pytest
@@ -937,6 +938,133 @@ def test_pillar_stem_backward_native_vs_oracle_autograd(train, max_points, n_poi
     for k, prm in enc.named_parameters():
         err = l2_err(prm.grad.cpu(), p[pre + k].grad, floor=1e-3 * gnorm)
         assert err < 3e-3, (k, err)       # (cap 16 at 15 points per pillar: 2.6e-3 on the layer-0 BatchNorm scale - the max over slots sits next to ties)
+
+
+# ---- the stem's column-group kernels (C > 512) and the misaligned-canvas backward: host-selected paths no C = 384 test reaches ----------------------------
+_SMALL = dict(B=2, grid=(4, 4), voxel=(8.0, 8.0, 100.0), zmax=100.0, max_points=8, max_voxels=16)
+_SMALL_PRE = "stem."
+
+
+@functools.lru_cache(maxsize=None)
+def _small_cloud():
+    """2 samples x 60 points on a 4 x 4 grid of 8 m cells: per sample 5 cells stay empty, two hold 14 and 11 points (more than max_points = 8)"""
+    g = torch.Generator().manual_seed(5)
+    vals, offs = [], [0]
+    for _ in range(_SMALL["B"]):
+        cells = torch.randperm(16, generator=g)[:11]
+        for cell, n in zip(cells.tolist(), [14, 11] + [4] * 8 + [3]):
+            xy = torch.tensor([cell % 4, cell // 4]) * 8.0 + torch.rand(n, 2, generator=g) * 7.99
+            vals.append(torch.cat([xy, torch.rand(n, 1, generator=g) * 99.99], 1))
+        offs.append(offs[-1] + 60)
+    return torch.cat(vals).float().contiguous(), torch.tensor(offs, dtype=torch.int64)
+
+
+@functools.lru_cache(maxsize=None)
+def _small_stem_reference(C):
+    """hand-made PFN weights (every 7th layer-1 BatchNorm weight negative: the min branch of the max) and the float64 autograd reference of O.pillar_stem"""
+    g = torch.Generator().manual_seed(100 + C)
+    rn = lambda *s, std: torch.randn(*s, generator=g) * std
+    sd = {}
+    for li, (n_out, n_in) in enumerate([(32, 8), (C, 64)]):
+        pre = f"{_SMALL_PRE}voxel_encoder.pfn_layers.{li}."
+        sd[pre + "linear.weight"] = rn(n_out, n_in, std=0.1)
+        sd[pre + "norm.weight"] = 1 + rn(n_out, std=0.1)
+        sd[pre + "norm.bias"] = rn(n_out, std=0.1)
+        sd[pre + "norm.running_mean"], sd[pre + "norm.running_var"] = torch.zeros(n_out), torch.ones(n_out)
+        sd[pre + "norm.num_batches_tracked"] = torch.zeros((), dtype=torch.int64)
+    sd[f"{_SMALL_PRE}voxel_encoder.pfn_layers.1.norm.weight"][::7] *= -1
+    vals, offs = _small_cloud()
+    p = {k: (v.double().requires_grad_(True) if v.is_floating_point() and "running" not in k else (v.double() if v.is_floating_point() else v.clone()))
+         for k, v in sd.items()}
+    kw = {k: v for k, v in _SMALL.items() if k != "B"}
+    ref = O.pillar_stem(vals, offs, p, _SMALL_PRE, training=True, **kw).flatten(2).transpose(1, 2)       # [B, 16, C]
+    gout = _rand(_SMALL["B"], 16, C, seed=8)
+    ref.backward(gout.double())
+    names = [f"pfn_layers.{li}.{k}" for li in (0, 1) for k in ("linear.weight", "norm.weight", "norm.bias")]
+    grads = {n: p[f"{_SMALL_PRE}voxel_encoder.{n}"].grad.float() for n in names}
+    return sd, ref.detach().float(), grads, gout
+
+
+def _small_stem_native(C, dtype, col_off=0, ld=None):
+    """hip.pillar_stem(keep_workspace=True) + hip.pillar_stem_bwd on the small cloud -> canvas [B, 16, ld] (7.0 where the stem must not write), gradients by name"""
+    hip = _h()
+    sd, _, _, gout = _small_stem_reference(C)
+    vals, offs = _small_cloud()
+    ld = C if ld is None else ld
+    lay = lambda li, k: sd[f"{_SMALL_PRE}voxel_encoder.pfn_layers.{li}.{k}"].to(DEV)
+    bn = lambda li: (lay(li, "norm.weight"), lay(li, "norm.bias"), lay(li, "norm.running_mean").clone(), lay(li, "norm.running_var").clone())
+    w1, w2 = lay(0, "linear.weight"), lay(1, "linear.weight").to(dtype)
+    canvas = torch.full((_SMALL["B"], 16, ld), 7.0, dtype=dtype, device=DEV)
+    _, ws, d = hip.pillar_stem(vals.to(DEV), offs.to(DEV), w1, bn(0), w2, bn(1), canvas, training=True, col_off=col_off, keep_workspace=True, **_SMALL)
+    dcanvas = torch.full((_SMALL["B"], 16, ld), 7.0, dtype=dtype, device=DEV)
+    dcanvas[..., col_off:col_off + C] = gout.to(DEV).to(dtype)
+    got = hip.pillar_stem_bwd(dcanvas, w1, bn(0)[0], w2.t().contiguous(), bn(1)[0], ws, d)
+    torch.cuda.synchronize()
+    names = ["pfn_layers.0.linear.weight", "pfn_layers.0.norm.weight", "pfn_layers.0.norm.bias", "pfn_layers.1.linear.weight", "pfn_layers.1.norm.weight",
+             "pfn_layers.1.norm.bias"]
+    return canvas.cpu(), {n: t.cpu() for n, t in zip(names, got)}
+
+
+def _assert_grads(got, want, bound):
+    gnorm = max(float(v.norm()) for v in want.values())
+    for k in want:
+        err = l2_err(got[k], want[k], floor=1e-3 * gnorm)
+        print(f"pillar stem small: {k} l2_err {err:.3e} (bound {bound})")
+        assert err < bound, (k, err)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_pillar_stem_column_group_kernels_above_512_channels(dtype):
+    """C = 576, the first width above 512 the stem accepts: forward and backward take pfn_l2_reduce_kernel, pfn_bwd_l2_stats_kernel and pfn_bwd_l2_rows_kernel.
+    fp32 against float64 autograd of the oracle with the bounds of test_pillar_stem_backward_native_vs_oracle_autograd; bf16 against the fp32 run with those of
+    test_pillar_stem_layer1_in_one_launch_vs_the_two_pass_exact_path; the same bits from two runs wherever the deterministic level covers the dtype (the bf16
+    backward kernels add with atomics at every level)."""
+    C = 576
+    _, ref, ref_g, _ = _small_stem_reference(C)
+    out32, g32 = _small_stem_native(C, torch.float32)
+    if dtype == torch.float32:
+        out, gr = out32, g32
+        e = rel_err(out, ref)
+        print(f"pillar stem C=576 fp32: forward rel_err {e:.3e}")
+        assert e < 1e-4
+        _assert_grads(gr, ref_g, 3e-3)
+    else:
+        out, gr = _small_stem_native(C, dtype)
+        e = rel_err(out.float(), out32)
+        print(f"pillar stem C=576 bf16 vs fp32: forward rel_err {e:.3e}")
+        assert e < 2e-2
+        _assert_grads({k: v.float() for k, v in gr.items()}, g32, 0.15)
+    level = _h().lib().p3_get_deterministic()
+    out2, gr2 = _small_stem_native(C, dtype)
+    if level >= (1 if dtype == torch.float32 else 2):
+        assert torch.equal(out, out2), "canvas not bit-reproducible"
+        if dtype == torch.float32:
+            for k in gr:
+                assert torch.equal(gr[k], gr2[k]), f"{k}: gradient not bit-reproducible"
+
+
+def test_pillar_stem_into_a_misaligned_column_block_of_a_wider_canvas():
+    """C = 64, fp32, canvas columns [2, 66) of 72: the canvas gradient rows are not 16-byte aligned, so the backward takes pfn_bwd_l2_stats_kernel at a width whose
+    other kernels are the lane-owns-8 ones.  Against float64 autograd (bounds as above) and against the same stem at col_off = 0: the forward runs the same kernels
+    on the same numbers - equal bits - and the gradients differ by the order of <= 16 fp32 additions per BatchNorm sum (bound: the fp32 forward bound, 1e-4);
+    nothing is written outside the column block."""
+    C, off, ld = 64, 2, 72
+    _, ref, ref_g, _ = _small_stem_reference(C)
+    out0, g0 = _small_stem_native(C, torch.float32)
+    out, gr = _small_stem_native(C, torch.float32, col_off=off, ld=ld)
+    assert bool((out[..., :off] == 7.0).all()) and bool((out[..., off + C:] == 7.0).all()), "stray write outside the column block"
+    assert torch.equal(out[..., off:off + C], out0)
+    e = rel_err(out0, ref)
+    print(f"pillar stem C=64 fp32: forward rel_err {e:.3e}")
+    assert e < 1e-4
+    _assert_grads(g0, ref_g, 3e-3)
+    _assert_grads(gr, ref_g, 3e-3)
+    _assert_grads(gr, g0, 1e-4)
+    out2, gr2 = _small_stem_native(C, torch.float32, col_off=off, ld=ld)
+    if _h().lib().p3_get_deterministic() >= 1:
+        assert torch.equal(out, out2)
+        for k in gr:
+            assert torch.equal(gr[k], gr2[k]), f"{k}: gradient not bit-reproducible"
 
 
 @pytest.mark.parametrize("precision,tol_out,tol_grad", [("fp32x3", 2e-5, 4e-3), ("bf16", 2e-2, 0.15)])
