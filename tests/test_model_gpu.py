@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from oracle import p3_oracle as O
-from tests.helpers import load_golden, rel_err
+from tests.helpers import elem_err, load_golden, rel_err
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -20,6 +20,19 @@ PARITY_MODES = ["fp32", "fp32x3"]     # both are held to the north star's tolera
 def perm_tol(tol):
     """the permutation matrix is held to the SAME 1e-3 as the logits in the fp32 parity mode (measured 2e-6); the bf16 mode keeps 5 x its tolerance"""
     return tol if tol <= TOL32 else tol * 5
+
+
+# Element-wise figure (tests.helpers.elem_err: |a-b| / max(|b|, 1 % of max|b|)) of logits and permutation against the oracle.  fp32: the north star's 1e-3 applied
+# element-wise.  fp32x3 / bf16: twice the largest value measured on MI355X over every parametrisation of the two tests that assert it, rounded up to one
+# significant digit (the measurements are tabulated in DESIGN.md, "Precision contract").
+ELEM_TOL = {"fp32": (1e-3, 1e-3), "fp32x3": (3e-3, 4e-5), "bf16": (2.0, 3e-2)}           # precision -> (logits, perm)
+
+
+def _elem_close(tag, precision, logits, ref_logits, perm, ref_perm):
+    el, ep = elem_err(logits.float().cpu(), ref_logits), elem_err(perm.float().cpu(), ref_perm)
+    tl, tp = ELEM_TOL[precision]
+    print(f"[elem] {tag} {precision}: logits elem_err {el:.3e} (bound {tl}), perm elem_err {ep:.3e} (bound {tp})")
+    assert el < tl and ep < tp, (tag, precision, el, tl, ep, tp)
 
 
 def _model(kind, precision, sd=None, **kw):
@@ -65,6 +78,7 @@ def test_pix2poly_forward_eval_vs_oracle(kind, precision, tol):
     print(f"[{kind}-{precision}] logits {rel_err(logits.float().cpu(), ref_logits):.3e} perm {rel_err(perm.float().cpu(), ref_perm):.3e}")
     assert rel_err(logits.float().cpu(), ref_logits) < tol
     assert rel_err(perm.float().cpu(), ref_perm) < perm_tol(tol)
+    _elem_close(kind, precision, logits, ref_logits, perm, ref_perm)
     if precision in ("fp32", "fp32x3"):   # bit-exact token indices
         assert torch.equal(logits.float().cpu().argmax(-1), ref_logits.argmax(-1))
 
@@ -442,6 +456,7 @@ def test_full_bench_batch_is_batch_independent_and_matches_the_oracle(precision)
             rl, rp = O.pix2poly_forward({k: v.clone() for k, v in sd.items()}, inp["y"][b:b + 1, :-1], inp["image"][b:b + 1],
                                         (inp["lidar_values"][lo:hi], torch.tensor([0, hi - lo])))
             assert rel_err(logits[b:b + 1].float().cpu(), rl) < tol and rel_err(perm[b:b + 1].float().cpu(), rp) < perm_tol(tol)
+            _elem_close(f"bench batch tile {b}", precision, logits[b:b + 1], rl, perm[b:b + 1], rp)
             if precision != "bf16":
                 assert torch.equal(logits[b:b + 1].float().cpu().argmax(-1), rl.argmax(-1))
 
