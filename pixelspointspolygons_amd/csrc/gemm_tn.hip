@@ -279,19 +279,16 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(TnArgs g) {
             for (int kk = 0; kk < BM / 16; ++kk) {
                 const int sl = kk & 1;
                 if (kk + 1 < BM / 16) issue(sl ^ 1, kk + 1);
-                s16x8 af[2], bf[2];
+                bf16x8_t af[2], bf[2];
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
-                    af[i] = __builtin_bit_cast(s16x8, u32x4{fa[sl][i][0].x, fa[sl][i][0].y, fa[sl][i][1].x, fa[sl][i][1].y});
-                    bf[i] = __builtin_bit_cast(s16x8, u32x4{fb[sl][i][0].x, fb[sl][i][0].y, fb[sl][i][1].x, fb[sl][i][1].y});
+                    af[i] = tr_frag(fa[sl][i][0], fa[sl][i][1]);
+                    bf[i] = tr_frag(fb[sl][i][0], fb[sl][i][1]);
                 }
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                            __builtin_bit_cast(__bf16 __attribute__((ext_vector_type(8))), af[i]),
-                            __builtin_bit_cast(__bf16 __attribute__((ext_vector_type(8))), bf[j]), acc[i][j], 0, 0, 0);
+                    for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bf[j], acc[i][j], 0, 0, 0);
                 if (kk + 1 < BM / 16) wait(sl ^ 1);
             }
         } else if constexpr (SPLIT) {
@@ -313,14 +310,13 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(TnArgs g) {
             asm volatile("s_waitcnt lgkmcnt(0)"
                          : "+v"(fa[0][0][0]), "+v"(fa[0][0][1]), "+v"(fa[0][1][0]), "+v"(fa[0][1][1]), "+v"(fb[0][0][0]), "+v"(fb[0][0][1]), "+v"(fb[0][1][0]), "+v"(fb[0][1][1]),
                            "+v"(fa[1][0][0]), "+v"(fa[1][0][1]), "+v"(fa[1][1][0]), "+v"(fa[1][1][1]), "+v"(fb[1][0][0]), "+v"(fb[1][0][1]), "+v"(fb[1][1][0]), "+v"(fb[1][1][1]));
-            typedef __bf16 bfx8 __attribute__((ext_vector_type(8)));
-            bfx8 af[2][2], bf[2][2];                 // [image][block]
+            bf16x8_t af[2][2], bf[2][2];             // [image][block]
 #pragma unroll
             for (int im = 0; im < 2; ++im)
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
-                    af[im][i] = __builtin_bit_cast(bfx8, u32x4{fa[im][i][0].x, fa[im][i][0].y, fa[im][i][1].x, fa[im][i][1].y});
-                    bf[im][i] = __builtin_bit_cast(bfx8, u32x4{fb[im][i][0].x, fb[im][i][0].y, fb[im][i][1].x, fb[im][i][1].y});
+                    af[im][i] = tr_frag(fa[im][i][0], fa[im][i][1]);
+                    bf[im][i] = tr_frag(fb[im][i][0], fb[im][i][1]);
                 }
 #pragma unroll
             for (int i = 0; i < 2; ++i)
@@ -545,6 +541,19 @@ float* p3_tn_park(float* C, int N, int K, int ldc, int splits) {
     return slot;
 }
 
+TnParts p3_tn_parts(float* C, int N, int K, int ldc, int splits, float* slabs, float* colsum, int cs_dtype) {
+    TnParts p = {(slabs && splits > 1) ? slabs : nullptr, nullptr, false, 0};
+    if (p.slabs) { float* slot = p3_tn_park(C, N, K, ldc, splits); if (slot) { p.slabs = slot; p.parked = true; } }
+    if (colsum) p.cs_slab = p3_colsum_parts(splits, N, colsum, cs_dtype, &p.cs_parked);
+    return p;
+}
+int p3_tn_parts_reduce(const TnParts& p, float* C, int N, int K, int ldc, int splits, float* colsum, hipStream_t s) {
+    if (p.slabs && !p.parked) p3_tn_reduce_launch(p.slabs, C, N, K, ldc, splits, s);
+    P3_LAUNCH_CHECK();
+    if (p.cs_slab && !p.cs_parked) return p3_det_reduce(p.cs_slab, splits, N, colsum, N, 1, s);
+    return P3_OK;
+}
+
 extern "C" int p3_tn_flush(void* stream) {
     hipStream_t s = (hipStream_t)stream;
     for (int base = 0; base < g_tnp_n; base += TNP_MAX) {
@@ -617,12 +626,9 @@ extern "C" int p3_gemm_tn_ex(const void* A, const void* B, float* C, int M, int 
     if (splits < 1) splits = 1;
     g.rows_per_split = p3_ceil_div(p3_ceil_div(M, splits), bm) * bm;
     splits = p3_ceil_div(M, g.rows_per_split);
-    g.slabs = (slabs && splits > 1) ? slabs : nullptr;
-    bool parked = false;
-    if (g.slabs) { float* slot = p3_tn_park(C, N, K, ldc, splits); if (slot) { g.slabs = slot; parked = true; } }
     g.splits = splits;
-    int cs_parked = 0;
-    g.cs_slab = colsum ? p3_colsum_parts(splits, N, colsum, dtype, &cs_parked) : nullptr;
+    const TnParts parts = p3_tn_parts(C, N, K, ldc, splits, slabs, colsum, dtype);
+    g.slabs = parts.slabs; g.cs_slab = parts.cs_slab;
     dim3 grid(tiles * splits), block(256);
     hipStream_t s = (hipStream_t)stream;
 #define P3_TN_LAUNCH(MODE)                                                                            \
@@ -641,13 +647,7 @@ extern "C" int p3_gemm_tn_ex(const void* A, const void* B, float* C, int M, int 
     else if (g.b_mode == P3_A_AFFINE_MASK2) P3_TN_LAUNCH(P3_A_AFFINE_MASK2);
     else P3_TN_LAUNCH(P3_A_PAIR_AFFINE_RELU);
 #undef P3_TN_LAUNCH
-    if (g.slabs && !parked) {
-        int64_t gr = ((int64_t)N * K + 255) / 256; if (gr > 4096) gr = 4096;
-        hipLaunchKernelGGL(tn_reduce_kernel, dim3((int)gr), dim3(256), 0, s, g.slabs, C, N, K, ldc, splits);
-    }
-    P3_LAUNCH_CHECK();
-    if (g.cs_slab && !cs_parked) return p3_det_reduce(g.cs_slab, splits, N, colsum, N, 1, s);
-    return P3_OK;
+    return p3_tn_parts_reduce(parts, C, N, K, ldc, splits, colsum, s);
 }
 
 extern "C" int p3_gemm_tn(const void* A, const void* B, float* C, int M, int N, int K, int lda, int ldb, int ldc, int dtype, void* stream) {

@@ -88,7 +88,7 @@ __global__ __launch_bounds__(512, 1) void mask2_dw_mma_kernel(MdArgs g) {
                 m1[e] = (on0 ? 0x3f80u : 0u) | (on1 ? 0x3f800000u : 0u);
                 m2[e] = (on0 ? (hw[e] & 0xffffu) : 0u) | (on1 ? (hw[e] & 0xffff0000u) : 0u);
             }
-            const bf16x8_t af = __builtin_bit_cast(bf16x8_t, u32x4_t{fa[0].x, fa[0].y, fa[1].x, fa[1].y});
+            const bf16x8_t af = tr_frag(fa[0], fa[1]);
             acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, __builtin_bit_cast(bf16x8_t, m1), acc[0], 0, 0, 0);
             acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, __builtin_bit_cast(bf16x8_t, m2), acc[1], 0, 0, 0);
         }

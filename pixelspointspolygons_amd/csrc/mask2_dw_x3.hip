@@ -115,8 +115,7 @@ __global__ __launch_bounds__(512, 2) void mask2_dw_x3_kernel(MxArgs g) {
             }
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fah[0]), "+v"(fah[1]), "+v"(fal[0]), "+v"(fal[1]), "+v"(f1[0]), "+v"(f1[1]), "+v"(f2h[0]), "+v"(f2h[1]),
                                                   "+v"(f2l[0]), "+v"(f2l[1]));
-            auto frag = [](const u32x2_t (&f)[2]) __attribute__((always_inline)) { return __builtin_bit_cast(bf16x8_t, u32x4_t{f[0].x, f[0].y, f[1].x, f[1].y}); };
-            const bf16x8_t ah = frag(fah), al = frag(fal), m1 = frag(f1), m2h = frag(f2h), m2l = frag(f2l);
+            const bf16x8_t ah = tr_frag(fah[0], fah[1]), al = tr_frag(fal[0], fal[1]), m1 = tr_frag(f1[0], f1[1]), m2h = tr_frag(f2h[0], f2h[1]), m2l = tr_frag(f2l[0], f2l[1]);
             acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, m1, acc[0], 0, 0, 0);
             acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, m1, acc[0], 0, 0, 0);
             acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, m2h, acc[1], 0, 0, 0);

@@ -31,6 +31,8 @@ __device__ __forceinline__ uint32_t pack_bf2(float lo, float hi) {
 typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
+// one bf16 MFMA operand from the two halves of a transposing read (lds_read_tr16_b64: rows +0..3, then rows +4..7)
+__device__ __forceinline__ bf16x8_t tr_frag(u32x2_t a, u32x2_t b) { return __builtin_bit_cast(bf16x8_t, u32x4_t{a.x, a.y, b.x, b.y}); }
 
 // eight fp32 values -> bf16 hi plane (round to nearest even) and bf16 lo plane (the rounded remainder): the operand split of every fp32x3 kernel
 __device__ __forceinline__ void split8(const float (&v)[8], u32x4_t& h, u32x4_t& l) {
@@ -274,6 +276,12 @@ int p3_mask2_dw_x3_try(const void* A, const void* B, float* C, int M, int N, int
                        float* slabs, int max_slabs, hipStream_t s);                                        // mask2_dw_x3.hip: the P3_F32X3 form
 void p3_tn_reduce_launch(const float* slabs, float* C, int N, int K, int ldc, int splits, hipStream_t s);  // gemm_tn.hip: float64 sum of the split-M partial tiles
 float* p3_tn_park(float* C, int N, int K, int ldc, int splits);                                            // gemm_tn.hip: deferred reduce slot or NULL
+// where one split-M weight-gradient launch puts its partials (gemm_tn.hip).  p3_tn_parts before the launch: slabs - the caller's `slabs` when there is more than
+// one split, or a parked slot in its place (the reduce waits for p3_tn_flush); cs_slab - the bias column sums' partials, parked or deterministic scratch; NULL =
+// atomics.  p3_tn_parts_reduce behind the launch: its status, then the reduces of what is not parked.
+struct TnParts { float* slabs; float* cs_slab; bool parked; int cs_parked; };
+TnParts p3_tn_parts(float* C, int N, int K, int ldc, int splits, float* slabs, float* colsum, int cs_dtype);
+int p3_tn_parts_reduce(const TnParts& p, float* C, int N, int K, int ldc, int splits, float* colsum, hipStream_t s);
 void p3_pair_dv_reduce_launch(const float* slab, float* dV, int nblk, int B, int N, int C, hipStream_t s); // scorenet_bwd.hip
 int p3_gemm_dma_eligible(const p3_gemm_desc* d, const void* A, const void* W, const void* C);              // gemm_dma.hip
 int p3_gemm_dma_launch(const void* A, const void* W, void* C, const p3_gemm_desc* d, int variant, hipStream_t s);

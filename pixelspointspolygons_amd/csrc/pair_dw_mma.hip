@@ -117,7 +117,7 @@ __global__ __launch_bounds__(512, 1) void pair_dw_mma_kernel(PdArgs g) {
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa[0][0]), "+v"(fa[0][1]), "+v"(fa[1][0]), "+v"(fa[1][1]));
 #pragma unroll
             for (int ib = 0; ib < 2; ++ib) {
-                const bf16x8_t af = __builtin_bit_cast(bf16x8_t, u32x4_t{fa[ib][0].x, fa[ib][0].y, fa[ib][1].x, fa[ib][1].y});
+                const bf16x8_t af = tr_frag(fa[ib][0], fa[ib][1]);
 #pragma unroll
                 for (int jb = 0; jb < 2; ++jb) acc[ib][jb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bfr[jb], acc[ib][jb], 0, 0, 0);
             }

@@ -541,6 +541,64 @@ def test_gemm_tn_x3_accumulates_into_a_column_slice():
     _close("gemm_tn_x3 colsum", cs, cs_preset.double() + _planes_value(dyp).sum(0), 1e-5)
 
 
+# the LDS-DMA weight-gradient kernels keep FOUR step buffers in LDS and three steps in flight (csrc/tn_dma_tile.h): a split with fewer steps than that fills
+# less and waits for fewer.  (kernel, N, K, M, steps per split by the host's split plan - one tile: splits = min(256 / tiles, M / (2 * step rows)) -, direct):
+# direct = lib().p3_gemm_tn_x3 on raw plane buffers (Planes pads its rows to 64).  128 x 3072 is 8 tiles of 128 x 384: the fewest at which the host picks the
+# wide kernel, whose plan counts 32-row steps (M = 32, 64 -> one split) while it runs 16-row ones.
+TN_SHORT = [("gemm_tn_dma_kernel<4>", 128, 128, 64, "1", False), ("gemm_tn_dma_kernel<4>", 128, 128, 128, "2", False),
+            ("gemm_tn_dma_kernel<4>", 128, 128, 320, "3 + 2", False),                      # two uneven splits of 192 and 128 rows
+            ("gemm_tn_x3_kernel<4>", 128, 128, 32, "1", True), ("gemm_tn_x3_kernel<4>", 128, 128, 96, "3", True), ("gemm_tn_x3_kernel<4>", 128, 128, 64, "2", False),
+            ("gemm_tn_x3_wide_kernel<4>", 128, 3072, 32, "2", True), ("gemm_tn_x3_wide_kernel<4>", 128, 3072, 64, "4", False)]
+
+
+@pytest.mark.parametrize("level", [2, None])
+@pytest.mark.parametrize("kernel,N,K,M,steps,direct", TN_SHORT)
+def test_gemm_tn_lds_dma_pipelines_shorter_than_their_buffers(det, kernel, N, K, M, steps, direct, level):
+    """splits of 1 .. 4 steps on the three LDS-DMA weight-gradient kernels, out a preset column slice of a guarded matrix, the bias column sums preset and guarded,
+    against float64 of the operands' own values: 2e-5 / column sums 1e-4 (bf16: test_gemm_tn_dma_kernel), 1e-5 both (planes: test_gemm_tn_x3_weight_gradient).
+    level 2 and the default level; at level 2 a second launch gives the same bits."""
+    h = _h()
+    if level is not None:
+        det(level)
+    bf = kernel == "gemm_tn_dma_kernel<4>"
+    a, b = _rand(M, N, seed=21), _rand(M, K, seed=22)
+    if bf:
+        a, b = a.bfloat16(), b.bfloat16()
+        A, B = _column_slice(a, 64), _column_slice(b, 64)
+        a64, b64 = a.double(), b.double()
+        run = lambda out, cs: h.gemm_tn(A, B, out=out, colsum_out=cs)
+    elif direct:
+        ah, bh = a.bfloat16(), b.bfloat16()
+        al, bl = (a - ah.float()).bfloat16(), (b - bh.float()).bfloat16()
+        a64, b64 = ah.double() + al.double(), bh.double() + bl.double()
+        P = [poisoned(t, ld=t.shape[1] + 8, extra_rows=64, device=DEV) for t in (ah, al, bh, bl)]          # NaN row padding, 64 NaN rows behind row M
+
+        def run(out, cs):
+            slabs, ns = h._tn_slabs(N, K, out)
+            h.check(h.lib().p3_gemm_tn_x3(h.ptr(P[0]), h.ptr(P[1]), N + 8, h.ptr(P[2]), h.ptr(P[3]), K + 8, h.ptr(out), out.stride(0), M, N, K, h.ptr(cs),
+                                          h.ptr(slabs), ns, h.stream()), "p3_gemm_tn_x3")
+    else:
+        ap, bp = _planes_in(a), _planes_in(b)
+        a64, b64 = _planes_value(ap), _planes_value(bp)
+        run = lambda out, cs: h.gemm_tn_x3(ap, bp, out=out, colsum_out=cs)
+    cs_preset = _rand(N, seed=32)
+    got = []
+    for _ in range(2 if level == 2 else 1):
+        out, g, own, preset = _accumulate_target(N, K)
+        cs, gcs = _vec(N, fill=cs_preset)
+        _, name = _launch(lambda: run(out, cs))
+        torch.cuda.synchronize()
+        assert name == kernel, (name, kernel)
+        g.check(valid=own)
+        gcs.check()
+        got.append((out, cs))
+    tag = f"{kernel} {M}x{N}x{K} ({steps} steps) level {level}"
+    _close(tag, got[0][0], preset + a64.t() @ b64, 2e-5 if bf else 1e-5)
+    _close(tag + " colsum", got[0][1], cs_preset.double() + a64.sum(0), 1e-4 if bf else 1e-5)
+    if level == 2:
+        assert torch.equal(got[1][0], got[0][0]) and torch.equal(got[1][1], got[0][1])
+
+
 @pytest.mark.parametrize("rows,cols", [(1, 8), (70, 136), (129, 384)])
 def test_planes_conversions_with_strided_source_and_destination(rows, cols):
     """to_planes / to_planes_into / from_planes: NaN-padded fp32 source, guarded padded destinations; the split is exact (hi = bf16(x), lo = bf16(x - hi):
