@@ -836,7 +836,7 @@ int64_t p3_init_contours_workspace_bytes(int B, int H, int W);
 /* ------------------------------------------------------------------------------------------
  * FFL corner-aware contour simplification: the array half of `post_process` (predict/ffl/polygonize_acm.py:277-284 and polygonize_asm.py:498-504:
  * skimage.measure.approximate_polygon, frame_field_utils.detect_corners :71-114 over math_utils.compute_crossfield_uv, polygonize_utils.split_polylines_corner
- * :47-61, LineString.simplify per piece) on the device.  The planar-graph half (unary_union, polygonize_full, the area / probability filters) stays host code.
+ * :47-61, LineString.simplify per piece) on the device.  The planar-graph half (unary_union, polygonize_full, the area / probability filters) is p3_ffl_polygons below.
  * Polyline i is the EXPLICIT point sequence q_0 .. q_{n-1} = pos[index[slice[i,0] .. slice[i,1])] (pos[slice ...] when index is NULL), the first point
  * appended once more when closed[i] is set; coordinates are (row, col).  A polyline with fewer than 2 explicit points gives no piece.
  *   DP(points, tol): Douglas-Peucker.  The first and last point are kept; in a section (s, e) the distance of point k is |cross(q_k - q_s, d)| / |d| with
@@ -1000,6 +1000,50 @@ int p3_hisup_polygons_rings(const int32_t* labels, const int32_t* n_regions, con
                             float* ring_pos, int32_t* ring_src, int64_t* ring_slice, int32_t* ring_region, int32_t* ring_flags, int32_t* ring_area2,
                             int32_t* region_rings, int32_t* n_holes, int32_t* ring_counts, int32_t* status, void* workspace, void* stream);
 int64_t p3_hisup_polygons_rings_workspace_bytes(int B, int H, int W, int max_regions, int max_vertices, int max_rings, int max_ring_vertices);
+
+/* ------------------------------------------------------------------------------------------
+ * FFL polygons: the planar-graph half of shapely_postprocess (predict/ffl/polygonize_acm.py:281-324, polygonize_asm.py:438-494: LineString per piece and
+ * the border ring, shapely.ops.unary_union, polygonize_full / polygonize, the min_area filter, polygonize_utils.compute_geom_prob :64-101 and the
+ * seg_threshold filter) on the device, behind p3_corner_split (csrc/ffl_polygons.hip).  DESIGN.md section 19 holds the definition in full.
+ * Input: the pieces as p3_corner_split leaves them - out_pos fp32 [V,2] (row, col), piece_slice int64 [Q,2], piece_batch int32 [Q] - and the indicator map
+ * fp32 [B,H,W].  x = col, y = row.  Per image b:
+ *   1  segments: the consecutive vertex pairs of the image's pieces, zero-length pairs dropped (-0 counts as +0), and the border ring (0,0), (0,H-1),
+ *      (W-1,H-1), (W-1,0).
+ *   2  a segment end that lies exactly on a border side splits that side there.
+ *   3  nodes: the distinct end points; edges: the distinct unordered node pairs.
+ *   4  two edges without a common node that share a point, or two edges with one common node that overlap collinearly (this covers a node inside an
+ *      edge): image_status bit 0 and the image gives no polygon.  Predicates are signs of (b-a) x (c-a) in double.  A coordinate that is not finite:
+ *      image_status bit 1, no polygon.
+ *   5  dangles: edges with an end of degree 1 are deleted until none is left; then every edge whose two half-edges lie on one traced ring (a cut).
+ *   6  faces: next(u->v) is the half-edge that comes before v->u in counter-clockwise order (half-plane, then cross product) among those leaving v, so that
+ *      bounded faces have a positive S = sum(x_i y_{i+1} - x_{i+1} y_i).
+ *   7  a ring starts at its half-edge of smallest key (origin (x, y), destination (x, y)); S is summed in double from there.  S > 0: a shell.  S < 0:
+ *      a hole of the smallest-area shell of another component that contains its start node (crossing number), else the unbounded face, dropped.
+ *      S == 0: image_status bit 2, no polygon.
+ *   8  a polygon: a shell and its holes in key order; the polygons of an image in key order of their shells, images in order.  area = S(shell) / 2 -
+ *      sum |S(hole) / 2|.  poly_flags bit 0: not (min_area < area).
+ *   9  probability, compute_geom_prob: the shell's bounds minx = int(min x), maxx = int(max x) + 1 (int() truncates towards zero), the same in y; prob = 0
+ *      when minx < 0 or miny < 0 or maxx > W or maxy > H.  Else every vertex becomes rint(x - minx) + minx (half to even, in the cropped window as the
+ *      reference rounds it), a pixel of the window [minx, maxx) x [miny, maxy) is covered by a ring set when it lies on an edge of a rounded ring or
+ *      inside by the even-odd rule over the whole set, raster = covered(shell) and not covered(holes), prob = sum(indicator[raster]) / count(raster) in
+ *      double, 0 without a pixel.  poly_flags bit 1: not (seg_threshold < prob).
+ * Outputs: ring_pos fp32 [max_vertices,2] (row, col; closed rings, the first vertex again at the end), ring_slice int64 [max_rings,2], poly_rings int64
+ * [max_polygons,2] = [first, one past the last) ring, the shell first; poly_batch int32, poly_area fp32, poly_prob fp32, poly_flags int32 [max_polygons];
+ * image_status int32 [B]; counts int32 [3] = (polygons, rings, vertices); status int32 [1]: bit 0 = a capacity was too small (counts hold the true totals,
+ * nothing is written past a capacity), bit 1 = a piece with piece_batch outside [0, B) or a piece_slice row outside [0, V] was left out.  With E = 2 V +
+ * 4 B (an image of n piece vertices has at most 2 n + 4 edges) E polygons, E rings and 3 E vertices can never overflow: a ring has 3 half-edges at least.
+ * Errors before any launch, P3_EINVAL with a message: negative counts, H or W < 2, NaN thresholds, null pointers, and piece_slice / piece_batch in host
+ * memory - the values are then checked right there (piece_batch out of [0, B), a piece_slice row outside out_pos), and the call is refused either way.
+ * An image of up to 1024 edge slots (its segments + its segment ends on the border + 4) runs in one workgroup with every working array in LDS, a larger
+ * one (or all, force_fallback != 0) runs the same device function over `workspace`; the probability takes one workgroup per polygon.  No floating-point
+ * atomics, no host synchronisation; two runs, either form, an image alone or inside a batch give the same bits.
+ * workspace: p3_ffl_polygons_workspace_bytes(V, B) bytes.
+ * ------------------------------------------------------------------------------------------ */
+int p3_ffl_polygons(const float* out_pos, int64_t V, const int64_t* piece_slice, const int32_t* piece_batch, int Q, const float* indicator, int B, int H,
+                    int W, double min_area, double seg_threshold, int force_fallback, int max_polygons, int max_rings, int max_vertices,
+                    float* ring_pos, int64_t* ring_slice, int64_t* poly_rings, int32_t* poly_batch, float* poly_area, float* poly_prob,
+                    int32_t* poly_flags, int32_t* image_status, int32_t* counts, int32_t* status, void* workspace, void* stream);
+int64_t p3_ffl_polygons_workspace_bytes(int64_t V, int B);
 
 #ifdef __cplusplus
 }

@@ -1442,8 +1442,71 @@ def corner_split(pos, index, poly_slice, closed, poly_batch, c0c2, tol_pre, tol,
                       dict(out_pos=0, out_src=0, piece_slice=1, piece_poly=1, piece_batch=1))
 
 
+# ------------------------------------------------------------------------------------------ FFL polygons: planar faces, area and probability filters
+def ffl_polygons_capacity(V, B):
+    """(max_polygons, max_rings, max_vertices) that cannot overflow for V piece vertices in B images: an image of n piece vertices has at most n segments and
+    n + 4 border edges (the four sides, cut once per vertex on them), E = 2 V + 4 B edges in all; every ring has 3 half-edges at least, so there are at
+    most 2 E / 3 <= E rings and polygons, and the closed rings hold at most 2 E + 2 E / 3 <= 3 E vertices."""
+    E = 2 * int(V) + 4 * int(B)
+    return E, E, 3 * E
+
+
+def ffl_polygons_device(out_pos, piece_slice, piece_batch, indicator, min_area, seg_threshold, max_polygons=None, max_rings=None, max_vertices=None,
+                        force_fallback=False, out=None):
+    """p3_ffl_polygons (the planar-graph half of FFL's shapely_postprocess: unary_union, polygonize_full, the area and probability filters; DESIGN.md
+    section 19) without any synchronisation.  out_pos fp32 [V,2] (row, col), piece_slice [Q,2], piece_batch [Q]: the pieces as corner_split leaves them;
+    indicator [B,H,W].
+    -> dict(ring_pos f32 [max_vertices,2] (row, col; closed rings), ring_slice i64 [max_rings,2], poly_rings i64 [max_polygons,2] (the rings of a polygon,
+    shell first), poly_batch i32, poly_area f32, poly_prob f32, poly_flags i32 [max_polygons] (bit 0: not min_area < area, bit 1: not seg_threshold <
+    prob), image_status i32 [B] (bit 0 not planar as given, bit 1 a coordinate is not finite, bit 2 a ring of area 0: the image gives no polygon),
+    counts i32 [3] = (polygons, rings, vertices), status i32 [1] (bit 0: a capacity was too small; counts are the true totals then and nothing is written
+    past the capacities; bit 1: a piece with piece_batch outside [0, B) or a slice outside out_pos was left out)).  The default capacities
+    (ffl_polygons_capacity) cannot overflow.  out: the caller's own tensors for any of the outputs (`_outputs`); they have to fit the capacities."""
+    for t in (out_pos, piece_slice, piece_batch, indicator):
+        _dev(t)
+    if out_pos.dtype != torch.float32 or out_pos.dim() != 2 or out_pos.shape[1] != 2:
+        raise P3Error(f"ffl_polygons: out_pos must be float32 [V, 2], got {out_pos.dtype} {tuple(out_pos.shape)}")
+    V, Q = out_pos.shape[0], piece_slice.shape[0]
+    if piece_slice.dim() != 2 or piece_slice.shape[1] != 2 or piece_batch.dim() != 1 or piece_batch.shape[0] != Q or piece_slice.dtype.is_floating_point \
+            or piece_batch.dtype.is_floating_point:
+        raise P3Error(f"ffl_polygons: integer piece_slice [Q, 2] and piece_batch [Q] expected, got {piece_slice.dtype} {tuple(piece_slice.shape)}, "
+                      f"{piece_batch.dtype} {tuple(piece_batch.shape)}")
+    if indicator.dim() != 3 or indicator.shape[0] < 1 or min(indicator.shape[1:]) < 2 or not indicator.dtype.is_floating_point:
+        raise P3Error(f"ffl_polygons: a floating-point indicator [B, H, W] with B >= 1 and H, W >= 2 expected, got {indicator.dtype} {tuple(indicator.shape)}")
+    B, H, W = indicator.shape
+    cap = ffl_polygons_capacity(V, B)
+    npoly, nr, nv = (c if m is None else int(m) for c, m in zip(cap, (max_polygons, max_rings, max_vertices)))
+    if npoly < 1 or nr < 1 or nv < 1:
+        raise P3Error(f"ffl_polygons: max_polygons = {max_polygons}, max_rings = {max_rings}, max_vertices = {max_vertices}")
+    dev, f32, i32, i64 = out_pos.device, torch.float32, torch.int32, torch.int64
+    out = _outputs("ffl_polygons", dev, (("ring_pos", (nv, 2), f32), ("ring_slice", (nr, 2), i64), ("poly_rings", (npoly, 2), i64), ("poly_batch", (npoly,), i32),
+                                         ("poly_area", (npoly,), f32), ("poly_prob", (npoly,), f32), ("poly_flags", (npoly,), i32), ("image_status", (B,), i32),
+                                         ("counts", (3,), i32), ("status", (1,), i32)), out)
+    # converted copies stay referenced until the launch is queued
+    p32, ind = out_pos.contiguous(), indicator.contiguous().float()
+    sl, pb = piece_slice.to(i64).contiguous(), piece_batch.to(i32).contiguous()
+    ws = workspace(int(lib().p3_ffl_polygons_workspace_bytes(V, B)), dev, "ffl_polygons")
+    check(lib().p3_ffl_polygons(ptr(p32), V, ptr(sl), ptr(pb), Q, ptr(ind), B, H, W, float(min_area), float(seg_threshold), int(bool(force_fallback)),
+                                npoly, nr, nv, ptr(out["ring_pos"]), ptr(out["ring_slice"]), ptr(out["poly_rings"]), ptr(out["poly_batch"]),
+                                ptr(out["poly_area"]), ptr(out["poly_prob"]), ptr(out["poly_flags"]), ptr(out["image_status"]), ptr(out["counts"]),
+                                ptr(out["status"]), ptr(ws), stream()), "p3_ffl_polygons")
+    return out
+
+
+def ffl_polygons(out_pos, piece_slice, piece_batch, indicator, min_area, seg_threshold, max_polygons=None, max_rings=None, max_vertices=None,
+                 force_fallback=False):
+    """the checking form of ffl_polygons_device: reads counts and status once (the only read-back), raises when a capacity was too small or a piece was
+    malformed and narrows the outputs to what was found; counts = (polygons, rings, vertices) as ints."""
+    out = ffl_polygons_device(out_pos, piece_slice, piece_batch, indicator, min_area, seg_threshold, max_polygons, max_rings, max_vertices, force_fallback)
+    fit = lambda P, R, Vn: (f"{P} polygons of {R} rings and {Vn} vertices do not fit max_polygons = {out['poly_rings'].shape[0]}, max_rings = "
+                            f"{out['ring_slice'].shape[0]}, max_vertices = {out['ring_pos'].shape[0]}")
+    return _read_back(out, "ffl_polygons", ((1, fit), (2, "a piece has piece_batch outside [0, B) or a piece_slice row outside out_pos")),
+                      dict(ring_pos=2, ring_slice=1, poly_rings=0, poly_batch=0, poly_area=0, poly_prob=0, poly_flags=0))
+
+
 # ------------------------------------------------------------------------------------------ FFL active-skeleton optimiser
 ASM_LDS_CAP = 4096         # csrc/asm.hip: nodes of one connected component that fit the one-launch LDS path
+FFL_POLY_LDS_CAP = 1024    # csrc/ffl_polygons.hip: edge slots of one image (its segments + its segment ends on the border + 4) that run in LDS
 ASM_MAX_KNOTS = 8
 
 

@@ -7,8 +7,9 @@ on the host) are built on the device too: `init_contours` (csrc/contours.hip, p3
 counts and no host contour.  The definition init_contours is held to is DESIGN.md section 13 (a pixel that equals the level exactly is linked by grid edge,
 not by coordinate).  `optimize_contours` still takes host contours a caller already has (`pre_computed={"init_contours_batch": ...}` of the reference).
 
-The array half of `post_process` behind (Douglas-Peucker, corner split) is polygonize_post.py; its shapely half (union, polygon assembly, filters) stays host code
-of the caller, and `tensorpoly_to_contours_batch` still hands the whole post-process the contours.
+`post_process` behind is polygonize_post.py: its array half (Douglas-Peucker, corner split) and its shapely half (union, polygon assembly, filters;
+`polygonize_post.polygonize_acm_polygons` is the whole of `PolygonizerACM.__call__`).  `tensorpoly_to_contours_batch` still hands a caller's own post-process
+the contours.
 The optional `dist` term (not in the shipped config) is not built; the ASM method is polygonize_asm.py.
 
 `TensorPoly`, `contours_batch_to_tensorpoly` and `tensorpoly_to_contours_batch` keep the reference's fields (torch_lydorn/torchvision/transforms/tensorpoly.py):

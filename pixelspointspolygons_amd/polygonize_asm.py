@@ -9,8 +9,8 @@ The marching-squares initialisation in front (`init_method: marching_squares`, g
 on the device -> optimised skeleton on the device, with one read-back of a few counts per stage and no host contour.
 `contours_to_skeleton`, `skeletons_to_tensorskeleton` and the host `AsmPlan` stay for callers that already hold host contours or skeletons.
 
-What stays host code of the caller: the `skimage` skeletonize plus `skan` initialisation (`init_method: skeleton`) in front, and the shapely half of
-`post_process` behind (its corner split is polygonize_post.corner_split_skeleton).
+What stays host code of the caller: the `skimage` skeletonize plus `skan` initialisation (`init_method: skeleton`) in front.  `post_process` behind is
+polygonize_post.py: `corner_split_skeleton`, and `polygonize_asm_polygons` for the whole of `PolygonizerASM.__call__` down to the filtered polygons.
 
 `Skeleton`, `Paths`, `TensorSkeleton`, `skeletons_to_tensorskeleton` and `tensorskeleton_to_skeletons` keep the fields of
 torch_lydorn/torchvision/transforms/tensorskeleton.py: pos [N,2] (row, col), degrees [N], path_index [M], path_delim [P+1], batch [N], batch_delim [B+1],

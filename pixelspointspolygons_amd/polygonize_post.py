@@ -3,9 +3,12 @@ polygonize_asm.py:498-504) - approximate_polygon, detect_corners over compute_cr
 as one call of csrc/corner_split.hip (p3_corner_split) on the optimised `TensorPoly` (ACM) or `TensorSkeleton` (ASM) that never left the GPU.  DESIGN.md
 section 14 holds the definition; Douglas-Peucker is held to a float64 restatement and hand-checkable cases, not to skimage or GEOS.
 
-What stays host code of the caller (INTEGRATION.md): the planar-graph half - `LineString(piece[:, ::-1])` per piece, the border ring,
-`shapely.ops.unary_union`, `polygonize_full`, the area / probability filters.  `pieces_to_host` hands it the pieces: a few hundred vertices per batch
-instead of every optimised vertex.
+The planar-graph half behind it - `LineString(piece[:, ::-1])` per piece, the border ring, `shapely.ops.unary_union`, `polygonize_full`, the area /
+probability filters - runs on the device too: `polygons_from_pieces` (csrc/ffl_polygons.hip, p3_ffl_polygons) makes polygons with
+holes, areas, probabilities and filter flags out of the pieces, `polygonize_acm_polygons` / `polygonize_asm_polygons` are the whole of
+`PolygonizerACM.__call__` / `PolygonizerASM.__call__`, and `polygons_to_host` gives the reference's (polygons_batch, probs_batch).  An image whose pieces
+are not planar as given (GEOS would insert nodes there) is flagged in image_status and gives no polygon: for that image the caller runs the shapely block of
+INTEGRATION.md on `pieces_to_host`.
 
 A tolerance list gives a dict keyed "tol_{}", as the reference's shapely_postprocess does."""
 import numpy as np
@@ -101,3 +104,63 @@ def polygonize_asm_pieces(seg_batch, crossfield_batch, config, tolerance=None):
     if tensorskeleton is None:
         return _empty_pieces(seg_batch, tolerance)
     return corner_split_skeleton(tensorskeleton, crossfield_batch, tolerance)
+
+
+# ------------------------------------------------------------------------------------------ polygons
+def _indicator(seg_batch, name):
+    if not torch.is_tensor(seg_batch) or not seg_batch.is_cuda:
+        raise hip.P3Error(f"{name}: seg_batch must be on the device (there is no CPU path)")
+    if seg_batch.dim() != 4 or seg_batch.shape[1] < 1:
+        raise hip.P3Error(f"{name}: seg_batch should be (N, C, H, W), got {tuple(seg_batch.shape)}")
+    return seg_batch[:, 0]
+
+
+def polygons_from_pieces(result, seg_batch, config, force_fallback=False):
+    """The pieces of a corner-split result (or its "tol_{}" dict) -> polygons on the device: hip.ffl_polygons on the indicator seg_batch[:, 0] with
+    config["min_area"] and config["seg_threshold"].  -> the trimmed dict of hip.ffl_polygons plus batch_size, or a dict of those keyed "tol_{}".  One
+    read-back (counts and status) per tolerance."""
+    indicator = _indicator(seg_batch, "polygons_from_pieces")
+    if "out_pos" not in result:
+        return {k: polygons_from_pieces(v, seg_batch, config, force_fallback) for k, v in result.items()}
+    if not result["out_pos"].is_cuda:
+        raise hip.P3Error("polygons_from_pieces: the pieces must be on the device (there is no CPU path)")
+    if int(result["batch_size"]) != indicator.shape[0]:
+        raise hip.P3Error(f"polygons_from_pieces: the pieces come from {result['batch_size']} images, seg_batch holds {indicator.shape[0]}")
+    out = hip.ffl_polygons(result["out_pos"], result["piece_slice"], result["piece_batch"], indicator, config["min_area"], config["seg_threshold"],
+                           force_fallback=force_fallback)
+    out["batch_size"] = indicator.shape[0]
+    return out
+
+
+def polygonize_acm_polygons(seg_batch, crossfield_batch, config=polygonize_acm.ACM_DEFAULTS, tolerance=None):
+    """PolygonizerACM.__call__ on the device: polygonize_acm_pieces followed by polygons_from_pieces.  A batch without any contour gives the border
+    polygon of every image (the filters decide about it), never None."""
+    _indicator(seg_batch, "polygonize_acm_polygons")
+    return polygons_from_pieces(polygonize_acm_pieces(seg_batch, crossfield_batch, config, tolerance), seg_batch, config)
+
+
+def polygonize_asm_polygons(seg_batch, crossfield_batch, config, tolerance=None):
+    """PolygonizerASM.__call__ (config["init_method"] must be "marching_squares") on the device: polygonize_asm_pieces followed by polygons_from_pieces."""
+    _indicator(seg_batch, "polygonize_asm_polygons")
+    return polygons_from_pieces(polygonize_asm_pieces(seg_batch, crossfield_batch, config, tolerance), seg_batch, config)
+
+
+def polygons_to_host(result, kept_only=True):
+    """-> (polygons_batch, probs_batch, image_status): per image a list of (exterior, [interiors]) with float64 [n, 2] (x, y) arrays, closed, ready for
+    shapely.geometry.Polygon(*p), and the list of their probabilities, in the device's order; image_status as a list of ints (an image with a bit set has
+    no polygon here: INTEGRATION.md).  kept_only: leave out the polygons a filter flagged (poly_flags != 0), as the reference does.  A "tol_{}" dict
+    gives a dict of those.  One download per field."""
+    if "ring_pos" not in result:
+        return {k: polygons_to_host(v, kept_only) for k, v in result.items()}
+    pos = result["ring_pos"].cpu().numpy().astype(np.float64)[:, ::-1]
+    rsl, prs = result["ring_slice"].cpu().numpy(), result["poly_rings"].cpu().numpy()
+    pb, prob, flags = result["poly_batch"].cpu().numpy(), result["poly_prob"].cpu().numpy(), result["poly_flags"].cpu().numpy()
+    B = int(result["batch_size"])
+    polygons, probs = [[] for _ in range(B)], [[] for _ in range(B)]
+    for (r0, r1), b, p, f in zip(prs, pb, prob, flags):
+        if kept_only and f:
+            continue
+        rings = [np.ascontiguousarray(pos[s:e]) for s, e in rsl[r0:r1]]
+        polygons[int(b)].append((rings[0], rings[1:]))
+        probs[int(b)].append(float(p))
+    return polygons, probs, result["image_status"].cpu().tolist()
