@@ -179,10 +179,8 @@ extern "C" int p3_acm_optimize(float* pos, int64_t N, const int32_t* poly_slice,
     if (fast) {
         size_t lds = (size_t)lds_len * 2 * sizeof(float2);
         if (lds < 64) lds = 64;
-        acm_lds_kernel<<<dim3(P), dim3(ACM_THREADS), lds, s>>>((float2*)pos, N, poly_slice, poly_batch, is_endpoint, f, sc, first_iter, steps, lds_len,
-                                                                poly_losses);
-        P3_LAUNCH_CHECK();
-        if (p3_tracing()) p3_note_kernel("acm_lds_kernel");
+        P3_TRY(p3_launch<acm_lds_kernel>("acm_lds_kernel", P, ACM_THREADS, lds, s, (float2*)pos, N, poly_slice, poly_batch, is_endpoint, f, sc, first_iter, steps, lds_len,
+                                         poly_losses));
     }
     if (slow) {
         float2* ws = (float2*)workspace;
@@ -191,16 +189,12 @@ extern "C" int p3_acm_optimize(float* pos, int64_t N, const int32_t* poly_slice,
             const float2* src = (k & 1) ? ws : (const float2*)pos;
             float2* dst = (k & 1) ? (float2*)pos : ws;
             const float lr = acm_lr(sc, first_iter + k);
-            acm_global_kernel<<<dim3(P, (unsigned)chunks), dim3(ACM_THREADS), 0, s>>>(src, dst, N, poly_slice, poly_batch, is_endpoint, f, lr, lds_len,
-                                                                                      force_fallback, k == steps - 1 ? vloss : nullptr);
-            P3_LAUNCH_CHECK();
+            P3_TRY(p3_launch<acm_global_kernel>("acm_global_kernel", dim3(P, (unsigned)chunks), ACM_THREADS, 0, s, src, dst, N, poly_slice, poly_batch, is_endpoint, f, lr,
+                                                lds_len, force_fallback, k == steps - 1 ? vloss : nullptr));
         }
-        if ((steps & 1) || poly_losses) {
-            acm_global_finish_kernel<<<dim3(P), dim3(ACM_THREADS), 0, s>>>(ws, (float2*)pos, N, poly_slice, poly_batch, B, lds_len, force_fallback, steps & 1,
-                                                                           vloss, poly_losses);
-            P3_LAUNCH_CHECK();
-        }
-        if (p3_tracing()) p3_note_kernel("acm_global_kernel");
+        if ((steps & 1) || poly_losses)
+            P3_TRY(p3_launch<acm_global_finish_kernel>(nullptr, P, ACM_THREADS, 0, s, ws, (float2*)pos, N, poly_slice, poly_batch, B, lds_len, force_fallback, steps & 1,
+                                                       vloss, poly_losses));
     }
     return P3_OK;
 }

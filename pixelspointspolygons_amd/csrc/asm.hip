@@ -301,9 +301,8 @@ extern "C" int p3_asm_optimize(float* pos, float* sq, int64_t N, const int32_t* 
     if (fast) {
         size_t lds = (size_t)lds_len * 2 * sizeof(float2);
         if (lds < 64) lds = 64;
-        asm_lds_kernel<<<dim3(C), dim3(ASM_THREADS), lds, s>>>((float2*)pos, (float2*)sq, N, pl, f, sc, first_iter, steps, lds_len, (float2*)grad_out, comp_losses);
-        P3_LAUNCH_CHECK();
-        if (p3_tracing()) p3_note_kernel("asm_lds_kernel");
+        P3_TRY(p3_launch<asm_lds_kernel>("asm_lds_kernel", C, ASM_THREADS, lds, s, (float2*)pos, (float2*)sq, N, pl, f, sc, first_iter, steps, lds_len, (float2*)grad_out,
+                                         comp_losses));
     }
     if (slow) {
         float2* ws = (float2*)workspace;
@@ -315,15 +314,11 @@ extern "C" int p3_asm_optimize(float* pos, float* sq, int64_t N, const int32_t* 
             const AsmCoefs co = asm_coefs(sc, first_iter + k, lr_k);
             lr_k = lr_k * sc.gamma;
             const bool last = k == steps - 1;
-            asm_global_kernel<<<dim3(C, (unsigned)chunks), dim3(ASM_THREADS), 0, s>>>(src, dst, (float2*)sq, N, pl, f, co, lds_len, force_fallback,
-                                                                                      last ? (float2*)grad_out : nullptr, last ? nloss : nullptr);
-            P3_LAUNCH_CHECK();
+            P3_TRY(p3_launch<asm_global_kernel>("asm_global_kernel", dim3(C, (unsigned)chunks), ASM_THREADS, 0, s, src, dst, (float2*)sq, N, pl, f, co, lds_len,
+                                                force_fallback, last ? (float2*)grad_out : nullptr, last ? nloss : nullptr));
         }
-        if ((steps & 1) || comp_losses) {
-            asm_global_finish_kernel<<<dim3(C), dim3(ASM_THREADS), 0, s>>>(ws, (float2*)pos, N, pl, lds_len, force_fallback, steps & 1, nloss, comp_losses);
-            P3_LAUNCH_CHECK();
-        }
-        if (p3_tracing()) p3_note_kernel("asm_global_kernel");
+        if ((steps & 1) || comp_losses)
+            P3_TRY(p3_launch<asm_global_finish_kernel>(nullptr, C, ASM_THREADS, 0, s, ws, (float2*)pos, N, pl, lds_len, force_fallback, steps & 1, nloss, comp_losses));
     }
     return P3_OK;
 }

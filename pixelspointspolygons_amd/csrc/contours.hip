@@ -143,11 +143,8 @@ __global__ __launch_bounds__(IC_SCAN_THREADS) void ic_scan_tiles_kernel(int* sum
     int carry = 0;
     for (int at = 0; at < n; at += IC_SCAN_THREADS) {
         const int i = at + threadIdx.x;
-        const int v = i < n ? sums[i] : 0;
-        int total;
-        const int ex = wg_scan<false, int>(v, lds, total) - v;
-        if (i < n) sums[i] = carry + ex;
-        carry += total;
+        const int ex = wg_excl(i < n ? sums[i] : 0, lds, carry);
+        if (i < n) sums[i] = ex;
     }
     if (threadIdx.x == 0) sums[n] = carry;
 }
@@ -293,16 +290,12 @@ __global__ __launch_bounds__(IC_THREADS) void ic_key_reduce_kernel(int K, int tp
     for (int j = 0; j < IC_ITEMS; ++j) {
         const int k = blockIdx.x * IC_TILE + threadIdx.x * IC_ITEMS + j;
         const int len = k < K ? klen[(int64_t)b * K + k] : 0;
-        if (len > 0) { acc += ((unsigned long long)len << 32) | 1ull; longest = max(longest, len); }
+        if (len > 0) { acc += p3_pack2(len, 1); longest = max(longest, len); }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) longest = max(longest, __shfl_xor(longest, o, 64));
-    if ((threadIdx.x & 63) == 0) lmax[threadIdx.x >> 6] = longest;
+    const int mx = wg_max(longest, lmax);
     unsigned long long total;
-    wg_scan<false, unsigned long long>(acc, lds, total);          // its barriers publish lmax too
+    wg_scan<false, unsigned long long>(acc, lds, total);
     if (threadIdx.x == 0) {
-        int mx = 0;
-        for (int i = 0; i < IC_THREADS / 64; ++i) mx = max(mx, lmax[i]);
         tile_sums[b * tpk + blockIdx.x] = total;
         tile_max[b * tpk + blockIdx.x] = mx;
     }
@@ -319,27 +312,26 @@ __global__ __launch_bounds__(IC_SCAN_THREADS) void ic_key_scan_tiles_kernel(unsi
     int longest = 0;
     for (int at = 0; at < n; at += IC_SCAN_THREADS) {
         const int i = at + threadIdx.x;
-        const unsigned long long v = i < n ? sums[i] : 0ull;
         if (i < n) longest = max(longest, tile_max[i]);
-        unsigned long long total;
-        const unsigned long long ex = wg_scan<false, unsigned long long>(v, lds, total) - v;
-        if (i < n) sums[i] = carry + ex;
-        carry += total;
+        const unsigned long long ex = wg_excl(i < n ? sums[i] : 0ull, lds, carry);
+        if (i < n) sums[i] = ex;
     }
     if (threadIdx.x == 0) sums[n] = carry;
+    // the maximum by hand, thread 0 folds the 16 wave maxima below: wg_max here (its two barriers over 16 waves, every thread folding) measured 0.4 us on the 85 us
+    // of the whole call, on the one serial workgroup every launch of the stage waits for
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) longest = max(longest, __shfl_xor(longest, o, 64));
     if ((threadIdx.x & 63) == 0) lmax[threadIdx.x >> 6] = longest;
-    __syncthreads();          // also: sums[] of this workgroup are visible to it
+    __syncthreads();          // lmax[], and sums[] of this workgroup, are visible to it
     for (int b = threadIdx.x; b < B; b += IC_SCAN_THREADS) {
         const unsigned long long d = sums[(b + 1) * tpk] - sums[b * tpk];
-        n_vertices[b] = (int32_t)(d >> 32);
-        n_contours[b] = (int32_t)(d & 0xffffffffull);
+        n_vertices[b] = p3_hi32(d);
+        n_contours[b] = p3_lo32(d);
     }
     if (threadIdx.x == 0) {
         int mx = 0;
         for (int i = 0; i < IC_SCAN_THREADS / 64; ++i) mx = max(mx, lmax[i]);
-        const int N = (int)(carry >> 32), P = (int)(carry & 0xffffffffull);
+        const int N = p3_hi32(carry), P = p3_lo32(carry);
         counts[0] = N; counts[1] = P; counts[2] = mx;
         status[0] = (N > max_vertices || P > max_contours) ? 1 : 0;
     }
@@ -355,16 +347,16 @@ __global__ __launch_bounds__(IC_THREADS) void ic_key_place_kernel(int K, int tpk
 #pragma unroll
     for (int j = 0; j < IC_ITEMS; ++j) {
         len[j] = first + j < K ? klen[(int64_t)b * K + first + j] : 0;
-        if (len[j] > 0) mine += ((unsigned long long)len[j] << 32) | 1ull;
+        if (len[j] > 0) mine += p3_pack2(len[j], 1);
     }
     unsigned long long total;
     unsigned long long at = tile_offs[b * tpk + blockIdx.x] + wg_scan<false, unsigned long long>(mine, lds, total) - mine;
 #pragma unroll
     for (int j = 0; j < IC_ITEMS; ++j) {
         if (len[j] <= 0) continue;
-        koff[(int64_t)b * K + first + j] = (int)(at >> 32);
-        kidx[(int64_t)b * K + first + j] = (int)(at & 0xffffffffull);
-        at += ((unsigned long long)len[j] << 32) | 1ull;
+        koff[(int64_t)b * K + first + j] = p3_hi32(at);
+        kidx[(int64_t)b * K + first + j] = p3_lo32(at);
+        at += p3_pack2(len[j], 1);
     }
 }
 
@@ -393,13 +385,19 @@ __global__ __launch_bounds__(IC_THREADS) void ic_emit_kernel(const int* nv, int 
 }
 
 // ---------------------------------------------------------------------------------------------------------------- workspace
-struct IcLayout {
+struct IcWs {
     int64_t E, K, tpe, tpk, BE, BK;
-    int64_t o_vertex_of, o_vpos, o_vsucc, o_vpred, o_vkey, o_vimg, o_st_a, o_st_b, o_klen, o_koff, o_kidx, o_esums, o_ksums, o_kmax, bytes;
     int rounds;
+    int* vertex_of;
+    float2* vpos;
+    int *vsucc, *vpred, *vkey, *vimg;
+    int4* st[2];          // pass 1 ping-pongs between the two; pass 2 lives in the one pass 1 did not finish in
+    int *klen, *koff, *kidx, *esums;
+    unsigned long long* ksums;
+    int* kmax;
 };
-static IcLayout ic_layout(int B, int H, int W) {
-    IcLayout l;
+static IcWs ic_carve(int B, int H, int W, P3Carve& c) {
+    IcWs l;
     memset(&l, 0, sizeof l);
     if (B < 1 || H < 2 || W < 2) return l;
     l.E = (int64_t)H * (W - 1) + (int64_t)(H - 1) * W;
@@ -410,26 +408,28 @@ static IcLayout ic_layout(int B, int H, int W) {
     l.BK = B * l.K;
     l.rounds = 1;
     while (((int64_t)1 << l.rounds) < l.E) ++l.rounds;
-    int64_t at = 0;
-    l.o_vertex_of = at; at += p3_up256(l.BE * 4);
-    l.o_vpos = at; at += p3_up256(l.BE * 8);
-    l.o_vsucc = at; at += p3_up256(l.BE * 4);
-    l.o_vpred = at; at += p3_up256(l.BE * 4);
-    l.o_vkey = at; at += p3_up256(l.BE * 4);
-    l.o_vimg = at; at += p3_up256(l.BE * 4);
-    l.o_st_a = at; at += p3_up256(l.BE * 16);          // pass 1 ping-pongs between a and b; pass 2 lives in the one pass 1 did not finish in
-    l.o_st_b = at; at += p3_up256(l.BE * 16);
-    l.o_klen = at; at += p3_up256(l.BK * 4);
-    l.o_koff = at; at += p3_up256(l.BK * 4);
-    l.o_kidx = at; at += p3_up256(l.BK * 4);
-    l.o_esums = at; at += p3_up256((B * l.tpe + 1) * 4);
-    l.o_ksums = at; at += p3_up256((B * l.tpk + 1) * 8);
-    l.o_kmax = at; at += p3_up256(B * l.tpk * 4);
-    l.bytes = at;
+    l.vertex_of = c.take<int>(l.BE);
+    l.vpos = c.take<float2>(l.BE);
+    l.vsucc = c.take<int>(l.BE);
+    l.vpred = c.take<int>(l.BE);
+    l.vkey = c.take<int>(l.BE);
+    l.vimg = c.take<int>(l.BE);
+    l.st[0] = c.take<int4>(l.BE);
+    l.st[1] = c.take<int4>(l.BE);
+    l.klen = c.take<int>(l.BK);
+    l.koff = c.take<int>(l.BK);
+    l.kidx = c.take<int>(l.BK);
+    l.esums = c.take<int>(B * l.tpe + 1);
+    l.ksums = c.take<unsigned long long>(B * l.tpk + 1);
+    l.kmax = c.take<int>(B * l.tpk);
     return l;
 }
 
-extern "C" int64_t p3_init_contours_workspace_bytes(int B, int H, int W) { return ic_layout(B, H, W).bytes; }
+extern "C" int64_t p3_init_contours_workspace_bytes(int B, int H, int W) {
+    P3Carve c = {nullptr, 0};
+    ic_carve(B, H, W, c);
+    return c.at;
+}
 
 extern "C" int p3_init_contours(const float* indicator, int64_t stride_b, int64_t stride_r, int64_t stride_c, int B, int H, int W, double level, int max_vertices,
                                 int max_contours, float* pos, int64_t* poly_slice, int32_t* poly_batch, int64_t* batch, uint8_t* is_endpoint, int32_t* counts,
@@ -442,56 +442,46 @@ extern "C" int p3_init_contours(const float* indicator, int64_t stride_b, int64_
     P3_CHECK(level == level, P3_EINVAL, "p3_init_contours: level is NaN");
     hipStream_t s = (hipStream_t)stream;
     if (H < 2 || W < 2) {          // no cell, no contour
-        if (hipMemsetAsync(counts, 0, 3 * sizeof(int32_t), s) != hipSuccess || hipMemsetAsync(n_contours, 0, B * sizeof(int32_t), s) != hipSuccess ||
-            hipMemsetAsync(n_vertices, 0, B * sizeof(int32_t), s) != hipSuccess || hipMemsetAsync(status, 0, sizeof(int32_t), s) != hipSuccess)
-            P3_CHECK(false, P3_EINVAL, "p3_init_contours: hipMemsetAsync failed");
-        return P3_OK;
+        P3_TRY(p3_memset(counts, 0, 3 * sizeof(int32_t), s));
+        P3_TRY(p3_memset(n_contours, 0, B * sizeof(int32_t), s));
+        P3_TRY(p3_memset(n_vertices, 0, B * sizeof(int32_t), s));
+        return p3_memset(status, 0, sizeof(int32_t), s);
     }
     P3_CHECK(workspace, P3_EINVAL, "p3_init_contours: null workspace (p3_init_contours_workspace_bytes(B, H, W))");
     P3_CHECK(B <= 65535, P3_ESHAPE, "p3_init_contours: B > 65535");
-    const IcLayout l = ic_layout(B, H, W);
-    char* ws = (char*)workspace;
-    int* vertex_of = (int*)(ws + l.o_vertex_of);
-    float2* vpos = (float2*)(ws + l.o_vpos);
-    int *vsucc = (int*)(ws + l.o_vsucc), *vpred = (int*)(ws + l.o_vpred), *vkey = (int*)(ws + l.o_vkey), *vimg = (int*)(ws + l.o_vimg);
-    int4* st[2] = {(int4*)(ws + l.o_st_a), (int4*)(ws + l.o_st_b)};
-    int *klen = (int*)(ws + l.o_klen), *koff = (int*)(ws + l.o_koff), *kidx = (int*)(ws + l.o_kidx), *esums = (int*)(ws + l.o_esums), *kmax = (int*)(ws + l.o_kmax);
-    unsigned long long* ksums = (unsigned long long*)(ws + l.o_ksums);
+    P3Carve carve = {(char*)workspace, 0};
+    const IcWs l = ic_carve(B, H, W, carve);
     IcMap m;
     m.ind = indicator; m.sb = stride_b; m.sr = stride_r; m.sc = stride_c; m.B = B; m.H = H; m.W = W; m.level = level;
     m.E = (int)l.E; m.Hh = H * (W - 1); m.K = (int)l.K; m.tpe = (int)l.tpe; m.tpk = (int)l.tpk;
     const int ntile_e = B * (int)l.tpe;
-    const int* nv = esums + ntile_e;          // the vertex count, on the device
+    const int* nv = l.esums + ntile_e;          // the vertex count, on the device
     const int64_t want = (l.BE + IC_THREADS - 1) / IC_THREADS;
     const dim3 vgrid((unsigned)(want < IC_MAX_GRID ? want : IC_MAX_GRID)), egrid((unsigned)l.tpe, (unsigned)B), kgrid((unsigned)l.tpk, (unsigned)B);
 
-    if (hipMemsetAsync(klen, 0, l.BK * sizeof(int), s) != hipSuccess) P3_CHECK(false, P3_EINVAL, "p3_init_contours: hipMemsetAsync failed");
-    ic_count_kernel<<<egrid, IC_THREADS, 0, s>>>(m, esums);
-    ic_scan_tiles_kernel<<<1, IC_SCAN_THREADS, 0, s>>>(esums, ntile_e);
-    ic_compact_kernel<<<egrid, IC_THREADS, 0, s>>>(m, esums, vertex_of, vpos, vsucc, vpred, vkey, vimg);
-    ic_link_kernel<<<vgrid, IC_THREADS, 0, s>>>(nv, m.E, vertex_of, vimg, vkey, vsucc, vpred, st[0]);
-    P3_LAUNCH_CHECK();
+    P3_TRY(p3_memset(l.klen, 0, l.BK * sizeof(int), s));
+    P3_TRY(p3_launch<ic_count_kernel>(nullptr, egrid, IC_THREADS, 0, s, m, l.esums));
+    P3_TRY(p3_launch<ic_scan_tiles_kernel>(nullptr, 1, IC_SCAN_THREADS, 0, s, l.esums, ntile_e));
+    P3_TRY(p3_launch<ic_compact_kernel>(nullptr, egrid, IC_THREADS, 0, s, m, l.esums, l.vertex_of, l.vpos, l.vsucc, l.vpred, l.vkey, l.vimg));
+    P3_TRY(p3_launch<ic_link_kernel>(nullptr, vgrid, IC_THREADS, 0, s, nv, m.E, l.vertex_of, l.vimg, l.vkey, l.vsucc, l.vpred, l.st[0]));
     const int fin = l.rounds & 1;          // pass 1 ends in st[fin]
-    int2* rk[2] = {(int2*)st[1 - fin], (int2*)st[1 - fin] + l.BE};
+    int2* rk[2] = {(int2*)l.st[1 - fin], (int2*)l.st[1 - fin] + l.BE};
     const char* forced = getenv("P3_IC_DOUBLING");
     const bool per_image = (forced && forced[0] == 'i') || (!(forced && forced[0] == 'r') && l.E <= IC_IMAGE_MAX_EDGES);
     if (!per_image) {
-        for (int k = 0; k < l.rounds; ++k) ic_minmax_round_kernel<<<vgrid, IC_THREADS, 0, s>>>(nv, st[k & 1], st[(k + 1) & 1]);
-        ic_rank_init_kernel<<<vgrid, IC_THREADS, 0, s>>>(nv, st[fin], vpred, vkey, rk[0]);
-        for (int k = 0; k < l.rounds; ++k) ic_rank_round_kernel<<<vgrid, IC_THREADS, 0, s>>>(nv, rk[k & 1], rk[(k + 1) & 1]);
+        for (int k = 0; k < l.rounds; ++k) P3_TRY(p3_launch<ic_minmax_round_kernel>(nullptr, vgrid, IC_THREADS, 0, s, nv, l.st[k & 1], l.st[(k + 1) & 1]));
+        P3_TRY(p3_launch<ic_rank_init_kernel>(nullptr, vgrid, IC_THREADS, 0, s, nv, l.st[fin], l.vpred, l.vkey, rk[0]));
+        for (int k = 0; k < l.rounds; ++k) P3_TRY(p3_launch<ic_rank_round_kernel>("ic_rank_round_kernel", vgrid, IC_THREADS, 0, s, nv, rk[k & 1], rk[(k + 1) & 1]));
     } else {
-        ic_minmax_image_kernel<<<B, IC_IMAGE_THREADS, 0, s>>>(esums, m.tpe, l.rounds, st[0], st[1]);
-        ic_rank_image_kernel<<<B, IC_IMAGE_THREADS, 0, s>>>(esums, m.tpe, l.rounds, st[fin], vpred, vkey, rk[0], rk[1]);
+        P3_TRY(p3_launch<ic_minmax_image_kernel>(nullptr, B, IC_IMAGE_THREADS, 0, s, l.esums, m.tpe, l.rounds, l.st[0], l.st[1]));
+        P3_TRY(p3_launch<ic_rank_image_kernel>("ic_rank_image_kernel", B, IC_IMAGE_THREADS, 0, s, l.esums, m.tpe, l.rounds, l.st[fin], l.vpred, l.vkey, rk[0], rk[1]));
     }
-    P3_LAUNCH_CHECK();
     const int2* rank = rk[fin];          // pass 2 ends in rk[rounds & 1]
-    ic_tails_kernel<<<vgrid, IC_THREADS, 0, s>>>(nv, m.K, st[fin], rank, vsucc, vimg, klen);
-    ic_key_reduce_kernel<<<kgrid, IC_THREADS, 0, s>>>(m.K, m.tpk, klen, ksums, kmax);
-    ic_key_scan_tiles_kernel<<<1, IC_SCAN_THREADS, 0, s>>>(ksums, kmax, B, m.tpk, max_vertices, max_contours, counts, n_contours, n_vertices, status);
-    ic_key_place_kernel<<<kgrid, IC_THREADS, 0, s>>>(m.K, m.tpk, klen, ksums, koff, kidx);
-    ic_emit_kernel<<<vgrid, IC_THREADS, 0, s>>>(nv, m.K, st[fin], rank, vimg, vpos, klen, koff, kidx, max_vertices, max_contours, (float2*)pos, poly_slice, poly_batch,
-                                                batch, is_endpoint);
-    P3_LAUNCH_CHECK();
-    if (p3_tracing()) p3_note_kernel(per_image ? "ic_rank_image_kernel" : "ic_rank_round_kernel");
-    return P3_OK;
+    P3_TRY(p3_launch<ic_tails_kernel>(nullptr, vgrid, IC_THREADS, 0, s, nv, m.K, l.st[fin], rank, l.vsucc, l.vimg, l.klen));
+    P3_TRY(p3_launch<ic_key_reduce_kernel>(nullptr, kgrid, IC_THREADS, 0, s, m.K, m.tpk, l.klen, l.ksums, l.kmax));
+    P3_TRY(p3_launch<ic_key_scan_tiles_kernel>(nullptr, 1, IC_SCAN_THREADS, 0, s, l.ksums, l.kmax, B, m.tpk, max_vertices, max_contours, counts, n_contours, n_vertices,
+                                               status));
+    P3_TRY(p3_launch<ic_key_place_kernel>(nullptr, kgrid, IC_THREADS, 0, s, m.K, m.tpk, l.klen, l.ksums, l.koff, l.kidx));
+    return p3_launch<ic_emit_kernel>(nullptr, vgrid, IC_THREADS, 0, s, nv, m.K, l.st[fin], rank, l.vimg, l.vpos, l.klen, l.koff, l.kidx, max_vertices, max_contours,
+                                     (float2*)pos, poly_slice, poly_batch, batch, is_endpoint);
 }

@@ -259,14 +259,12 @@ __global__ __launch_bounds__(CS_SCAN_THREADS) void cs_offsets_kernel(CsIn in, in
         const int i = at + threadIdx.x;
         int64_t s0; int len = 0, n = 0;
         if (i < in.P) cs_range(in, i, s0, len, n);
-        int64_t total;
-        const int64_t incl = wg_scan<false, int64_t>((int64_t)n, red, total);
+        const int64_t ex = wg_excl((int64_t)n, red, carry);
         if (i < in.P) {
-            const bool fits = carry + incl <= in.E;
-            exoff[i] = fits ? carry + incl - n : -1;
+            const bool fits = ex + n <= in.E;
+            exoff[i] = fits ? ex : -1;
             over |= fits ? 0 : 1;
         }
-        carry += total;
     }
     if (__syncthreads_or(over) && threadIdx.x == 0) *flag = 2;
     if (threadIdx.x == 0) exoff[in.P] = carry < in.E ? carry : in.E;
@@ -317,21 +315,14 @@ __global__ __launch_bounds__(CS_SCAN_THREADS) void cs_scan_kernel(int P, const i
     for (int at = 0; at < P; at += CS_SCAN_THREADS) {
         const int i = at + threadIdx.x;
         unsigned long long v = 0;
-        if (i < P) { v = ((unsigned long long)(uint32_t)pcount[4 * (int64_t)i] << 32) | (uint32_t)pcount[4 * (int64_t)i + 1]; longest = max(longest, pcount[4 * (int64_t)i + 2]); }
-        unsigned long long total;
-        const unsigned long long incl = wg_scan<false, unsigned long long>(v, red, total);
-        if (i < P) ooff[i] = carry + incl - v;
-        carry += total;
+        if (i < P) { v = p3_pack2(pcount[4 * (int64_t)i], pcount[4 * (int64_t)i + 1]); longest = max(longest, pcount[4 * (int64_t)i + 2]); }
+        const unsigned long long ex = wg_excl(v, red, carry);
+        if (i < P) ooff[i] = ex;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) longest = max(longest, __shfl_xor(longest, o, 64));
-    if ((threadIdx.x & 63) == 0) lmax[threadIdx.x >> 6] = longest;
-    __syncthreads();
+    const int mx = wg_max(longest, lmax);
     if (threadIdx.x == 0) {
-        int mx = 0;
-        for (int i = 0; i < CS_SCAN_THREADS / 64; ++i) mx = max(mx, lmax[i]);
-        const long long nv = (long long)(carry >> 32), np = (long long)(carry & 0xffffffffull);
-        counts[0] = (int32_t)nv; counts[1] = (int32_t)np; counts[2] = mx;
+        const int nv = p3_hi32(carry), np = p3_lo32(carry);          // at most 2 E and E, and the entry point keeps E below 2^30
+        counts[0] = nv; counts[1] = np; counts[2] = mx;
         status[0] = ((nv > max_vertices || np > max_pieces) ? 1 : 0) | *flag;
     }
 }
@@ -364,31 +355,39 @@ __global__ __launch_bounds__(CS_THREADS) void cs_emit_kernel(CsIn in, CsStage st
 }
 
 // ---------------------------------------------------------------------------------------------------------------- workspace
-struct CsLayout { int64_t o_exoff, o_flag, o_pcount, o_ooff, o_src, o_piece, o_flags, o_pt, o_idx, o_se, o_key, o_state, o_mask, bytes; };
-static CsLayout cs_layout(int64_t E, int P) {
-    CsLayout l;
+struct CsWs {
+    int64_t* exoff;
+    int32_t *flag, *pcount;          // cleared together before every run: [flag, ooff)
+    unsigned long long* ooff;
+    int32_t* src; int2* piece; uint8_t* flags;
+    CsGlobal g;
+};
+static CsWs cs_carve(int64_t E, int P, P3Carve& c) {
+    CsWs l;
     memset(&l, 0, sizeof l);
     if (E < 1 || P < 1) return l;
     const int64_t E1 = E + (int64_t)CS_PAD * P;
-    int64_t at = 0;
-    l.o_exoff = at; at += p3_up256(((int64_t)P + 1) * 8);
-    l.o_flag = at; at += p3_up256(4);
-    l.o_pcount = at; at += p3_up256((int64_t)P * 16);
-    l.o_ooff = at; at += p3_up256((int64_t)P * 8);
-    l.o_src = at; at += p3_up256(2 * E * 4);
-    l.o_piece = at; at += p3_up256(E * 8);
-    l.o_flags = at; at += p3_up256(E);
-    l.o_pt = at; at += p3_up256(E * 8);
-    l.o_idx = at; at += p3_up256(E * 4);
-    l.o_se = at; at += p3_up256(E1 * 8);
-    l.o_key = at; at += p3_up256(E1 * 8);
-    l.o_state = at; at += p3_up256(E1);
-    l.o_mask = at; at += p3_up256(E);
-    l.bytes = at;
+    l.exoff = c.take<int64_t>((int64_t)P + 1);
+    l.flag = c.take<int32_t>(1);
+    l.pcount = c.take<int32_t>(4 * (int64_t)P);
+    l.ooff = c.take<unsigned long long>(P);
+    l.src = c.take<int32_t>(2 * E);
+    l.piece = c.take<int2>(E);
+    l.flags = c.take<uint8_t>(E);
+    l.g.pt = c.take<float2>(E);
+    l.g.idx = c.take<uint32_t>(E);
+    l.g.se = c.take<uint32_t>(2 * E1);
+    l.g.key = c.take<unsigned long long>(E1);
+    l.g.state = c.take<uint8_t>(E1);
+    l.g.mask = c.take<uint8_t>(E);
     return l;
 }
 
-extern "C" int64_t p3_corner_split_workspace_bytes(int64_t E, int P) { return cs_layout(E, P).bytes; }
+extern "C" int64_t p3_corner_split_workspace_bytes(int64_t E, int P) {
+    P3Carve c = {nullptr, 0};
+    cs_carve(E, P, c);
+    return c.at;
+}
 
 extern "C" int p3_corner_split(const float* pos, int64_t N, const int64_t* index, int64_t K, const int64_t* slice, const uint8_t* closed, const int32_t* poly_batch,
                                int P, const float* c0c2, int B, int H, int W, double tol_pre, double tol, int max_len, int force_fallback, int max_vertices,
@@ -403,37 +402,28 @@ extern "C" int p3_corner_split(const float* pos, int64_t N, const int64_t* index
     P3_CHECK(index || K == 0, P3_EINVAL, "p3_corner_split: K > 0 without index");
     hipStream_t s = (hipStream_t)stream;
     if (P == 0 || N == 0 || (index && K == 0)) {          // no explicit point
-        if (hipMemsetAsync(counts, 0, 3 * sizeof(int32_t), s) != hipSuccess || hipMemsetAsync(status, 0, sizeof(int32_t), s) != hipSuccess)
-            P3_CHECK(false, P3_EINVAL, "p3_corner_split: hipMemsetAsync failed");
-        return P3_OK;
+        P3_TRY(p3_memset(counts, 0, 3 * sizeof(int32_t), s));
+        return p3_memset(status, 0, sizeof(int32_t), s);
     }
     P3_CHECK(pos && slice && closed && poly_batch && c0c2, P3_EINVAL, "p3_corner_split: null pointer");
     P3_CHECK((max_vertices == 0 || (out_pos && out_src)) && (max_pieces == 0 || (piece_slice && piece_poly && piece_batch)), P3_EINVAL,
              "p3_corner_split: null output with a capacity above 0");
     P3_CHECK(workspace, P3_EINVAL, "p3_corner_split: null workspace (p3_corner_split_workspace_bytes((index ? K : N) + P, P))");
-    const CsLayout l = cs_layout(E, P);
-    char* ws = (char*)workspace;
+    P3Carve carve = {(char*)workspace, 0};
+    const CsWs l = cs_carve(E, P, carve);
     CsIn in;
     in.pos = (const float2*)pos; in.index = index; in.slice = slice; in.closed = closed; in.poly_batch = poly_batch; in.c0c2 = c0c2;
     in.N = N; in.K = index ? K : 0; in.E = E; in.P = P; in.B = B; in.H = H; in.W = W; in.tol_pre = tol_pre; in.tol = tol;
-    int64_t* exoff = (int64_t*)(ws + l.o_exoff);
-    int32_t* flag = (int32_t*)(ws + l.o_flag);
-    unsigned long long* ooff = (unsigned long long*)(ws + l.o_ooff);
-    CsStage st = {exoff, (int32_t*)(ws + l.o_src), (int2*)(ws + l.o_piece), (int32_t*)(ws + l.o_pcount), stage_flags ? stage_flags : (uint8_t*)(ws + l.o_flags)};
-    CsGlobal g = {(float2*)(ws + l.o_pt), (uint32_t*)(ws + l.o_idx), (uint32_t*)(ws + l.o_se), (unsigned long long*)(ws + l.o_key), (uint8_t*)(ws + l.o_state),
-                  (uint8_t*)(ws + l.o_mask)};
+    CsStage st = {l.exoff, l.src, l.piece, l.pcount, stage_flags ? stage_flags : l.flags};
     // a polyline nobody runs (under 2 points, over a wrong max_len, past the capacity E) has no piece and flags 0
-    if (hipMemsetAsync(ws + l.o_flag, 0, (size_t)(l.o_ooff - l.o_flag), s) != hipSuccess || hipMemsetAsync(st.flags, 0, (size_t)E, s) != hipSuccess)
-        P3_CHECK(false, P3_EINVAL, "p3_corner_split: hipMemsetAsync failed");
+    P3_TRY(p3_memset(l.flag, 0, (char*)l.ooff - (char*)l.flag, s));
+    P3_TRY(p3_memset(st.flags, 0, E, s));
     const bool fast = !force_fallback;
     const bool slow = force_fallback || max_len <= 0 || (int64_t)max_len + 1 > CS_LDS_CAP;          // + 1: the closing point
-    cs_offsets_kernel<<<1, CS_SCAN_THREADS, 0, s>>>(in, exoff, flag);
-    if (fast) cs_lds_kernel<<<P, CS_THREADS, 0, s>>>(in, st);
-    if (slow) cs_global_kernel<<<P, CS_THREADS, 0, s>>>(in, st, g, force_fallback ? 1 : 0);
-    P3_LAUNCH_CHECK();
-    cs_scan_kernel<<<1, CS_SCAN_THREADS, 0, s>>>(P, st.pcount, ooff, max_vertices, max_pieces, flag, counts, status);
-    cs_emit_kernel<<<P, CS_THREADS, 0, s>>>(in, st, ooff, max_vertices, max_pieces, (float2*)out_pos, out_src, piece_slice, piece_poly, piece_batch);
-    P3_LAUNCH_CHECK();
-    if (p3_tracing()) p3_note_kernel(fast ? "cs_lds_kernel" : "cs_global_kernel");
-    return P3_OK;
+    P3_TRY(p3_launch<cs_offsets_kernel>(nullptr, 1, CS_SCAN_THREADS, 0, s, in, l.exoff, l.flag));
+    if (fast) P3_TRY(p3_launch<cs_lds_kernel>("cs_lds_kernel", P, CS_THREADS, 0, s, in, st));
+    if (slow) P3_TRY(p3_launch<cs_global_kernel>(fast ? nullptr : "cs_global_kernel", P, CS_THREADS, 0, s, in, st, l.g, force_fallback ? 1 : 0));
+    P3_TRY(p3_launch<cs_scan_kernel>(nullptr, 1, CS_SCAN_THREADS, 0, s, P, st.pcount, l.ooff, max_vertices, max_pieces, l.flag, counts, status));
+    return p3_launch<cs_emit_kernel>(nullptr, P, CS_THREADS, 0, s, in, st, l.ooff, max_vertices, max_pieces, (float2*)out_pos, out_src, piece_slice, piece_poly,
+                                     piece_batch);
 }

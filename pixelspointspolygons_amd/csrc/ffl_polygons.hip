@@ -99,7 +99,7 @@ __device__ __forceinline__ bool ffp_not_planar(const FfpPt* node, int a, int b, 
 }
 __device__ __forceinline__ int ffp_origin(const FfpWork& w, int h) { return (h & 1) ? w.ev[h >> 1] : w.eu[h >> 1]; }
 __device__ __forceinline__ unsigned long long ffp_key(const FfpWork& w, int h) {
-    return ((unsigned long long)(uint32_t)ffp_origin(w, h) << 32) | (uint32_t)ffp_origin(w, h ^ 1);
+    return p3_pack2(ffp_origin(w, h), ffp_origin(w, h ^ 1));
 }
 // direction g comes before direction h counter-clockwise from the positive x axis (both leave node o)
 __device__ __forceinline__ bool ffp_angle_less(const FfpWork& w, int o, int g, int h) {
@@ -120,10 +120,8 @@ __device__ __forceinline__ void ffp_trace(const FfpWork& w, int N, int ne, int* 
     int carry = 0;
     for (int at = 0; at < N; at += FFP_THREADS) {
         const int n = at + tid, v = n < N ? w.deg[n] : 0;
-        int total;
-        const int incl = wg_scan<false, int>(v, red, total);
-        if (n < N) w.start[n] = carry + incl - v;
-        carry += total;
+        const int ex = wg_excl(v, red, carry);
+        if (n < N) w.start[n] = ex;
     }
     if (tid == 0) w.start[N] = carry;
     __syncthreads();
@@ -217,10 +215,8 @@ __device__ __forceinline__ int ffp_image(const FfpIn& in, const FfpWork& w, int 
                 if (!isfinite(a.x) || !isfinite(a.y) || !isfinite(c.x) || !isfinite(c.y)) atomicOr(&sh[0], 2);
                 if (!ffp_eq(a, c)) ++cnt;
             }
-        int total;
-        const int incl = wg_scan<false, int>(cnt, red, total);
+        int o = wg_excl(cnt, red, nseg);
         if (mine && cnt) {
-            int o = nseg + incl - cnt;
             for (int64_t k = s; k + 1 < e; ++k) {
                 const FfpPt a = ffp_load(in, k), c = ffp_load(in, k + 1);
                 if (ffp_eq(a, c)) continue;
@@ -228,7 +224,6 @@ __device__ __forceinline__ int ffp_image(const FfpIn& in, const FfpWork& w, int 
                 ++o;
             }
         }
-        nseg += total;
     }
     if (nseg > C - 4) { nseg = C - 4; if (tid == 0) atomicOr(&sh[0], 8); }          // cannot happen: ffp_count gave the image nseg + 4 slots at least
     __syncthreads();
@@ -364,10 +359,8 @@ __device__ __forceinline__ int ffp_image(const FfpIn& in, const FfpWork& w, int 
     int cr = 0, cv = 0;
     for (int at = 0; at < ns; at += FFP_THREADS) {          // deg[rank] = first ring, start[rank] = first vertex of the polygon
         const int r = at + tid, h = r < ns ? w.adj[r] : 0, nr = r < ns ? w.rank[h] : 0, nv = r < ns ? w.srt[h] : 0;
-        int tr, tv;
-        const int ir = wg_scan<false, int>(nr, red, tr), iv = wg_scan<false, int>(nv, red, tv);
-        if (r < ns) { w.deg[r] = cr + ir - nr; w.start[r] = cv + iv - nv; w.ringof[h] = r; }          // ringof[shell] = its rank from here on
-        cr += tr; cv += tv;
+        const int er = wg_excl(nr, red, cr), ev = wg_excl(nv, red, cv);
+        if (r < ns) { w.deg[r] = er; w.start[r] = ev; w.ringof[h] = r; }          // ringof[shell] = its rank from here on
     }
     __syncthreads();
     FFP_FOR(h, H2) {          // every ring that is put out: its index, its vertices
@@ -436,11 +429,8 @@ __global__ __launch_bounds__(FFP_SCAN_THREADS) void ffp_offsets_kernel(int B, co
     int64_t carry = 0;
     for (int at = 0; at < B; at += FFP_SCAN_THREADS) {
         const int i = at + threadIdx.x;
-        const int64_t v = i < B ? slots[i] : 0;
-        int64_t total;
-        const int64_t incl = wg_scan<false, int64_t>(v, red, total);
-        if (i < B) soff[i] = carry + incl - v;
-        carry += total;
+        const int64_t ex = wg_excl((int64_t)(i < B ? slots[i] : 0), red, carry);
+        if (i < B) soff[i] = ex;
     }
     if (threadIdx.x == 0) soff[B] = carry;
 }
@@ -490,15 +480,12 @@ __global__ __launch_bounds__(FFP_SCAN_THREADS) void ffp_scan_kernel(int B, const
     for (int at = 0; at < B; at += FFP_SCAN_THREADS) {
         const int i = at + threadIdx.x;
         for (int k = 0; k < 3; ++k) {
-            const int64_t v = i < B ? pcount[4 * (int64_t)i + k] : 0;
-            int64_t total;
-            const int64_t incl = wg_scan<false, int64_t>(v, red, total);
-            if (i < B) ioff[3 * (int64_t)i + k] = carry[k] + incl - v;
-            carry[k] += total;
+            const int64_t ex = wg_excl((int64_t)(i < B ? pcount[4 * (int64_t)i + k] : 0), red, carry[k]);
+            if (i < B) ioff[3 * (int64_t)i + k] = ex;
         }
     }
     if (threadIdx.x == 0) {
-        for (int k = 0; k < 3; ++k) { ioff[3 * (int64_t)B + k] = carry[k]; counts[k] = (int32_t)(carry[k] > 0x7fffffff ? 0x7fffffff : carry[k]); }
+        for (int k = 0; k < 3; ++k) { ioff[3 * (int64_t)B + k] = carry[k]; counts[k] = p3_sat31(carry[k]); }
         status[0] = ((carry[0] > max_polygons || carry[1] > max_rings || carry[2] > max_vertices) ? 1 : 0) | *flag;
     }
 }
@@ -632,38 +619,47 @@ __global__ __launch_bounds__(FFP_PROB_THREADS) void ffp_prob_kernel(int B, int H
 }
 
 // ---------------------------------------------------------------------------------------------------------------- workspace
-struct FfpLayout { int64_t S, I, o_slots, o_flag, o_pcount, o_soff, o_ioff, o_pos, o_ipos, o_ring, o_poly, o_area, o_aflag, o_rbox, o_rS, o_node, o_eu, o_ev, o_elive, o_fl, o_ints, bytes; };
-static FfpLayout ffp_layout(int64_t V, int B) {
-    FfpLayout l;
+struct FfpWs {
+    int64_t S;
+    int32_t* slots;
+    int32_t *flag, *pcount;          // cleared together before every run: [flag, soff)
+    int64_t *soff, *ioff;
+    FfpStage st;
+    FfpGlobal g;
+};
+static FfpWs ffp_carve(int64_t V, int B, P3Carve& c) {
+    FfpWs l;
     memset(&l, 0, sizeof l);
     if (V < 0 || B < 1) return l;
     const int64_t S = 3 * V + 4 * (int64_t)B, I = 2 * S + (int64_t)FFP_PAD * B;          // an image's slots: segments + 2 ends each + 4
-    int64_t at = 0;
-    l.S = S; l.I = I;
-    l.o_slots = at; at += p3_up256((int64_t)B * 4);
-    l.o_flag = at; at += p3_up256(4);
-    l.o_pcount = at; at += p3_up256((int64_t)B * 16);
-    l.o_soff = at; at += p3_up256(((int64_t)B + 1) * 8);
-    l.o_ioff = at; at += p3_up256(((int64_t)B + 1) * 24);
-    l.o_pos = at; at += p3_up256(3 * S * 8);
-    l.o_ipos = at; at += p3_up256(3 * S * 8);
-    l.o_ring = at; at += p3_up256(S * 8);
-    l.o_poly = at; at += p3_up256(S * 8);
-    l.o_area = at; at += p3_up256(S * 4);
-    l.o_aflag = at; at += p3_up256(S * 4);
-    l.o_rbox = at; at += p3_up256(S * 16);
-    l.o_rS = at; at += p3_up256(2 * S * 8);
-    l.o_node = at; at += p3_up256(I * 8);
-    l.o_eu = at; at += p3_up256(S * 4);
-    l.o_ev = at; at += p3_up256(S * 4);
-    l.o_elive = at; at += p3_up256(S);
-    l.o_fl = at; at += p3_up256(2 * S);
-    l.o_ints = at; at += p3_up256(10 * I * 4);
-    l.bytes = at;
+    l.S = S; l.g.I = I;
+    l.slots = c.take<int32_t>(B);
+    l.flag = c.take<int32_t>(1);
+    l.pcount = c.take<int32_t>(4 * (int64_t)B);
+    l.soff = c.take<int64_t>((int64_t)B + 1);
+    l.ioff = c.take<int64_t>(3 * ((int64_t)B + 1));
+    l.st.pos = c.take<float2>(3 * S);
+    l.st.ipos = c.take<int2>(3 * S);
+    l.st.ring = c.take<int2>(S);
+    l.st.poly = c.take<int2>(S);
+    l.st.area = c.take<float>(S);
+    l.st.aflag = c.take<int32_t>(S);
+    l.st.rbox = c.take<int4>(S);
+    l.g.rS = c.take<double>(2 * S);
+    l.g.node = c.take<FfpPt>(I);
+    l.g.eu = c.take<int32_t>(S);
+    l.g.ev = c.take<int32_t>(S);
+    l.g.elive = c.take<uint8_t>(S);
+    l.g.fl = c.take<uint8_t>(2 * S);
+    l.g.ints = c.take<int32_t>(10 * I);
     return l;
 }
 
-extern "C" int64_t p3_ffl_polygons_workspace_bytes(int64_t V, int B) { return ffp_layout(V, B).bytes; }
+extern "C" int64_t p3_ffl_polygons_workspace_bytes(int64_t V, int B) {
+    P3Carve c = {nullptr, 0};
+    ffp_carve(V, B, c);
+    return c.at;
+}
 
 // the array can be read by the host (no device allocation, or no device at all): its values are checked here and the call is refused either way
 static bool ffp_host_array(const void* p) {
@@ -698,33 +694,23 @@ extern "C" int p3_ffl_polygons(const float* out_pos, int64_t V, const int64_t* p
              P3_EINVAL, "p3_ffl_polygons: null output with a capacity above 0");
     P3_CHECK(workspace, P3_EINVAL, "p3_ffl_polygons: null workspace (p3_ffl_polygons_workspace_bytes(V, B))");
     hipStream_t s = (hipStream_t)stream;
-    const FfpLayout l = ffp_layout(V, B);
-    char* ws = (char*)workspace;
+    P3Carve carve = {(char*)workspace, 0};
+    const FfpWs l = ffp_carve(V, B, carve);
     FfpIn in = {(const float2*)out_pos, piece_slice, piece_batch, V, Q, B, H, W, min_area};
-    int32_t* slots = (int32_t*)(ws + l.o_slots);
-    int32_t* flag = (int32_t*)(ws + l.o_flag);
-    int64_t* soff = (int64_t*)(ws + l.o_soff);
-    int64_t* ioff = (int64_t*)(ws + l.o_ioff);
-    FfpImages im = {slots, soff, l.S, (int32_t*)(ws + l.o_pcount), image_status};
-    FfpStage st = {(float2*)(ws + l.o_pos), (int2*)(ws + l.o_ipos), (int2*)(ws + l.o_ring), (int2*)(ws + l.o_poly), (float*)(ws + l.o_area), (int32_t*)(ws + l.o_aflag),
-                   (int4*)(ws + l.o_rbox)};
-    FfpGlobal g = {(double*)(ws + l.o_rS), (FfpPt*)(ws + l.o_node), (int32_t*)(ws + l.o_eu), (int32_t*)(ws + l.o_ev), (uint8_t*)(ws + l.o_elive),
-                   (uint8_t*)(ws + l.o_fl), (int32_t*)(ws + l.o_ints), l.I};
-    if (hipMemsetAsync(ws + l.o_flag, 0, (size_t)(l.o_soff - l.o_flag), s) != hipSuccess)          // flag and pcount
-        P3_CHECK(false, P3_EINVAL, "p3_ffl_polygons: hipMemsetAsync failed");
+    FfpImages im = {l.slots, l.soff, l.S, l.pcount, image_status};
+    P3_TRY(p3_memset(l.flag, 0, (char*)l.soff - (char*)l.flag, s));
     const int all_global = force_fallback ? 1 : 0;
-    ffp_count_kernel<<<B, FFP_THREADS, 0, s>>>(in, slots, flag);
-    ffp_offsets_kernel<<<1, FFP_SCAN_THREADS, 0, s>>>(B, slots, soff);
-    ffp_lds_kernel<<<B, FFP_THREADS, 0, s>>>(in, im, st, all_global);
-    ffp_global_kernel<<<B, FFP_THREADS, 0, s>>>(in, im, st, g, all_global);
-    P3_LAUNCH_CHECK();
-    ffp_scan_kernel<<<1, FFP_SCAN_THREADS, 0, s>>>(B, im.pcount, ioff, max_polygons, max_rings, max_vertices, flag, counts, status);
-    ffp_emit_kernel<<<B, FFP_THREADS, 0, s>>>(B, im, st, ioff, max_polygons, max_rings, max_vertices, (float2*)ring_pos, ring_slice, poly_rings, poly_batch, poly_area);
+    P3_TRY(p3_launch<ffp_count_kernel>(nullptr, B, FFP_THREADS, 0, s, in, l.slots, l.flag));
+    P3_TRY(p3_launch<ffp_offsets_kernel>(nullptr, 1, FFP_SCAN_THREADS, 0, s, B, l.slots, l.soff));
+    P3_TRY(p3_launch<ffp_lds_kernel>(force_fallback ? nullptr : "ffp_lds_kernel", B, FFP_THREADS, 0, s, in, im, l.st, all_global));
+    P3_TRY(p3_launch<ffp_global_kernel>(force_fallback ? "ffp_global_kernel" : nullptr, B, FFP_THREADS, 0, s, in, im, l.st, l.g, all_global));
+    P3_TRY(p3_launch<ffp_scan_kernel>(nullptr, 1, FFP_SCAN_THREADS, 0, s, B, l.pcount, l.ioff, max_polygons, max_rings, max_vertices, l.flag, counts, status));
+    P3_TRY(p3_launch<ffp_emit_kernel>(nullptr, B, FFP_THREADS, 0, s, B, im, l.st, l.ioff, max_polygons, max_rings, max_vertices, (float2*)ring_pos, ring_slice, poly_rings,
+                                      poly_batch, poly_area));
     if (max_polygons > 0) {
         const int grid = max_polygons < 4096 ? max_polygons : 4096;
-        ffp_prob_kernel<<<grid, FFP_PROB_THREADS, 0, s>>>(B, H, W, indicator, im, st, ioff, max_polygons, seg_threshold, poly_prob, poly_flags);
+        P3_TRY(p3_launch<ffp_prob_kernel>(nullptr, grid, FFP_PROB_THREADS, 0, s, B, H, W, indicator, im, l.st, l.ioff, max_polygons, seg_threshold, poly_prob,
+                                          poly_flags));
     }
-    P3_LAUNCH_CHECK();
-    if (p3_tracing()) p3_note_kernel(force_fallback ? "ffp_global_kernel" : "ffp_lds_kernel");
     return P3_OK;
 }

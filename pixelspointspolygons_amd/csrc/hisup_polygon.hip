@@ -210,8 +210,7 @@ __device__ int hp_polygon(const HpArgs& a, HpShared& sh, const uint32_t* ring, i
     for (int v0 = 0; v0 < k; v0 += HP_NT) {
         const int v = v0 + tid;
         const int f = v < k && seq.keep(v, k) ? 1 : 0;
-        int tot;
-        const int at = running + wg_scan<false>(f, sh.red, tot) - f;
+        const int at = wg_excl(f, sh.red, running);
         if (f && base >= 0) {
             float x, y;
             int src;
@@ -221,7 +220,6 @@ __device__ int hp_polygon(const HpArgs& a, HpShared& sh, const uint32_t* ring, i
             if (at == 0) { stg.pos[(int64_t)(base + kept) * 2] = x; stg.pos[(int64_t)(base + kept) * 2 + 1] = y; stg.src[base + kept] = src;
             }
         }
-        running += tot;
     }
     return nv;
 }
@@ -345,7 +343,7 @@ __device__ void hp_holes(const HpArgs& a, HpShared& sh, uint8_t* st, uint8_t* T,
                 return true;
             });
             if (area < 0) area = -area;
-            sh.a2 = (int)(area < 0x7fffffffLL ? area : 0x7fffffffLL);
+            sh.a2 = p3_sat31(area);
             sh.ymin = ymin; sh.ymax = ymax; sh.xmin = xmin; sh.xmax = xmax; sh.m = cnt;
         }
         __syncthreads();
@@ -510,19 +508,16 @@ __global__ __launch_bounds__(1024) void hp_offsets_kernel(const int32_t* __restr
     for (int64_t i0 = 0; i0 < R; i0 += 1024) {
         const int64_t i = i0 + tid;
         const int v = i < R ? nv[i] : 0;
-        long long tot;
-        const long long incl = wg_scan<false>((long long)v, red, tot);
-        if (i < R) { poly_slice[i * 2] = running + incl - v; poly_slice[i * 2 + 1] = running + incl; }
-        running += tot;
+        const long long lo = wg_excl((long long)v, red, running);
+        if (i < R) { poly_slice[i * 2] = lo; poly_slice[i * 2 + 1] = lo + v; }
         longest = max(longest, v);
     }
-    int lm;
-    wg_scan<true>(longest, redm, lm);
+    const int lm = wg_max(longest, redm);
     __syncthreads();
     for (int b = tid; b < B; b += 1024)
         n_vertices[b] = (int32_t)(poly_slice[((int64_t)b * max_regions + max_regions - 1) * 2 + 1] - poly_slice[(int64_t)b * max_regions * 2]);
     if (tid == 0) {
-        counts[0] = (int32_t)(running < 0x7fffffffLL ? running : 0x7fffffffLL);
+        counts[0] = p3_sat31(running);
         counts[1] = lm;
         if (running > max_vertices) atomicOr(status, 1);
         if (stop != 0) atomicOr(status, 4);                  // a run cut short for a measurement never passes for a result
@@ -544,24 +539,17 @@ __global__ __launch_bounds__(1024) void hp_ring_offsets_kernel(const int32_t* __
     for (int64_t i0 = 0; i0 < R; i0 += 1024) {
         const int64_t i = i0 + tid;
         const int v = i < R ? r_n[i] : 0;
-        long long tot, vt;
-        const long long incl = wg_scan<false>((long long)v, red, tot);
-        if (i < R) {
-            const long long lo = rings + incl - v, hi = rings + incl;
-            region_rings[i * 2] = (int32_t)(lo < 0x7fffffffLL ? lo : 0x7fffffffLL); region_rings[i * 2 + 1] = (int32_t)(hi < 0x7fffffffLL ? hi : 0x7fffffffLL);
-        }
-        rings += tot;
+        const long long lo = wg_excl((long long)v, red, rings);
+        if (i < R) { region_rings[i * 2] = p3_sat31(lo); region_rings[i * 2 + 1] = p3_sat31(lo + v); }
         __syncthreads();
-        wg_scan<false>((long long)(i < R ? r_nv[i] : 0), red, vt);
-        verts += vt;
+        wg_excl((long long)(i < R ? r_nv[i] : 0), red, verts);          // the total alone
         longest = max(longest, i < R ? r_long[i] : 0);
         __syncthreads();
     }
-    int lm;
-    wg_scan<true>(longest, redm, lm);
+    const int lm = wg_max(longest, redm);
     if (tid == 0) {
-        ring_counts[0] = (int32_t)(rings < 0x7fffffffLL ? rings : 0x7fffffffLL);
-        ring_counts[1] = (int32_t)(verts < 0x7fffffffLL ? verts : 0x7fffffffLL);
+        ring_counts[0] = p3_sat31(rings);
+        ring_counts[1] = p3_sat31(verts);
         ring_counts[2] = lm;
         if (rings > max_rings) atomicOr(status, 8);
         if (verts > max_ring_vertices) atomicOr(status, 16);
@@ -580,10 +568,8 @@ __global__ __launch_bounds__(1024) void hp_ring_offsets_kernel(const int32_t* __
     for (int i0 = 0; i0 < Q; i0 += 1024) {
         const int i = i0 + tid;
         const int v = i < Q ? fin_nv[i] : 0;
-        long long tot;
-        const long long incl = wg_scan<false>((long long)v, red, tot);
-        if (i < Q) { ring_slice[(int64_t)i * 2] = running + incl - v; ring_slice[(int64_t)i * 2 + 1] = running + incl; }
-        running += tot;
+        const long long lo = wg_excl((long long)v, red, running);
+        if (i < Q) { ring_slice[(int64_t)i * 2] = lo; ring_slice[(int64_t)i * 2 + 1] = lo + v; }
         __syncthreads();
     }
 }
@@ -605,32 +591,37 @@ __global__ __launch_bounds__(HP_NT) void hp_pack_kernel(const int32_t* __restric
     }
 }
 
-struct HpLayout {
-    int64_t nv, stage_base, defer, stage_pos, stage_src, slabs, total, slab_bytes, map_bytes;
-    int64_t r_n, r_nv, r_long, r_done, r_rec, fin_nv, fin_base, r_stage_pos, r_stage_src;                 // with rings only
+struct HpWs {
+    unsigned long long* counters;                        // 256 bytes: staging entries handed out - vertices [0], ring vertices [1] - and ring records (a uint at byte 16)
+    int32_t *nv, *stage_base, *defer;
+    float* stage_pos; int32_t* stage_src;
+    int32_t *r_n, *r_nv, *r_long, *r_done, *r_rec, *fin_nv, *fin_base;                 // with rings only
+    float* r_stage_pos; int32_t* r_stage_src;
+    uint8_t* slabs;
+    int64_t slab_bytes, map_bytes;
     int n_slabs, ring_cap;
 };
 
-// max_rings == 0: the layout of p3_hisup_polygons
-HpLayout hp_layout(int B, int H, int W, int max_regions, int max_vertices, int max_rings, int max_ring_vertices) {
-    HpLayout L = {};
+// max_rings == 0: the workspace of p3_hisup_polygons
+HpWs hp_carve(int B, int H, int W, int max_regions, int max_vertices, int max_rings, int max_ring_vertices, P3Carve& c) {
+    HpWs L = {};
     const int64_t R = (int64_t)B * max_regions;
-    int64_t o = 256;                                     // the staging counters: vertices at 0, ring vertices at 8, ring records at 16
-    L.nv = o; o += p3_up256(R * 4);
-    L.stage_base = o; o += p3_up256(R * 4);
-    L.defer = o; o += p3_up256(R * 4);
-    L.stage_pos = o; o += p3_up256((int64_t)max_vertices * 8);
-    L.stage_src = o; o += p3_up256((int64_t)max_vertices * 4);
+    L.counters = (unsigned long long*)c.take_bytes(256);
+    L.nv = c.take<int32_t>(R);
+    L.stage_base = c.take<int32_t>(R);
+    L.defer = c.take<int32_t>(R);
+    L.stage_pos = c.take<float>(2 * (int64_t)max_vertices);
+    L.stage_src = c.take<int32_t>(max_vertices);
     if (max_rings > 0) {
-        L.r_n = o; o += p3_up256(R * 4);
-        L.r_nv = o; o += p3_up256(R * 4);
-        L.r_long = o; o += p3_up256(R * 4);
-        L.r_done = o; o += p3_up256(R * 4);
-        L.r_rec = o; o += p3_up256((int64_t)max_rings * HP_REC * 4);
-        L.fin_nv = o; o += p3_up256((int64_t)max_rings * 4);
-        L.fin_base = o; o += p3_up256((int64_t)max_rings * 4);
-        L.r_stage_pos = o; o += p3_up256((int64_t)max_ring_vertices * 8);
-        L.r_stage_src = o; o += p3_up256((int64_t)max_ring_vertices * 4);
+        L.r_n = c.take<int32_t>(R);
+        L.r_nv = c.take<int32_t>(R);
+        L.r_long = c.take<int32_t>(R);
+        L.r_done = c.take<int32_t>(R);
+        L.r_rec = c.take<int32_t>((int64_t)max_rings * HP_REC);
+        L.fin_nv = c.take<int32_t>(max_rings);
+        L.fin_base = c.take<int32_t>(max_rings);
+        L.r_stage_pos = c.take<float>(2 * (int64_t)max_ring_vertices);
+        L.r_stage_src = c.take<int32_t>(max_ring_vertices);
     }
     L.map_bytes = p3_up256((int64_t)(H + 3) * (W + 3));
     L.ring_cap = (int)(2 * ((int64_t)H * (W + 1) + (int64_t)W * (H + 1)) + 8);        // the ring bound of the header; an inner ring stays below it
@@ -639,9 +630,13 @@ HpLayout hp_layout(int B, int H, int W, int max_regions, int max_vertices, int m
     L.n_slabs = (int)(R < HP_SLABS ? R : HP_SLABS);
     if (L.n_slabs > fit) L.n_slabs = fit < 1 ? 1 : (int)fit;
     if (L.n_slabs < 1) L.n_slabs = 1;
-    L.slabs = o; o += L.n_slabs * L.slab_bytes;
-    L.total = o;
+    L.slabs = (uint8_t*)c.take_bytes(L.n_slabs * L.slab_bytes);
     return L;
+}
+int64_t hp_bytes(int B, int H, int W, int max_regions, int max_vertices, int max_rings, int max_ring_vertices) {
+    P3Carve c = {nullptr, 0};
+    hp_carve(B, H, W, max_regions, max_vertices, max_rings, max_ring_vertices, c);
+    return c.at;
 }
 
 struct HpRingOut {
@@ -655,54 +650,45 @@ int hp_run(const int32_t* labels, const int32_t* n_regions, const int32_t* bbox,
            int max_regions, int max_vertices, int max_rings, int max_ring_vertices, int force_fallback, float* pos, int32_t* src, int64_t* poly_slice,
            int32_t* poly_flags, int32_t* hole_pixels, int32_t* n_vertices, int32_t* counts, int32_t* status, const HpRingOut* ro, void* workspace, void* stream) {
     hipStream_t s = (hipStream_t)stream;
-    const HpLayout L = hp_layout(B, H, W, max_regions, max_vertices, max_rings, max_ring_vertices);
-    uint8_t* ws = (uint8_t*)workspace;
-    hipError_t e = hipMemsetAsync(ws, 0, 256, s);
-    if (e == hipSuccess) e = hipMemsetAsync(status, 0, 4, s);
-    if (e != hipSuccess) { p3_set_error(hipGetErrorString(e)); return (int)e; }
+    P3Carve carve = {(char*)workspace, 0};
+    const HpWs L = hp_carve(B, H, W, max_regions, max_vertices, max_rings, max_ring_vertices, carve);
+    P3_TRY(p3_memset(L.counters, 0, 256, s));
+    P3_TRY(p3_memset(status, 0, 4, s));
     HpArgs a = {};
     a.labels = labels; a.n_regions = n_regions; a.bbox = bbox; a.juncs = juncs; a.junc_counts = junc_counts;
     a.B = B; a.H = H; a.W = W; a.max_regions = max_regions; a.max_vertices = max_vertices;
     const char* stop = getenv("P3_HISUP_POLY_STOP");            // tools/bench_hisup_polygons.py: the share of the single-lane walk
     a.stop = stop && (stop[0] == '1' || stop[0] == '2') && stop[1] == 0 ? stop[0] - '0' : 0;          // "1" and "2" only: anything else is a full run
-    a.nv = (int32_t*)(ws + L.nv); a.stage_base = (int32_t*)(ws + L.stage_base); a.defer = (int32_t*)(ws + L.defer);
-    a.alloc = (unsigned long long*)ws;
-    a.stage_pos = (float*)(ws + L.stage_pos); a.stage_src = (int32_t*)(ws + L.stage_src);
+    a.nv = L.nv; a.stage_base = L.stage_base; a.defer = L.defer;
+    a.alloc = L.counters;
+    a.stage_pos = L.stage_pos; a.stage_src = L.stage_src;
     a.poly_flags = poly_flags; a.hole_pixels = hole_pixels; a.status = status;
     if (kRings) {
         a.max_rings = max_rings; a.max_ring_vertices = max_ring_vertices; a.n_holes = ro->n_holes;
-        a.r_n = (int32_t*)(ws + L.r_n); a.r_nv = (int32_t*)(ws + L.r_nv); a.r_long = (int32_t*)(ws + L.r_long); a.r_done = (int32_t*)(ws + L.r_done);
-        a.r_alloc = (unsigned long long*)(ws + 8); a.r_slots = (unsigned int*)(ws + 16);
-        a.r_rec = (int32_t*)(ws + L.r_rec); a.r_stage_pos = (float*)(ws + L.r_stage_pos); a.r_stage_src = (int32_t*)(ws + L.r_stage_src);
+        a.r_n = L.r_n; a.r_nv = L.r_nv; a.r_long = L.r_long; a.r_done = L.r_done;
+        a.r_alloc = L.counters + 1; a.r_slots = (unsigned int*)(L.counters + 2);
+        a.r_rec = L.r_rec; a.r_stage_pos = L.r_stage_pos; a.r_stage_src = L.r_stage_src;
     }
     const int64_t R = (int64_t)B * max_regions;
-    int rc = p3_launch<hp_lds_kernel<kRings>>(kRings ? "hisup_polygons_rings_lds" : "hisup_polygons_lds", dim3((unsigned)R), dim3(HP_NT), 0, s, a, force_fallback);
-    if (rc != P3_OK) return rc;
-    rc = p3_launch<hp_ws_kernel<kRings>>(kRings ? "hisup_polygons_rings_ws" : "hisup_polygons_ws", dim3(L.n_slabs), dim3(HP_NT), 0, s, a, ws + L.slabs, L.slab_bytes,
-                                         L.map_bytes, L.ring_cap);
-    if (rc != P3_OK) return rc;
-    rc = p3_launch<hp_offsets_kernel>(nullptr, dim3(1), dim3(1024), 0, s, (const int32_t*)a.nv, B, max_regions, max_vertices, a.stop, poly_slice, n_vertices, counts, status);
-    if (rc != P3_OK) return rc;
-    rc = p3_launch<hp_pack_kernel>(nullptr, dim3(p3_ceil_div(R, HP_NT / 64)), dim3(HP_NT), 0, s, (const int32_t*)a.nv, (const int32_t*)a.stage_base,
-                                   (const int64_t*)poly_slice, (const float*)a.stage_pos, (const int32_t*)a.stage_src, (const int32_t*)status, 1,
-                                   (const int32_t*)nullptr, R, max_vertices, pos, src);
-    if (rc != P3_OK || !kRings) return rc;
-    int32_t* fin_nv = (int32_t*)(ws + L.fin_nv);
-    int32_t* fin_base = (int32_t*)(ws + L.fin_base);
-    rc = p3_launch<hp_ring_offsets_kernel>(nullptr, dim3(1), dim3(1024), 0, s, (const int32_t*)a.r_n, (const int32_t*)a.r_nv, (const int32_t*)a.r_long,
-                                           (const int32_t*)a.r_rec, R, max_rings, max_ring_vertices, ro->region_rings, ro->ring_slice, ro->ring_region,
-                                           ro->ring_flags, ro->ring_area2, fin_nv, fin_base, ro->ring_counts, status);
-    if (rc != P3_OK) return rc;
-    return p3_launch<hp_pack_kernel>(nullptr, dim3(p3_ceil_div(max_rings, HP_NT / 64)), dim3(HP_NT), 0, s, (const int32_t*)fin_nv, (const int32_t*)fin_base,
-                                     (const int64_t*)ro->ring_slice, (const float*)a.r_stage_pos, (const int32_t*)a.r_stage_src, (const int32_t*)status, 8 | 16,
-                                     (const int32_t*)ro->ring_counts, (int64_t)max_rings, max_ring_vertices, ro->ring_pos, ro->ring_src);
+    P3_TRY(p3_launch<hp_lds_kernel<kRings>>(kRings ? "hisup_polygons_rings_lds" : "hisup_polygons_lds", (unsigned)R, HP_NT, 0, s, a, force_fallback));
+    P3_TRY(p3_launch<hp_ws_kernel<kRings>>(kRings ? "hisup_polygons_rings_ws" : "hisup_polygons_ws", L.n_slabs, HP_NT, 0, s, a, L.slabs, L.slab_bytes, L.map_bytes,
+                                           L.ring_cap));
+    P3_TRY(p3_launch<hp_offsets_kernel>(nullptr, 1, 1024, 0, s, a.nv, B, max_regions, max_vertices, a.stop, poly_slice, n_vertices, counts, status));
+    const int32_t* every = nullptr;
+    P3_TRY(p3_launch<hp_pack_kernel>(nullptr, p3_ceil_div(R, HP_NT / 64), HP_NT, 0, s, a.nv, a.stage_base, poly_slice, a.stage_pos, a.stage_src, status, 1, every, R,
+                                     max_vertices, pos, src));
+    if (!kRings) return P3_OK;
+    P3_TRY(p3_launch<hp_ring_offsets_kernel>(nullptr, 1, 1024, 0, s, a.r_n, a.r_nv, a.r_long, a.r_rec, R, max_rings, max_ring_vertices, ro->region_rings, ro->ring_slice,
+                                             ro->ring_region, ro->ring_flags, ro->ring_area2, L.fin_nv, L.fin_base, ro->ring_counts, status));
+    return p3_launch<hp_pack_kernel>(nullptr, p3_ceil_div(max_rings, HP_NT / 64), HP_NT, 0, s, L.fin_nv, L.fin_base, ro->ring_slice, a.r_stage_pos, a.r_stage_src, status,
+                                     8 | 16, ro->ring_counts, (int64_t)max_rings, max_ring_vertices, ro->ring_pos, ro->ring_src);
 }
 
 }  // namespace
 
 extern "C" int64_t p3_hisup_polygons_workspace_bytes(int B, int H, int W, int max_regions, int max_vertices) {
     if (B <= 0 || H <= 0 || W <= 0 || max_regions <= 0 || max_vertices <= 0) return 0;
-    return hp_layout(B, H, W, max_regions, max_vertices, 0, 0).total;
+    return hp_bytes(B, H, W, max_regions, max_vertices, 0, 0);
 }
 
 extern "C" int p3_hisup_polygons(const int32_t* labels, const int32_t* n_regions, const int32_t* bbox, const float* juncs, const int32_t* junc_counts, int B,
@@ -721,7 +707,7 @@ extern "C" int p3_hisup_polygons(const int32_t* labels, const int32_t* n_regions
 
 extern "C" int64_t p3_hisup_polygons_rings_workspace_bytes(int B, int H, int W, int max_regions, int max_vertices, int max_rings, int max_ring_vertices) {
     if (B <= 0 || H <= 0 || W <= 0 || max_regions <= 0 || max_vertices <= 0 || max_rings <= 0 || max_ring_vertices <= 0) return 0;
-    return hp_layout(B, H, W, max_regions, max_vertices, max_rings, max_ring_vertices).total;
+    return hp_bytes(B, H, W, max_regions, max_vertices, max_rings, max_ring_vertices);
 }
 
 extern "C" int p3_hisup_polygons_rings(const int32_t* labels, const int32_t* n_regions, const int32_t* bbox, const float* juncs, const int32_t* junc_counts,

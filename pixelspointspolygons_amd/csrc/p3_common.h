@@ -87,6 +87,26 @@ __device__ __forceinline__ T wg_scan(T v, T* red, T& total) {
     if (w == 0) return v;
     return MAX ? (base > v ? base : v) : base + v;
 }
+// one chunk of an exclusive sum that takes the workgroup several passes: the sum of everything in front of v (`carry`: the chunks before), then carry takes the chunk in
+template <typename T>
+__device__ __forceinline__ T wg_excl(T v, T* red, T& carry) {
+    T total;
+    const T ex = carry + wg_scan<false, T>(v, red, total) - v;
+    carry += total;
+    return ex;
+}
+// the maximum over the workgroup, in every thread
+template <typename T>
+__device__ __forceinline__ T wg_max(T v, T* red) {
+    T total;
+    wg_scan<true, T>(v, red, total);
+    return total;
+}
+// two 32-bit counts that one 64-bit scan sums together (or a sort key and its payload), and a 64-bit total clamped into an int32 output
+__device__ __forceinline__ unsigned long long p3_pack2(uint32_t hi, uint32_t lo) { return ((unsigned long long)hi << 32) | lo; }
+__device__ __forceinline__ int p3_hi32(unsigned long long k) { return (int)(k >> 32); }
+__device__ __forceinline__ int p3_lo32(unsigned long long k) { return (int)(k & 0xffffffffull); }
+__device__ __forceinline__ int32_t p3_sat31(int64_t x) { return (int32_t)(x < 0x7fffffff ? x : 0x7fffffff); }
 
 // ---- counter-based dropout (p3_dropout) ---------------------------------------------------------------------------------
 // Element (row, col) of a site: bits = hash32(rowkey(row) ^ colkey(col >> 1)), 16 bits per element (low half: even col, high half:
@@ -173,6 +193,18 @@ __device__ __forceinline__ void p3_commit(float* out, float* slab, int n, int id
 
 static inline int p3_ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 static inline int64_t p3_up256(int64_t v) { return (v + 255) & ~(int64_t)255; }          // workspace sections start on 256-byte boundaries
+// A workspace cut into sections, in the order they are taken: take<T>(n) is the next section, n elements of T.  base == NULL measures - every section is NULL and
+// `at` ends at the bytes the workspace needs - so one function over a P3Carve states each section's type and size once, for the size query and for the entry point.
+struct P3Carve {
+    char* base;
+    int64_t at;
+    void* take_bytes(int64_t bytes) {
+        char* p = base ? base + at : nullptr;
+        at += p3_up256(bytes);
+        return p;
+    }
+    template <class T> T* take(int64_t n) { return (T*)take_bytes(n * (int64_t)sizeof(T)); }
+};
 
 void p3_set_error(const char* msg);
 int p3_tracing(void);                     // p3_trace_kernels(1): launch sites record the kernel they picked (p3_last_kernel)
@@ -199,6 +231,18 @@ int p3_det_reduce2(const float* parts, int nparts, int64_t stride, float* tmp, f
             p3_set_error(hipGetErrorString(e_));       \
             return (int)e_;                            \
         }                                              \
+    } while (0)
+// the status of a HIP runtime call (a memset, a copy) as an entry point returns it: P3_OK, or the hipError_t with its message in p3_set_error
+static inline int p3_hip_status(hipError_t e) {
+    if (e != hipSuccess) p3_set_error(hipGetErrorString(e));
+    return (int)e;
+}
+static inline int p3_memset(void* p, int byte, int64_t bytes, hipStream_t s) { return p3_hip_status(hipMemsetAsync(p, byte, (size_t)bytes, s)); }
+// a step that returns such a status - p3_launch, p3_memset: the first one that fails ends the entry point with its code
+#define P3_TRY(status)                     \
+    do {                                   \
+        const int rc_ = (status);          \
+        if (rc_ != P3_OK) return rc_;      \
     } while (0)
 
 // ---- dtype code -> template argument ---------------------------------------------------------------------------------------------------------------

@@ -1221,8 +1221,6 @@ __global__ void pfn_bwd_l1_finalize_kernel(const float* __restrict__ acc, const 
     if (k == 0) { dg1[c] = acc[ACC_DG + c]; db1[c] = acc[ACC_DB + c]; }
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct Ws {
     int* sorted; int* vox_xy; int* vox_start; int* vox_cnt; int* vox_row; int* nvox; int* totals;
     float* sums1; float* sums2; float* sc1; float* sh1; float* sc2; float* sh2; float* hmax; float* hmin;
@@ -1234,29 +1232,28 @@ struct Ws {
 };
 
 Ws carve(void* base, const p3_pillar_desc* d) {
-    Ws w; char* p = (char*)base; size_t off = 0;
-    const size_t nv = (size_t)d->B * d->max_voxels;
-    const size_t rows = (size_t)d->total_points + nv;
-    const size_t es = d->dtype == P3_BF16 ? 2 : 4;
-    auto take = [&](size_t bytes) { void* r = p ? p + off : nullptr; off += align256(bytes); return r; };
-    w.totals = (int*)take(256);
-    w.sums1 = (float*)take(2 * C1 * 4);
-    w.sums2 = (float*)take(2 * (size_t)d->C * 4);
+    Ws w; P3Carve c = {(char*)base, 0};
+    const int64_t nv = (int64_t)d->B * d->max_voxels;
+    const int64_t rows = (int64_t)d->total_points + nv;
+    const int64_t es = d->dtype == P3_BF16 ? 2 : 4;
+    w.totals = (int*)c.take_bytes(256);
+    w.sums1 = c.take<float>(2 * C1);
+    w.sums2 = c.take<float>(2 * (int64_t)d->C);
     // [totals, sc1) is cleared every call
-    w.sc1 = (float*)take(C1 * 4); w.sh1 = (float*)take(C1 * 4);
-    w.sc2 = (float*)take((size_t)d->C * 4); w.sh2 = (float*)take((size_t)d->C * 4);
-    w.m1 = (float*)take(C1 * 4); w.r1 = (float*)take(C1 * 4);
-    w.m2 = (float*)take((size_t)d->C * 4); w.r2 = (float*)take((size_t)d->C * 4);
-    w.acc1 = (float*)take(ACC1_FLOATS * 4);
-    w.sorted = (int*)take((size_t)(d->total_points > 0 ? d->total_points : 1) * 4);
-    w.vox_xy = (int*)take(nv * 4); w.vox_start = (int*)take(nv * 4); w.vox_cnt = (int*)take(nv * 4); w.vox_row = (int*)take(nv * 4);
-    w.nvox = (int*)take((size_t)d->B * 4);
-    w.hmax = (float*)take(nv * d->C * 4); w.hmin = (float*)take(nv * d->C * 4);
-    w.F8 = (float*)take(rows * 8 * 4); w.row_w = (float*)take(rows * 4); w.row_vox = (int*)take(rows * 4);
-    w.X2 = take(rows * K2 * es);
-    w.H2 = take(rows * (size_t)d->C * es);
-    w.sort_tmp = (unsigned*)take((size_t)d->B * (SORT_SPLIT + 1) * (size_t)(d->nx + 1) * (d->ny + 1) * 2 * 4);   // the split sort's chunk histograms + cell starts
-    w.bytes = off;
+    w.sc1 = c.take<float>(C1); w.sh1 = c.take<float>(C1);
+    w.sc2 = c.take<float>(d->C); w.sh2 = c.take<float>(d->C);
+    w.m1 = c.take<float>(C1); w.r1 = c.take<float>(C1);
+    w.m2 = c.take<float>(d->C); w.r2 = c.take<float>(d->C);
+    w.acc1 = c.take<float>(ACC1_FLOATS);
+    w.sorted = c.take<int>(d->total_points > 0 ? d->total_points : 1);
+    w.vox_xy = c.take<int>(nv); w.vox_start = c.take<int>(nv); w.vox_cnt = c.take<int>(nv); w.vox_row = c.take<int>(nv);
+    w.nvox = c.take<int>(d->B);
+    w.hmax = c.take<float>(nv * d->C); w.hmin = c.take<float>(nv * d->C);
+    w.F8 = c.take<float>(rows * 8); w.row_w = c.take<float>(rows); w.row_vox = c.take<int>(rows);
+    w.X2 = c.take_bytes(rows * K2 * es);          // bf16 or fp32 by the stem's dtype
+    w.H2 = c.take_bytes(rows * d->C * es);
+    w.sort_tmp = c.take<unsigned>((int64_t)d->B * (SORT_SPLIT + 1) * (int64_t)(d->nx + 1) * (d->ny + 1) * 2);   // the split sort's chunk histograms + cell starts
+    w.bytes = (size_t)c.at;
     return w;
 }
 
@@ -1306,11 +1303,6 @@ int pfn_partials(bool want, int parts, int n, const Stem& c, float* out, float* 
 // f(std::true_type{}) or f(std::false_type{}): a runtime flag as a template argument
 template <typename F> int by_flag(bool v, F&& f) { return v ? f(std::true_type{}) : f(std::false_type{}); }
 
-int hip_status(hipError_t e) {
-    if (e != hipSuccess) p3_set_error(hipGetErrorString(e));
-    return (int)e;
-}
-
 }  // namespace
 
 // zero `per_row` 16-byte chunks at the start of every row (row pitch ldb bytes): the canvas columns the pillars scatter into
@@ -1346,7 +1338,7 @@ static int pfn_pillarize(const float* values, const int64_t* offsets, const floa
         if (e == hipSuccess) e = hipMemsetAsync(w.F8, 0, (char*)w.row_vox - (char*)w.F8, s);
     }
     if (e == hipSuccess) e = hipMemsetAsync(w.row_vox, 0xFF, c.rows * 4, s);   // -1 = unused row
-    if (e != hipSuccess) return hip_status(e);
+    if (e != hipSuccess) return p3_hip_status(e);
     // zero canvas columns [col_off, col_off + C) of every token row (empty pillars stay exactly 0)
     const size_t rowb = (size_t)d->C * c.es, ldb = (size_t)d->out_ld * c.es, offb = (size_t)d->out_col_off * c.es;
     const int64_t nrows = (int64_t)d->B * d->nx * d->ny;
@@ -1357,7 +1349,7 @@ static int pfn_pillarize(const float* values, const int64_t* offsets, const floa
         rc = p3_launch<zero_cols16_kernel>(nullptr, dim3((unsigned)((tot + 255) / 256 < 16384 ? (tot + 255) / 256 : 16384)), dim3(256), 0, s, (char*)out + offb,
                                            (int64_t)ldb, per_row, tot);
     } else {
-        rc = hip_status(hipMemset2DAsync((char*)out + offb, ldb, 0, rowb, (size_t)nrows, s));
+        rc = p3_hip_status(hipMemset2DAsync((char*)out + offb, ldb, 0, rowb, (size_t)nrows, s));
     }
     if (rc != P3_OK) return rc;
 
@@ -1506,7 +1498,7 @@ extern "C" int p3_pillar_stem_bwd_phased(const void* dcanvas, int dcanvas_ld, co
             if (e == hipSuccess) e = hipMemsetAsync(dg2, 0, (size_t)C * 4, s);
             if (e == hipSuccess) e = hipMemsetAsync(db2, 0, (size_t)C * 4, s);
             if (e == hipSuccess) e = hipMemsetAsync(dw2, 0, (size_t)C * K2 * 4, s);
-            if (e != hipSuccess) return hip_status(e);
+            if (e != hipSuccess) return p3_hip_status(e);
             const int g3 = vgrid < L2S_BLOCKS ? vgrid : L2S_BLOCKS, ncell = d->nx * d->ny;
             const T* dcv = (const T*)dcanvas + d->out_col_off;
             constexpr int per16 = 16 / (int)sizeof(T);       // the lane-owns-8 form reads the canvas gradient in 16-byte pieces

@@ -107,26 +107,20 @@ __global__ __launch_bounds__(SK_SCAN_THREADS) void sk_scan_kernel(SkIn in, const
         const int p = at + threadIdx.x;
         const int n = p < in.P ? klen[p] : 0;
         const int c = n > 0 ? kclosed[p] : 0;
-        const sk_u64 v = n > 0 ? (((sk_u64)n << 32) | 1ull) : 0ull;
-        sk_u64 total;
-        int total_closed;
-        const sk_u64 ex = carry + wg_scan<false, sk_u64>(v, lds64, total) - v;
-        const int exc = carry_closed + wg_scan<false, int>(c, lds32, total_closed) - c;
+        const sk_u64 ex = wg_excl(n > 0 ? p3_pack2(n, 1) : 0ull, lds64, carry);
+        const int exc = wg_excl(c, lds32, carry_closed);
         if (p < in.P) {
-            noff[p] = (int)(ex >> 32);
+            noff[p] = p3_hi32(ex);
             coff[p] = exc;
-            kidx[p] = (int)(ex & 0xffffffffull);
+            kidx[p] = p3_lo32(ex);
             // batch_delim[b] = kept paths of the images in front of b: every image between the previous contour's (exclusive) and this one's (inclusive)
             const int cur = sk_image(in, p), prev = p > 0 ? sk_image(in, p - 1) : -1;
-            for (int b = prev + 1; b <= cur; ++b) batch_delim[b] = (int64_t)(ex & 0xffffffffull);
+            for (int b = prev + 1; b <= cur; ++b) batch_delim[b] = p3_lo32(ex);
             longest = max(longest, n);
         }
-        carry += total;
-        carry_closed += total_closed;
     }
-    int longest_all;
-    wg_scan<true, int>(longest, lds32, longest_all);
-    const int nodes = (int)(carry >> 32), paths = (int)(carry & 0xffffffffull), slots = nodes + carry_closed;
+    const int longest_all = wg_max(longest, lds32);
+    const int nodes = p3_hi32(carry), paths = p3_lo32(carry), slots = nodes + carry_closed;
     const int last = in.P > 0 ? sk_image(in, in.P - 1) : -1;
     for (int b = last + 1 + threadIdx.x; b <= in.B; b += SK_SCAN_THREADS) batch_delim[b] = paths;
     if (threadIdx.x == 0) {
@@ -161,9 +155,23 @@ __global__ __launch_bounds__(SK_THREADS) void sk_emit_kernel(SkIn in, const int*
     }
 }
 
-static int64_t sk_ws_bytes(int P) { return 5 * p3_up256((int64_t)(P > 0 ? P : 0) * 4); }
+struct SkWs { int *klen, *kclosed, *noff, *coff, *kidx; };
+static SkWs sk_carve(int P, P3Carve& c) {
+    const int64_t n = P > 0 ? P : 0;
+    SkWs l;
+    l.klen = c.take<int>(n);
+    l.kclosed = c.take<int>(n);
+    l.noff = c.take<int>(n);
+    l.coff = c.take<int>(n);
+    l.kidx = c.take<int>(n);
+    return l;
+}
 
-extern "C" int64_t p3_skeleton_from_contours_workspace_bytes(int P) { return sk_ws_bytes(P); }
+extern "C" int64_t p3_skeleton_from_contours_workspace_bytes(int P) {
+    P3Carve c = {nullptr, 0};
+    sk_carve(P, c);
+    return c.at;
+}
 
 extern "C" int p3_skeleton_from_contours(const float* pos, int64_t N, const int64_t* poly_slice, const int32_t* poly_batch, const uint8_t* is_endpoint, int P, int B,
                                          int filter, double min_area, int max_nodes, int max_slots, int max_paths, float* out_pos, int64_t* degrees,
@@ -179,29 +187,24 @@ extern "C" int p3_skeleton_from_contours(const float* pos, int64_t N, const int6
     P3_CHECK(empty || ((max_nodes == 0 || (out_pos && degrees && batch)) && (max_slots == 0 || path_index)), P3_EINVAL,
              "p3_skeleton_from_contours: null output with a capacity above 0");
     hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(batch_delim, 0, ((int64_t)B + 1) * sizeof(int64_t), s) != hipSuccess) P3_CHECK(false, P3_EINVAL, "p3_skeleton_from_contours: hipMemsetAsync failed");
+    P3_TRY(p3_memset(batch_delim, 0, ((int64_t)B + 1) * sizeof(int64_t), s));
     if (empty) {
-        if (hipMemsetAsync(counts, 0, 4 * sizeof(int32_t), s) != hipSuccess || hipMemsetAsync(status, 0, sizeof(int32_t), s) != hipSuccess)
-            P3_CHECK(false, P3_EINVAL, "p3_skeleton_from_contours: hipMemsetAsync failed");
-        return P3_OK;
+        P3_TRY(p3_memset(counts, 0, 4 * sizeof(int32_t), s));
+        return p3_memset(status, 0, sizeof(int32_t), s);
     }
     SkIn in;
     in.pos = (const float2*)pos; in.slice = poly_slice; in.poly_batch = poly_batch; in.is_endpoint = is_endpoint;
     in.N = (int)N; in.P = P; in.B = B; in.filter = filter ? 1 : 0; in.min_area = min_area;
-    char* ws = (char*)workspace;
-    const int64_t sec = p3_up256((int64_t)P * 4);
-    int *klen = (int*)ws, *kclosed = (int*)(ws + sec), *noff = (int*)(ws + 2 * sec), *coff = (int*)(ws + 3 * sec), *kidx = (int*)(ws + 4 * sec);
-    sk_keep_kernel<<<P, SK_THREADS, 0, s>>>(in, klen, kclosed);
-    sk_scan_kernel<<<1, SK_SCAN_THREADS, 0, s>>>(in, klen, kclosed, noff, coff, kidx, max_nodes, max_slots, max_paths, path_delim, batch_delim, counts, status);
-    sk_emit_kernel<<<P, SK_THREADS, 0, s>>>(in, klen, kclosed, noff, coff, kidx, max_nodes, max_slots, max_paths, (float2*)out_pos, degrees, path_index, path_delim,
-                                            batch);
-    P3_LAUNCH_CHECK();
-    return P3_OK;
+    P3Carve carve = {(char*)workspace, 0};
+    const SkWs l = sk_carve(P, carve);
+    P3_TRY(p3_launch<sk_keep_kernel>(nullptr, P, SK_THREADS, 0, s, in, l.klen, l.kclosed));
+    P3_TRY(p3_launch<sk_scan_kernel>(nullptr, 1, SK_SCAN_THREADS, 0, s, in, l.klen, l.kclosed, l.noff, l.coff, l.kidx, max_nodes, max_slots, max_paths, path_delim,
+                                     batch_delim, counts, status));
+    return p3_launch<sk_emit_kernel>(nullptr, P, SK_THREADS, 0, s, in, l.klen, l.kclosed, l.noff, l.coff, l.kidx, max_nodes, max_slots, max_paths, (float2*)out_pos,
+                                     degrees, path_index, path_delim, batch);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the plan
-__device__ __forceinline__ int ap_hi(sk_u64 k) { return (int)(k >> 32); }
-__device__ __forceinline__ int ap_lo(sk_u64 k) { return (int)(k & 0xffffffffull); }
 __device__ __forceinline__ int ap_in(int i, int n) { return i < 0 ? 0 : (i >= n ? n - 1 : i); }          // whatever a key holds, an index stays inside its array
 __device__ __forceinline__ int ap_node(const int64_t* idx, int k, int N) {          // the node of slot k, clamped into [0, N)
     const int64_t v = idx[k];
@@ -218,7 +221,7 @@ __global__ __launch_bounds__(SK_THREADS) void ap_mark_kernel(const int64_t* idx,
         if (i < M) {
             const int64_t v = idx[i];
             if (v < 0 || v >= N) atomicOr(status, 2);
-            key[i] = ((sk_u64)(unsigned)ap_node(idx, (int)i, N) << 32) | (sk_u64)(unsigned)i;
+            key[i] = p3_pack2(ap_node(idx, (int)i, N), (uint32_t)i);
             if (i == 0) startf[0] = 1;
             if (i == M - 1) endf[M - 1] = 1;
         }
@@ -238,14 +241,12 @@ __global__ __launch_bounds__(SK_SCAN_THREADS) void ap_scan_kernel(const int* src
         int v[SK_SCAN_ITEMS], sum = 0;
 #pragma unroll
         for (int j = 0; j < SK_SCAN_ITEMS; ++j) { v[j] = first + j < n ? src[first + j] : 0; sum += v[j]; }
-        int total;
-        int ex = carry + wg_scan<false, int>(sum, lds, total) - sum;
+        int ex = wg_excl(sum, lds, carry);
 #pragma unroll
         for (int j = 0; j < SK_SCAN_ITEMS; ++j) {
             if (first + j < n) dst[first + j] = ex;
             ex += v[j];
         }
-        carry += total;
     }
     if (threadIdx.x == 0) dst[n] = carry;
 }
@@ -286,25 +287,27 @@ __global__ __launch_bounds__(SK_THREADS) void ap_merge_kernel(const sk_u64* src,
         dst[(rs < ps ? rs : ps) + (g - rs) + (lo - first)] = key;
     }
 }
-// sorts n keys; they start in a, b is as large; returns where they end up
-static const sk_u64* ap_sort(sk_u64* a, sk_u64* b, int n, hipStream_t s) {
-    if (n <= 0) return a;
-    ap_sort_tile_kernel<<<p3_ceil_div(n, SK_SORT_TILE), SK_SORT_TILE / 2, 0, s>>>(a, b, n);
+// sorts n keys; they start in a, b is as large; *sorted: where they end up
+static int ap_sort(sk_u64* a, sk_u64* b, int n, hipStream_t s, const sk_u64** sorted) {
+    *sorted = a;
+    if (n <= 0) return P3_OK;
+    P3_TRY(p3_launch<ap_sort_tile_kernel>(nullptr, p3_ceil_div(n, SK_SORT_TILE), SK_SORT_TILE / 2, 0, s, a, b, n));
     sk_u64 *src = b, *dst = a;
     const int grid = p3_ceil_div(n, SK_THREADS) < SK_MAX_GRID ? p3_ceil_div(n, SK_THREADS) : SK_MAX_GRID;
     for (int64_t run = SK_SORT_TILE; run < n; run <<= 1) {
-        ap_merge_kernel<<<grid, SK_THREADS, 0, s>>>(src, dst, n, run);
+        P3_TRY(p3_launch<ap_merge_kernel>(nullptr, grid, SK_THREADS, 0, s, src, dst, n, run));
         sk_u64* t = src; src = dst; dst = t;
     }
-    return src;
+    *sorted = src;
+    return P3_OK;
 }
 
 // 4: gstart (-1 before) / gend per node from run A
 __global__ __launch_bounds__(SK_THREADS) void ap_groups_kernel(const sk_u64* sa, int M, int N, int* gstart, int* gend) {
     for (int j = blockIdx.x * SK_THREADS + threadIdx.x; j < M; j += gridDim.x * SK_THREADS) {
-        const int v = ap_in(ap_hi(sa[j]), N);
-        if (j == 0 || ap_hi(sa[j - 1]) != v) gstart[v] = j;
-        if (j == M - 1 || ap_hi(sa[j + 1]) != v) gend[v] = j + 1;
+        const int v = ap_in(p3_hi32(sa[j]), N);
+        if (j == 0 || p3_hi32(sa[j - 1]) != v) gstart[v] = j;
+        if (j == M - 1 || p3_hi32(sa[j + 1]) != v) gend[v] = j + 1;
     }
 }
 
@@ -319,15 +322,13 @@ __global__ __launch_bounds__(SK_SCAN_THREADS) void ap_components_kernel(const sk
     for (int at = 0; at < M; at += SK_SCAN_THREADS) {
         const int j = at + threadIdx.x;
         int a = 0, b = 0, flag = 0;
-        if (j >= 1 && j < M && ap_hi(sa[j]) == ap_hi(sa[j - 1])) {
-            a = ap_in(ap_path(pid_ex, startf, ap_in(ap_lo(sa[j - 1]), M)), paths);
-            b = ap_in(ap_path(pid_ex, startf, ap_in(ap_lo(sa[j]), M)), paths);
+        if (j >= 1 && j < M && p3_hi32(sa[j]) == p3_hi32(sa[j - 1])) {
+            a = ap_in(ap_path(pid_ex, startf, ap_in(p3_lo32(sa[j - 1]), M)), paths);
+            b = ap_in(ap_path(pid_ex, startf, ap_in(p3_lo32(sa[j]), M)), paths);
             flag = a != b ? 1 : 0;
         }
-        int total;
-        const int ex = nlinks + wg_scan<false, int>(flag, lds, total) - flag;
+        const int ex = wg_excl(flag, lds, nlinks);
         if (flag) links[ex] = make_int2(a, b);
-        nlinks += total;
     }
     __syncthreads();
     for (;;) {
@@ -352,7 +353,7 @@ __global__ __launch_bounds__(SK_SCAN_THREADS) void ap_components_kernel(const sk
 __global__ __launch_bounds__(SK_THREADS) void ap_node_min_kernel(const sk_u64* sa, int N, int M, const int* gstart, const int* pid_ex, const int* startf, const int* plab, int* pmin) {
     for (int v = blockIdx.x * SK_THREADS + threadIdx.x; v < N; v += gridDim.x * SK_THREADS) {
         const int j = gstart[v];
-        if (j >= 0 && j < M) atomicMin(pmin + ap_in(plab[ap_in(ap_path(pid_ex, startf, ap_in(ap_lo(sa[j]), M)), M)], M), v);
+        if (j >= 0 && j < M) atomicMin(pmin + ap_in(plab[ap_in(ap_path(pid_ex, startf, ap_in(p3_lo32(sa[j]), M)), M)], M), v);
     }
 }
 // keys of sort B
@@ -360,17 +361,17 @@ __global__ __launch_bounds__(SK_THREADS) void ap_node_key_kernel(const sk_u64* s
                                                                  const int* pmin, sk_u64* key) {
     for (int v = blockIdx.x * SK_THREADS + threadIdx.x; v < N; v += gridDim.x * SK_THREADS) {
         const int j = gstart[v];
-        const int cmin = (j >= 0 && j < M) ? pmin[ap_in(plab[ap_in(ap_path(pid_ex, startf, ap_in(ap_lo(sa[j]), M)), M)], M)] : v;
-        key[v] = ((sk_u64)(unsigned)cmin << 32) | (sk_u64)(unsigned)v;
+        const int cmin = (j >= 0 && j < M) ? pmin[ap_in(plab[ap_in(ap_path(pid_ex, startf, ap_in(p3_lo32(sa[j]), M)), M)], M)] : v;
+        key[v] = p3_pack2(cmin, v);
     }
 }
 // 8a: cn_node, its inverse, the first-of-component flags and the occurrence counts in cn order
 __global__ __launch_bounds__(SK_THREADS) void ap_cn_kernel(const sk_u64* sb, int N, const int* gstart, const int* gend, int32_t* cn_node, int* cn_pos, int* first, int* occs) {
     for (int i = blockIdx.x * SK_THREADS + threadIdx.x; i < N; i += gridDim.x * SK_THREADS) {
-        const int v = ap_in(ap_lo(sb[i]), N);
+        const int v = ap_in(p3_lo32(sb[i]), N);
         cn_node[i] = v;
         cn_pos[v] = i;
-        first[i] = (i == 0 || ap_hi(sb[i - 1]) != ap_hi(sb[i])) ? 1 : 0;
+        first[i] = (i == 0 || p3_hi32(sb[i - 1]) != p3_hi32(sb[i])) ? 1 : 0;
         occs[i] = gstart[v] >= 0 ? gend[v] - gstart[v] : 0;
     }
 }
@@ -394,7 +395,7 @@ __global__ __launch_bounds__(SK_THREADS) void ap_node_local_kernel(int N, const 
 __global__ __launch_bounds__(SK_THREADS) void ap_slots_kernel(const sk_u64* sa, int M, int N, const int64_t* idx, const int* gstart, const int* cn_pos, const int32_t* cn_occ,
                                                               const int* startf, const int* endf, const int32_t* node_local, int32_t* slot_k, int32_t* slot_nb) {
     for (int j = blockIdx.x * SK_THREADS + threadIdx.x; j < M; j += gridDim.x * SK_THREADS) {
-        const int v = ap_in(ap_hi(sa[j]), N), k = ap_in(ap_lo(sa[j]), M);
+        const int v = ap_in(p3_hi32(sa[j]), N), k = ap_in(p3_lo32(sa[j]), M);
         const int64_t t = (int64_t)cn_occ[ap_in(cn_pos[v], N)] + (j - gstart[v]);
         if (t < 0 || t >= M) continue;          // cannot happen: the runs partition the slots
         slot_k[t] = k;
@@ -403,33 +404,42 @@ __global__ __launch_bounds__(SK_THREADS) void ap_slots_kernel(const sk_u64* sa, 
     }
 }
 
-struct ApLayout { int64_t o_startf, o_endf, o_pid, o_keya, o_keya2, o_gstart, o_gend, o_plab, o_pmin, o_links, o_keyb, o_keyb2, o_cn_pos, o_first, o_comp_ex, o_occs, bytes; };
-static ApLayout ap_layout(int64_t N, int64_t M) {
-    ApLayout l;
-    int64_t at = 0;
+struct ApWs {
+    int *startf, *endf, *pid_ex;
+    sk_u64 *keya, *keya2;
+    int *gstart, *gend, *plab, *pmin;
+    int2* links;
+    sk_u64 *keyb, *keyb2;
+    int *cn_pos, *first, *comp_ex, *occs;
+};
+static ApWs ap_carve(int64_t N, int64_t M, P3Carve& c) {
+    ApWs l;
     if (N < 0) N = 0;
     if (M < 0) M = 0;
-    l.o_startf = at; at += p3_up256(M * 4);
-    l.o_endf = at; at += p3_up256(M * 4);
-    l.o_pid = at; at += p3_up256((M + 1) * 4);
-    l.o_keya = at; at += p3_up256(M * 8);
-    l.o_keya2 = at; at += p3_up256(M * 8);
-    l.o_gstart = at; at += p3_up256(N * 4);
-    l.o_gend = at; at += p3_up256(N * 4);
-    l.o_plab = at; at += p3_up256(M * 4);
-    l.o_pmin = at; at += p3_up256(M * 4);
-    l.o_links = at; at += p3_up256(M * 8);
-    l.o_keyb = at; at += p3_up256(N * 8);
-    l.o_keyb2 = at; at += p3_up256(N * 8);
-    l.o_cn_pos = at; at += p3_up256(N * 4);
-    l.o_first = at; at += p3_up256(N * 4);
-    l.o_comp_ex = at; at += p3_up256((N + 1) * 4);
-    l.o_occs = at; at += p3_up256(N * 4);
-    l.bytes = at;
+    l.startf = c.take<int>(M);
+    l.endf = c.take<int>(M);
+    l.pid_ex = c.take<int>(M + 1);
+    l.keya = c.take<sk_u64>(M);
+    l.keya2 = c.take<sk_u64>(M);
+    l.gstart = c.take<int>(N);
+    l.gend = c.take<int>(N);
+    l.plab = c.take<int>(M);
+    l.pmin = c.take<int>(M);
+    l.links = c.take<int2>(M);
+    l.keyb = c.take<sk_u64>(N);
+    l.keyb2 = c.take<sk_u64>(N);
+    l.cn_pos = c.take<int>(N);
+    l.first = c.take<int>(N);
+    l.comp_ex = c.take<int>(N + 1);
+    l.occs = c.take<int>(N);
     return l;
 }
 
-extern "C" int64_t p3_asm_plan_workspace_bytes(int64_t N, int64_t M) { return ap_layout(N, M).bytes; }
+extern "C" int64_t p3_asm_plan_workspace_bytes(int64_t N, int64_t M) {
+    P3Carve c = {nullptr, 0};
+    ap_carve(N, M, c);
+    return c.at;
+}
 
 extern "C" int p3_asm_plan(const int64_t* path_index, int64_t M, const int64_t* path_delim, int64_t D, int64_t N, int32_t* comp_ptr, int32_t* cn_node, int32_t* cn_occ,
                            int32_t* slot_nb, int32_t* node_local, int32_t* slot_k, int32_t* counts, int32_t* status, void* workspace, void* stream) {
@@ -439,46 +449,42 @@ extern "C" int p3_asm_plan(const int64_t* path_index, int64_t M, const int64_t* 
     P3_CHECK((M == 0 || (path_index && slot_nb && slot_k)) && (N == 0 || (cn_node && node_local)) && (D == 0 || path_delim), P3_EINVAL, "p3_asm_plan: null pointer");
     P3_CHECK(N == 0 || workspace, P3_EINVAL, "p3_asm_plan: null workspace (p3_asm_plan_workspace_bytes(N, M))");
     hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(counts, 0, 2 * sizeof(int32_t), s) != hipSuccess || hipMemsetAsync(status, 0, sizeof(int32_t), s) != hipSuccess)
-        P3_CHECK(false, P3_EINVAL, "p3_asm_plan: hipMemsetAsync failed");
+    P3_TRY(p3_memset(counts, 0, 2 * sizeof(int32_t), s));
+    P3_TRY(p3_memset(status, 0, sizeof(int32_t), s));
     if (N == 0) {          // no node: every id there is lies outside [0, 0)
-        if (hipMemsetAsync(comp_ptr, 0, sizeof(int32_t), s) != hipSuccess || hipMemsetAsync(cn_occ, 0, sizeof(int32_t), s) != hipSuccess ||
-            (M > 0 && hipMemsetD32Async((hipDeviceptr_t)status, 2, 1, s) != hipSuccess))
-            P3_CHECK(false, P3_EINVAL, "p3_asm_plan: hipMemsetAsync failed");
-        return P3_OK;
+        P3_TRY(p3_memset(comp_ptr, 0, sizeof(int32_t), s));
+        P3_TRY(p3_memset(cn_occ, 0, sizeof(int32_t), s));
+        return M > 0 ? p3_hip_status(hipMemsetD32Async((hipDeviceptr_t)status, 2, 1, s)) : P3_OK;
     }
-    const ApLayout l = ap_layout(N, M);
-    char* ws = (char*)workspace;
-    int *startf = (int*)(ws + l.o_startf), *endf = (int*)(ws + l.o_endf), *pid_ex = (int*)(ws + l.o_pid), *gstart = (int*)(ws + l.o_gstart), *gend = (int*)(ws + l.o_gend);
-    int *plab = (int*)(ws + l.o_plab), *pmin = (int*)(ws + l.o_pmin), *cn_pos = (int*)(ws + l.o_cn_pos), *first = (int*)(ws + l.o_first);
-    int *comp_ex = (int*)(ws + l.o_comp_ex), *occs = (int*)(ws + l.o_occs);
-    int2* links = (int2*)(ws + l.o_links);
+    P3Carve carve = {(char*)workspace, 0};
+    const ApWs l = ap_carve(N, M, carve);
     const int n = (int)N, m = (int)M;
     const int64_t span = M > D ? M : D;
     const auto grid_of = [](int64_t items) { const int64_t g = (items + SK_THREADS - 1) / SK_THREADS; return (unsigned)(g < 1 ? 1 : (g < SK_MAX_GRID ? g : SK_MAX_GRID)); };
     const unsigned ngrid = grid_of(N), mgrid = grid_of(M);
-    if (hipMemsetAsync(gstart, 0xff, N * sizeof(int), s) != hipSuccess) P3_CHECK(false, P3_EINVAL, "p3_asm_plan: hipMemsetAsync failed");
-    const sk_u64* sa = (const sk_u64*)(ws + l.o_keya);
+    P3_TRY(p3_memset(l.gstart, 0xff, N * sizeof(int), s));
+    const sk_u64* sa = l.keya;
     if (M > 0) {
-        if (hipMemsetAsync(startf, 0, M * sizeof(int), s) != hipSuccess || hipMemsetAsync(endf, 0, M * sizeof(int), s) != hipSuccess ||
-            hipMemsetAsync(pmin, 0x7f, M * sizeof(int), s) != hipSuccess)
-            P3_CHECK(false, P3_EINVAL, "p3_asm_plan: hipMemsetAsync failed");
-        ap_mark_kernel<<<grid_of(span), SK_THREADS, 0, s>>>(path_index, m, path_delim, D, n, startf, endf, (sk_u64*)(ws + l.o_keya), status);
-        ap_scan_kernel<<<1, SK_SCAN_THREADS, 0, s>>>(startf, pid_ex, m);
-        sa = ap_sort((sk_u64*)(ws + l.o_keya), (sk_u64*)(ws + l.o_keya2), m, s);
-        ap_groups_kernel<<<mgrid, SK_THREADS, 0, s>>>(sa, m, n, gstart, gend);
-        ap_components_kernel<<<1, SK_SCAN_THREADS, 0, s>>>(sa, m, pid_ex, startf, plab, links);
-        ap_node_min_kernel<<<ngrid, SK_THREADS, 0, s>>>(sa, n, m, gstart, pid_ex, startf, plab, pmin);
-        P3_LAUNCH_CHECK();
+        P3_TRY(p3_memset(l.startf, 0, M * sizeof(int), s));
+        P3_TRY(p3_memset(l.endf, 0, M * sizeof(int), s));
+        P3_TRY(p3_memset(l.pmin, 0x7f, M * sizeof(int), s));
+        P3_TRY(p3_launch<ap_mark_kernel>(nullptr, grid_of(span), SK_THREADS, 0, s, path_index, m, path_delim, D, n, l.startf, l.endf, l.keya, status));
+        P3_TRY(p3_launch<ap_scan_kernel>(nullptr, 1, SK_SCAN_THREADS, 0, s, l.startf, l.pid_ex, m));
+        P3_TRY(ap_sort(l.keya, l.keya2, m, s, &sa));
+        P3_TRY(p3_launch<ap_groups_kernel>(nullptr, mgrid, SK_THREADS, 0, s, sa, m, n, l.gstart, l.gend));
+        P3_TRY(p3_launch<ap_components_kernel>(nullptr, 1, SK_SCAN_THREADS, 0, s, sa, m, l.pid_ex, l.startf, l.plab, l.links));
+        P3_TRY(p3_launch<ap_node_min_kernel>(nullptr, ngrid, SK_THREADS, 0, s, sa, n, m, l.gstart, l.pid_ex, l.startf, l.plab, l.pmin));
     }
-    ap_node_key_kernel<<<ngrid, SK_THREADS, 0, s>>>(sa, n, m, gstart, pid_ex, startf, plab, pmin, (sk_u64*)(ws + l.o_keyb));
-    const sk_u64* sb = ap_sort((sk_u64*)(ws + l.o_keyb), (sk_u64*)(ws + l.o_keyb2), n, s);
-    ap_cn_kernel<<<ngrid, SK_THREADS, 0, s>>>(sb, n, gstart, gend, cn_node, cn_pos, first, occs);
-    ap_scan_kernel<<<1, SK_SCAN_THREADS, 0, s>>>(first, comp_ex, n);
-    ap_scan_kernel<<<1, SK_SCAN_THREADS, 0, s>>>(occs, cn_occ, n);
-    ap_comp_ptr_kernel<<<ngrid, SK_THREADS, 0, s>>>(n, first, comp_ex, comp_ptr, counts);
-    ap_node_local_kernel<<<ngrid, SK_THREADS, 0, s>>>(n, first, comp_ex, comp_ptr, cn_node, node_local, counts);
-    if (M > 0) ap_slots_kernel<<<mgrid, SK_THREADS, 0, s>>>(sa, m, n, path_index, gstart, cn_pos, cn_occ, startf, endf, node_local, slot_k, slot_nb);
-    P3_LAUNCH_CHECK();
+    P3_TRY(p3_launch<ap_node_key_kernel>(nullptr, ngrid, SK_THREADS, 0, s, sa, n, m, l.gstart, l.pid_ex, l.startf, l.plab, l.pmin, l.keyb));
+    const sk_u64* sb;
+    P3_TRY(ap_sort(l.keyb, l.keyb2, n, s, &sb));
+    P3_TRY(p3_launch<ap_cn_kernel>(nullptr, ngrid, SK_THREADS, 0, s, sb, n, l.gstart, l.gend, cn_node, l.cn_pos, l.first, l.occs));
+    P3_TRY(p3_launch<ap_scan_kernel>(nullptr, 1, SK_SCAN_THREADS, 0, s, l.first, l.comp_ex, n));
+    P3_TRY(p3_launch<ap_scan_kernel>(nullptr, 1, SK_SCAN_THREADS, 0, s, l.occs, cn_occ, n));
+    P3_TRY(p3_launch<ap_comp_ptr_kernel>(nullptr, ngrid, SK_THREADS, 0, s, n, l.first, l.comp_ex, comp_ptr, counts));
+    P3_TRY(p3_launch<ap_node_local_kernel>(nullptr, ngrid, SK_THREADS, 0, s, n, l.first, l.comp_ex, comp_ptr, cn_node, node_local, counts));
+    if (M > 0)
+        P3_TRY(p3_launch<ap_slots_kernel>(nullptr, mgrid, SK_THREADS, 0, s, sa, m, n, path_index, l.gstart, l.cn_pos, cn_occ, l.startf, l.endf, node_local, slot_k,
+                                          slot_nb));
     return P3_OK;
 }

@@ -125,6 +125,24 @@ def test_a_polyline_over_the_cap_takes_the_fallback_by_itself():
     assert want["counts"][0] < k // 10
 
 
+def test_more_polylines_than_one_pass_of_the_scan_workgroup():
+    """1025 polylines of 3 points: cs_offsets and cs_scan are one workgroup of 1024 threads, so the last polyline's offsets come from the carry of the first pass.
+    Right angles with legs a != b on an axis-aligned field: the middle point lies a b / sqrt(a^2 + b^2) >= 0.89 from the chord (tolerance 0.5), no edge on a diagonal."""
+    P = 1025
+    i = np.arange(P)
+    a, b = 1 + i % 3, 2 + i % 3 + (i // 3) % 2
+    pos = np.stack([np.stack([np.ones(P), np.ones(P)], 1), np.stack([np.ones(P), 1 + a], 1), np.stack([1 + b, 1 + a], 1)], 1).reshape(3 * P, 2)
+    assert pos.max() <= 7
+    slices = np.stack([3 * i, 3 * i + 3], 1).astype(np.int64)
+    c0c2 = np.zeros((1, 4, 8, 8), dtype=np.float32)
+    c0c2[0, 0] = -1.0
+    args = (pos.astype(np.float32), None, slices, (i % 2).astype(np.uint8), np.zeros(P, dtype=np.int32), c0c2)
+    want = R.corner_split(*args, 0.5, 0.5)
+    assert want["counts"][1] >= P
+    for fallback in (False, True):
+        same(host(run(*args, 0.5, 0.5, force_fallback=fallback), want["offsets"][-1]), want)
+
+
 def test_staircase_peels_one_point_per_round():
     """200 points of a zigzag whose amplitude decays by 3 % per point: the farthest point of every section is the one right behind its start, so
     Douglas-Peucker keeps one point per level and the recursion is 198 deep"""

@@ -76,6 +76,18 @@ def test_device_equals_the_restatement(batches, i):
     assert np.all(np.abs(want["poly_area"] - MIN_AREA) > 1e-4)          # no area is a tie; the probabilities are exact quotients on both sides
 
 
+def test_more_images_than_one_pass_of_the_scan_workgroups():
+    """1025 indicators of 2 x 2 and no piece: every image gives its border polygon (area 1), and the 1025th takes its edge slots (ffp_offsets) and its place in
+    the outputs (ffp_scan) from the carry of the first pass of the 1024-thread scans"""
+    five = indicators(5, 2, 2)
+    ind = five[np.arange(1025) % 5]
+    pieces = [[] for _ in range(1025)]
+    want = R.run(pieces, ind, 0.5, THRESHOLD)
+    assert tuple(want["counts"]) == (1025, 1025, 5 * 1025) and want["poly_batch"].tolist() == list(range(1025))
+    for fallback in (False, True):
+        same(device(pieces, ind, min_area=0.5, force_fallback=fallback), want, f"fallback={fallback}")
+
+
 def test_hand_cases_have_their_written_out_rings_on_the_device():
     for name in ("touching_squares", "theta", "open_polyline"):
         pieces, _, polygons, areas = C.HAND[name]

@@ -91,6 +91,23 @@ def test_big_images_take_the_workspace_form():
     assert bits(got, run(inp, force_fallback=True))
 
 
+@pytest.mark.parametrize("images", [3, 4])
+def test_more_region_slots_than_one_pass_of_the_offset_scan(images):
+    """400 region slots per image against the 1024 threads of hp_offsets_kernel, 8 x 8 labels, one 2 x 2 region in the first and in the last image.  3 images
+    (1200 slots): the empty slots 1024 .. 1199 and n_vertices[2] hold the carry of the first pass.  4 images (1600 slots): the last image's polygon is slot 1200,
+    in the second pass, and starts at the carry."""
+    fg = np.zeros((images, 8, 8), bool)
+    fg[0, 1:3, 1:3] = fg[images - 1, 4:6, 3:5] = True
+    inp = inputs(fg, [np.zeros((0, 2))] * images)
+    inp["bbox"] = np.concatenate([inp["bbox"], np.zeros((images, 399, 4), np.int32)], 1)
+    inp["R"] = 400
+    want = expected(inp)
+    assert want["n_vertices"][0] > 0 and want["n_vertices"][1] == 0 and want["poly_slice"][images - 1, 0].tolist() == [want["n_vertices"][0], want["counts"][0]]
+    got = run(inp)
+    same(got, want)
+    assert bits(got, run(inp, force_fallback=True))
+
+
 # ------------------------------------------------------------------------------------------------ (c) junctions
 def test_junction_cases():
     fg, juncs = R.junction_cases()

@@ -112,6 +112,36 @@ def test_golden_regions(first):
     assert seen >= 15 and rings >= 8
 
 
+@pytest.mark.parametrize("case_", ["squares", "courtyards"])
+def test_more_region_slots_than_one_pass_of_the_offset_scans(case_):
+    """400 region slots per image against the 1024 threads of hp_offsets_kernel and hp_ring_offsets_kernel.
+    squares: 3 images (1200 slots) of 8 x 8 labels, one 2 x 2 region in images 0 and 2; the empty slots 1024 .. 1199 and n_vertices[2] hold the carry of the first
+    pass, the ring carries stay 0 (no hole).
+    courtyards: 4 images (1600 slots) of 12 x 12, a 10 x 10 block with an 8 x 8 hole in images 0 and 3; image 3's region is slot 1200, in the second pass, so its
+    polygon, its ring and its ring's vertices start at non-zero carries."""
+    if case_ == "squares":
+        fg = np.zeros((3, 8, 8), bool)
+        fg[0, 1:3, 1:3] = fg[2, 4:6, 3:5] = True
+    else:
+        fg = np.zeros((4, 12, 12), bool)
+        fg[0, 1:11, 1:11] = fg[3, 1:11, 1:11] = True
+        fg[0, 2:10, 2:10] = fg[3, 2:10, 2:10] = False
+    last = len(fg) - 1
+    inp = inputs(fg, [NOJ] * len(fg))
+    inp["bbox"] = np.concatenate([inp["bbox"], np.zeros((len(fg), 399, 4), np.int32)], 1)
+    inp["R"] = 400
+    want = expected(inp)
+    assert want[0]["poly_slice"][last, 0].tolist() == [want[0]["n_vertices"][0], want[0]["counts"][0]] and want[0]["n_vertices"][0] > 0
+    assert want[1]["region_rings"].shape == (len(fg), 400, 2)
+    if case_ == "squares":
+        assert want[1]["ring_counts"][0] == 0
+    else:
+        assert want[1]["ring_counts"][0] == 2 and want[1]["region_rings"][last, 0].tolist() == [1, 2] and want[1]["ring_slice"][1, 0] > 0
+    got = run(inp)
+    same(got, want)
+    assert bits(got, run(inp, force_fallback=True))
+
+
 # ------------------------------------------------------------------------------------------------ (b) hand shapes
 def test_hand_shapes():
     inp, want = case("hand")

@@ -124,6 +124,20 @@ def test_batch_is_image_major_and_an_image_alone_gives_the_same(want):
         assert_same(alone[0], got[b], f"image {b} alone")
 
 
+def test_more_tiles_than_one_pass_of_the_tile_scans():
+    """1025 maps of 2 x 2 are 1025 edge tiles and 1025 key tiles; the workgroup that scans them has 1024 threads, so the last image's offsets come from the carry
+    of the first pass.  One corner pixel above the level in every third image: a two-vertex open contour there, nothing elsewhere."""
+    maps = np.zeros((1025, 2, 2), dtype=np.float32)
+    maps[::3, 0, 0] = 1.0
+    with_corner, empty = M.find_contours_ref(maps[0]), M.find_contours_ref(maps[1])
+    assert len(with_corner) == 1 and empty == []
+    ref = [with_corner if b % 3 == 0 else [] for b in range(len(maps))]
+    got, tp = device_contours(maps, 0.5)
+    for b in (0, 1, 3, 1020, 1023, 1024):
+        assert_same(got[b], M.as_float32(ref[b]), f"image {b}")
+    assert_fields(tp, ref)
+
+
 def test_two_images_with_contours_keep_image_major_order():
     a, b = M.smooth(33, 20, 7), M.smooth(33, 20, 4)
     ref = [M.find_contours_ref(a), M.find_contours_ref(b)]

@@ -129,6 +129,25 @@ def test_a_capacity_one_short_sets_status_keeps_the_counts_and_the_guards(short)
                                        max_paths=caps["paths"])
 
 
+def test_more_contours_than_one_pass_of_the_scan_workgroup():
+    """1025 open contours of 3 points, 600 in image 0 and 425 in image 1, no filter: sk_scan_kernel is one workgroup of 1024 threads, so the last contour takes
+    its first node, its first slot and its path number from the carry of the first pass"""
+    from pixelspointspolygons_amd import hip, polygonize_asm as A
+    P, split = 1025, 600
+    i = np.arange(P, dtype=np.float32)
+    cs = [np.array([[1 + k, 1], [1 + k, 2], [1.5 + k, 2]], dtype=np.float32) for k in i]
+    ref = A.skeletons_to_tensorskeleton([A.contours_to_skeleton(cs[:split], None), A.contours_to_skeleton(cs[split:], None)])
+    assert ref.num_paths == P and ref.pos.shape[0] == 3 * P
+    sl = torch.arange(P, dtype=torch.int64)
+    end = torch.tensor([1, 0, 1], dtype=torch.uint8).repeat(P)
+    out = hip.skeleton_from_contours(torch.from_numpy(np.concatenate(cs)).to(DEV), torch.stack([3 * sl, 3 * sl + 3], 1).to(DEV),
+                                     (sl >= split).to(torch.int32).to(DEV), end.to(DEV), 2, None)
+    assert out["counts"] == (3 * P, 3 * P, P, 3)
+    assert torch.equal(out["pos"].cpu().view(torch.int32), ref.pos.view(torch.int32))
+    for k in ("degrees", "path_index", "path_delim", "batch", "batch_delim"):
+        assert torch.equal(out[k].cpu(), getattr(ref, k)), k
+
+
 # ---------------------------------------------------------------------------------------------------------------- plan
 def test_plan_of_the_fixture_container_equals_the_host_plan():
     from pixelspointspolygons_amd import polygonize_asm as A
@@ -138,6 +157,17 @@ def test_plan_of_the_fixture_container_equals_the_host_plan():
     plan = plan_of(ts["path_index"], ts["path_delim"], N)
     assert (plan.num_comps, plan.max_comp) == (10, 80)
     assert_plan(plan, host)
+
+
+def test_plan_of_a_path_longer_than_one_pass_of_the_scan_workgroup():
+    """one open path over 4097 nodes in a permuted order: ap_scan takes 1024 threads x 4 entries = 4096 a pass, so the last slot and the last node take their
+    prefix from the carry of the first pass; the link scan of ap_components (1024 a pass) crosses four times and finds no link"""
+    from pixelspointspolygons_amd import polygonize_asm as A
+    N = 4097
+    idx, delim = np.random.default_rng(3).permutation(N).astype(np.int64), np.array([0, N], dtype=np.int64)
+    host = A.AsmPlan(idx, delim, N)
+    assert (host.num_comps, host.max_comp) == (1, N)
+    assert_plan(plan_of(idx, delim, N), host)
 
 
 def test_plan_of_the_adversarial_graph_equals_the_host_plan():
