@@ -910,6 +910,48 @@ int p3_asm_plan(const int64_t* path_index, int64_t M, const int64_t* path_delim,
 int64_t p3_asm_plan_workspace_bytes(int64_t N, int64_t M);
 
 /* ------------------------------------------------------------------------------------------
+ * FFL active-skeleton initialisation from the segmentation map: init_method "skeleton_device" (csrc/skeleton_thin.hip).  The reference's
+ * init_method "skeleton" (predict/ffl/polygonize_asm.py:655-675 compute_skeletons, then skimage binary_closing, skimage skeletonize and skan.Skeleton) restated
+ * with a written definition; it is NOT those libraries bit for bit (Zhang-Suen instead of skimage's table, the diagonal rule instead of skan's junctions).
+ * Input: seg fp32, image b at seg + b stride_b, channel c at + c stride_c (strides in elements), each channel H x W with contiguous rows.  Channel 0 is the
+ * interior probability, channel 1, read only when C >= 2, the edge probability.  level is rounded to fp32 (as torch compares a Python number with an fp32 map).
+ *   1 Edge mask.  m = (level < seg[0]) as fp32.  gx, gy = the 3 x 3 Sobel responses of m, replicate padding, divided by 8 (kornia's normalised kernel).
+ *     g = sqrt((2 gx)^2 + (2 gy)^2) in fp32; with C >= 2, g = clamp(seg[1] + g, 0, 1).  edge = (level < g).  Both comparisons are strict.  2 gx and 2 gy are
+ *     multiples of 1/4, the sum of squares is exact, the root is correctly rounded, nothing is contracted: the mask is torch's on the CPU bit for bit.
+ *   2 Pad by 2 on every side, edge replication: the working image is (H+4) x (W+4).
+ *   3 Closing: dilation, then erosion, by the 3 x 3 cross.  Outside the working image is background for the dilation, foreground for the erosion
+ *     (scipy.ndimage.binary_dilation(border_value=0), binary_erosion(border_value=1), what skimage's binary_closing does).
+ *   4 Thinning: Zhang-Suen on the working image, outside = background.  P2 .. P9 = N, NE, E, SE, S, SW, W, NW; B = their sum; A = the 0 -> 1 steps in the cyclic
+ *     sequence P2, P3, ..., P9, P2.  Sub-iteration 1 deletes a foreground pixel when 2 <= B <= 6, A == 1, P2 P4 P6 == 0 and P4 P6 P8 == 0; sub-iteration 2 when
+ *     2 <= B <= 6, A == 1, P2 P4 P8 == 0 and P2 P6 P8 == 0.  A sub-iteration decides every pixel from the image as it stood when it began.  A round is 1 then
+ *     2; rounds repeat until one deletes nothing.  No round cap: every round but the last deletes a pixel, at most (foreground + 1) rounds.
+ *   5 Crop the pad: the skeleton image is H x W.
+ *   6 Graph.  Two skeleton pixels are linked when they are 4-neighbours, or diagonal neighbours with neither of the two pixels 4-adjacent to both a skeleton
+ *     pixel (no triangles at staircase corners; nothing is disconnected, the two 4-links through the shared pixel remain).  degree = links of a pixel (at most
+ *     4).  A pixel without a link is no node.  Nodes are numbered in raster order (row, then column), image after image.  pos = (row, col) as fp32.
+ *   7 Paths.  A path is a maximal chain of links whose interior nodes all have degree 2; its two ends have degree != 2; a loop from a junction back to it is
+ *     [u, ..., u].  Of a chain's two directed readings the one with the lexicographically smaller (first node, second node) is kept.  A connected set of
+ *     degree-2 nodes without an end is a cycle: it starts at its smallest node, goes to the smaller of that node's two neighbours first, and repeats the
+ *     first id at its end.  Paths are ordered by (first node, second node), ascending; node ids are image-major, so paths are too.
+ * Output, the fields of p3_skeleton_from_contours: out_pos fp32 [max_nodes,2]; degrees int64 [max_nodes]; path_index int64 [max_slots]; path_delim int64
+ * [max_paths+1], entry P = M; batch int64 [max_nodes]; batch_delim int64 [B+1] = the paths in front of each image; counts int32 [4] = (N nodes, M slots,
+ * P paths, nodes of the longest path, a repeated end counted once); status int32 [1] bit 0 = a capacity was too small: counts hold the true totals and
+ * nothing is written past a capacity.
+ * Capacities that can never overflow: N <= B H W.  A node has at most 4 links (a diagonal link needs both 4-neighbours beside it empty), so there are at
+ * most 2 N links; every link lies on exactly one path and a path has one slot more than links: P <= links <= 2 N and M = links + P <= 4 N.
+ *   max_nodes = B H W, max_paths = 2 B H W, max_slots = 4 B H W.
+ * Size limit: H + 4 <= 512 and W + 4 <= 512 (one workgroup per image keeps two bit planes of the working image in 64 KB of LDS); a larger image, C < 1 or a
+ * negative capacity is P3_ESHAPE before any launch.  Three launches whatever the data, no memset, no host synchronisation.  One writer per output element;
+ * the one atomic is an or in LDS and no workspace word is written by two workgroups: two runs give the same bits, an image alone gives the rows it gives inside a batch, re-based.
+ * B == 0 or a batch without a skeleton pixel: zero counts, status and batch_delim, nothing else is touched.
+ * workspace: p3_skeleton_from_seg_workspace_bytes(B, H, W) bytes (0 for B <= 0).
+ * ------------------------------------------------------------------------------------------ */
+int p3_skeleton_from_seg(const float* seg, int B, int C, int H, int W, int64_t stride_b, int64_t stride_c, double level, int max_nodes, int max_slots,
+                         int max_paths, float* out_pos, int64_t* degrees, int64_t* path_index, int64_t* path_delim, int64_t* batch, int64_t* batch_delim,
+                         int32_t* counts, int32_t* status, void* workspace, void* stream);
+int64_t p3_skeleton_from_seg_workspace_bytes(int B, int H, int W);
+
+/* ------------------------------------------------------------------------------------------
  * HiSup polygons: models/hisup/polygon.py:56-93,111-169 (`ext_c_to_poly_coco`, `diagonal_to_square`, `simple_polygon`, `get_poly_crowdai` with
  * test_inria = False) on the device: the OUTER polygon of every region of p3_hisup_regions, what `forward_val` returns as `polys_pred`.
  * Inputs as the two kernels above write them: labels int32 [B,H,W], n_regions int32 [B], bbox int32 [B,max_regions,4], juncs fp32 [B,600,2] (x, y),

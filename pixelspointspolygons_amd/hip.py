@@ -1640,6 +1640,60 @@ def asm_plan(path_index, path_delim, num_nodes):
     return out
 
 
+# ------------------------------------------------------------------------------------------ FFL active-skeleton initialisation from the segmentation map
+SKELETON_THIN_MAX_SIDE = 508          # csrc/skeleton_thin.hip: H + 4 and W + 4 <= 512, two bit planes of the padded image in 64 KB of LDS
+
+
+def skeleton_from_seg_capacity(B, H, W):
+    """(max_nodes, max_slots, max_paths) that cannot overflow: N <= B H W; a node has at most 4 links (a diagonal link needs both 4-neighbours beside it
+    empty), so links <= 2 N; every link lies on exactly one path and a path has one slot more than links: P <= links and M = links + P <= 4 N."""
+    n = max(int(B) * int(H) * int(W), 1)
+    return n, 4 * n, 2 * n
+
+
+def skeleton_from_seg_device(seg, level=0.5, max_nodes=None, max_slots=None, max_paths=None, out=None):
+    """p3_skeleton_from_seg (init_method "skeleton_device", DESIGN.md section 20: edge mask, closing, Zhang-Suen thinning, link graph, maximal degree-2 paths)
+    without any synchronisation.  seg fp32 [B,C,H,W]: channel 0 the interior probability, channel 1 (when C >= 2) the edge probability; batch and channel
+    strides are taken as they are (a channel slice of a wider tensor is not copied), rows must be contiguous or the map is copied.  H, W <= 508.
+    -> dict(pos f32 [max_nodes,2] (row, col), degrees i64 [max_nodes], path_index i64 [max_slots], path_delim i64 [max_paths+1], batch i64 [max_nodes],
+    batch_delim i64 [B+1], counts i32 [4] = (nodes, slots, paths, nodes of the longest path), status i32 [1] (bit 0: a capacity was too small; counts are
+    the true totals then and nothing is written past the capacities)).  The default capacities (skeleton_from_seg_capacity) cannot overflow.
+    out: the caller's own tensors for any of the outputs (`_outputs`)."""
+    _dev(seg)
+    if seg.dim() != 4 or seg.shape[1] < 1 or seg.shape[2] < 1 or seg.shape[3] < 1:
+        raise P3Error(f"skeleton_from_seg: seg [B, C, H, W] with C, H, W >= 1 expected, got {tuple(seg.shape)}")
+    B, C, H, W = seg.shape
+    if max(H, W) > SKELETON_THIN_MAX_SIDE:
+        raise P3Error(f"skeleton_from_seg: H and W must not exceed {SKELETON_THIN_MAX_SIDE}, got {H} x {W}")
+    cap = skeleton_from_seg_capacity(B, H, W)
+    nn, ns, npth = (c if m is None else int(m) for c, m in zip(cap, (max_nodes, max_slots, max_paths)))
+    if nn < 1 or ns < 1 or npth < 1:
+        raise P3Error(f"skeleton_from_seg: max_nodes = {max_nodes}, max_slots = {max_slots}, max_paths = {max_paths}")
+    dev, i32, i64 = seg.device, torch.int32, torch.int64
+    out = _outputs("skeleton_from_seg", dev, (("pos", (nn, 2), torch.float32), ("degrees", (nn,), i64), ("path_index", (ns,), i64), ("path_delim", (npth + 1,), i64),
+                                              ("batch", (nn,), i64), ("batch_delim", (B + 1,), i64), ("counts", (4,), i32), ("status", (1,), i32)), out)
+    # a converted copy stays referenced until the launch is queued
+    s32 = seg if seg.dtype == torch.float32 else seg.float()
+    if s32.stride(3) != 1 or s32.stride(2) != W or min(s32.stride(0), s32.stride(1)) < 0:
+        s32 = s32.contiguous()
+    ws = workspace(int(lib().p3_skeleton_from_seg_workspace_bytes(B, H, W)), dev, "skeleton_from_seg") if B else None
+    check(lib().p3_skeleton_from_seg(ptr(s32), B, C, H, W, s32.stride(0), s32.stride(1), float(level), nn, ns, npth, ptr(out["pos"]), ptr(out["degrees"]),
+                                     ptr(out["path_index"]), ptr(out["path_delim"]), ptr(out["batch"]), ptr(out["batch_delim"]), ptr(out["counts"]),
+                                     ptr(out["status"]), ptr(ws), stream()), "p3_skeleton_from_seg")
+    return out
+
+
+def skeleton_from_seg(seg, level=0.5, max_nodes=None, max_slots=None, max_paths=None):
+    """the checking form of skeleton_from_seg_device: reads counts and status once (the only read-back), raises when a capacity was too small and narrows
+    the arrays: pos [N,2], degrees [N], path_index [M], path_delim [P+1] ([0] without a path), batch [N]; counts = (N, M, P, longest)."""
+    out = skeleton_from_seg_device(seg, level, max_nodes, max_slots, max_paths)
+    fit = lambda N, M, P, _: (f"{N} nodes, {M} slots and {P} paths do not fit max_nodes = {out['pos'].shape[0]}, max_slots = {out['path_index'].shape[0]}, "
+                              f"max_paths = {out['path_delim'].shape[0] - 1}")
+    P = _read_back(out, "skeleton_from_seg", ((1, fit),), dict(pos=0, degrees=0, batch=0, path_index=1))["counts"][2]
+    out["path_delim"] = out["path_delim"][:P + 1] if P else torch.zeros(1, dtype=torch.int64, device=seg.device)          # nothing was written without a path
+    return out
+
+
 def cast(a, dtype):
     out = torch.empty(a.shape, dtype=dtype, device=a.device)
     check(lib().p3_cast(ptr(a.contiguous()), dt(a), ptr(out), dt(out), a.numel(), stream()), "p3_cast")

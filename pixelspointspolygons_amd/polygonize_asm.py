@@ -9,8 +9,14 @@ The marching-squares initialisation in front (`init_method: marching_squares`, g
 on the device -> optimised skeleton on the device, with one read-back of a few counts per stage and no host contour.
 `contours_to_skeleton`, `skeletons_to_tensorskeleton` and the host `AsmPlan` stay for callers that already hold host contours or skeletons.
 
-What stays host code of the caller: the `skimage` skeletonize plus `skan` initialisation (`init_method: skeleton`) in front.  `post_process` behind is
-polygonize_post.py: `corner_split_skeleton`, and `polygonize_asm_polygons` for the whole of `PolygonizerASM.__call__` down to the filtered polygons.
+The reference's default initialisation (`init_method: skeleton`, compute_skeletons :655-675 and get_skeleton: skimage binary_closing, skimage skeletonize,
+skan.Skeleton) has a device restatement under a name of its own, `init_method: skeleton_device`: p3_skeleton_from_seg (csrc/skeleton_thin.hip) builds the edge
+mask, closes it, thins it with Zhang-Suen and reads the path graph off the skeleton, junctions and shared walls included (DESIGN.md section 20 holds the
+definition and the two stated deviations from skimage and skan).  `init_skeletons(..., method="skeleton_device")` and `polygonize_device` take it.
+
+What stays host code of the caller: the `skimage` skeletonize plus `skan` initialisation itself (`init_method: skeleton`), which still raises here.
+`post_process` behind is polygonize_post.py: `corner_split_skeleton`, and `polygonize_asm_polygons` for the whole of `PolygonizerASM.__call__` down to the
+filtered polygons.
 
 `Skeleton`, `Paths`, `TensorSkeleton`, `skeletons_to_tensorskeleton` and `tensorskeleton_to_skeletons` keep the fields of
 torch_lydorn/torchvision/transforms/tensorskeleton.py: pos [N,2] (row, col), degrees [N], path_index [M], path_delim [P+1], batch [N], batch_delim [B+1],
@@ -342,17 +348,28 @@ def optimize_skeletons(seg_batch, crossfield_batch, skeletons_batch, config=ASM_
     return [skeleton_to_polylines(sk) for sk in tensorskeleton_to_skeletons(optimizer.optimize())]
 
 
-def init_skeletons(seg_or_indicator, level=0.5, min_area=10):
-    """get_marching_squares_skeleton per image + skeletons_to_tensorskeleton on the device: seg [B, C, H, W] (channel 0 is the indicator, read in place) or
-    indicator [B, H, W] -> a device TensorSkeleton that carries its device-built plan, None when no path is kept.  min_area None keeps every contour.
-    Three stages (contours, skeleton, plan), each with one read-back of its counts; no contour, node or path index reaches the host."""
+INIT_METHODS = ("marching_squares", "skeleton_device")          # what init_skeletons builds on the device
+
+
+def init_skeletons(seg_or_indicator, level=0.5, min_area=10, method="marching_squares"):
+    """The initial skeletons of a batch on the device: seg [B, C, H, W] (channel 0 is the indicator, read in place) or indicator [B, H, W] -> a device
+    TensorSkeleton that carries its device-built plan, None when no path is kept.  No contour, node or path index reaches the host.
+    method "marching_squares": get_marching_squares_skeleton per image + skeletons_to_tensorskeleton; min_area None keeps every contour.  Three stages
+    (contours, skeleton, plan), each with one read-back of its counts.
+    method "skeleton_device": p3_skeleton_from_seg (edge mask from channel 0 and, when there is one, the edge channel 1; closing; thinning; path graph) and
+    the plan, two read-backs.  min_area is unused there, as in the reference's get_skeleton."""
+    if method not in INIT_METHODS:
+        raise ValueError(f"init_skeletons: method = {method!r}; built on the device: {', '.join(INIT_METHODS)}")
     if not seg_or_indicator.is_cuda:
         raise hip.P3Error("init_skeletons: the map must be a device tensor (there is no CPU path)")
     B = seg_or_indicator.shape[0]
-    c = hip.init_contours(seg_or_indicator, level)
-    if c["counts"][1] == 0:
-        return None
-    sk = hip.skeleton_from_contours(c["pos"], c["poly_slice"], c["poly_batch"], c["is_endpoint"], B, min_area)
+    if method == "skeleton_device":
+        sk = hip.skeleton_from_seg(seg_or_indicator if seg_or_indicator.dim() == 4 else seg_or_indicator[:, None], level)
+    else:
+        c = hip.init_contours(seg_or_indicator, level)
+        if c["counts"][1] == 0:
+            return None
+        sk = hip.skeleton_from_contours(c["pos"], c["poly_slice"], c["poly_batch"], c["is_endpoint"], B, min_area)
     if sk["counts"][2] == 0:
         return None
     tensorskeleton = TensorSkeleton(pos=sk["pos"], degrees=sk["degrees"], path_index=sk["path_index"], path_delim=sk["path_delim"], batch=sk["batch"],
@@ -362,15 +379,22 @@ def init_skeletons(seg_or_indicator, level=0.5, min_area=10):
 
 
 def polygonize_device(seg_batch, crossfield_batch, config=ASM_DEFAULTS):
-    """PolygonizerASM.__call__ (:715-752) with init_method "marching_squares" and without a host skeleton: initial skeletons at config["data_level"] /
-    config["min_area"], the plan and the optimiser, all on the device.  -> the optimised device TensorSkeleton (polygonize_post.corner_split_skeleton or
-    tensorskeleton_to_skeletons take it from there), None when no path is kept.  ASM_DEFAULTS keeps the reference's init_method "skeleton", which is not
-    built: pass {**ASM_DEFAULTS, "init_method": "marching_squares"}."""
-    if config["init_method"] != "marching_squares":
-        raise NotImplementedError(f"init_method = {config['init_method']!r}: only \"marching_squares\" is built on the device; the skimage skeletonize / skan "
-                                  "initialisation (\"skeleton\") is host code of the caller, whose skeletons optimize_skeletons takes")
+    """PolygonizerASM.__call__ (:715-752) without a host skeleton: initial skeletons at config["data_level"] (and config["min_area"] for marching squares),
+    the plan and the optimiser, all on the device.  -> the optimised device TensorSkeleton (polygonize_post.corner_split_skeleton or
+    tensorskeleton_to_skeletons take it from there), None when no path is kept.  config["init_method"]: "marching_squares" or "skeleton_device" (DESIGN.md
+    section 20).  ASM_DEFAULTS keeps the reference's "skeleton", the skimage / skan route itself, which is not built: pass
+    {**ASM_DEFAULTS, "init_method": "skeleton_device"}."""
+    method = config["init_method"]
+    if method == "skeleton":
+        # the message this case has always raised, word for word, and behind it where the device restatement is found
+        raise NotImplementedError(f"init_method = {method!r}: only \"marching_squares\" is built on the device; the skimage skeletonize / skan "
+                                  "initialisation (\"skeleton\") is host code of the caller, whose skeletons optimize_skeletons takes.  Of the reference's "
+                                  "methods, that is: a device restatement of \"skeleton\" with two stated deviations from skimage and skan has a name of its "
+                                  "own, init_method \"skeleton_device\" (DESIGN.md section 20)")
+    if method not in INIT_METHODS:
+        raise NotImplementedError(f"init_method = {method!r} not recognized; built on the device: {', '.join(INIT_METHODS)}")
     _check_maps("polygonize_device", seg_batch, crossfield_batch)
-    tensorskeleton = init_skeletons(seg_batch, config["data_level"], config["min_area"])
+    tensorskeleton = init_skeletons(seg_batch, config["data_level"], config["min_area"], method)
     if tensorskeleton is None:
         return None
     return TensorSkeletonOptimizer(config, tensorskeleton, seg_batch[:, 0, :, :], crossfield_batch).optimize()

@@ -97,7 +97,7 @@ def polygonize_acm_pieces(seg_batch, crossfield_batch, config=polygonize_acm.ACM
 
 
 def polygonize_asm_pieces(seg_batch, crossfield_batch, config, tolerance=None):
-    """The ASM twin: polygonize_asm.polygonize_device (config["init_method"] must be "marching_squares") followed by the ASM form at config["tolerance"] (or
+    """The ASM twin: polygonize_asm.polygonize_device (config["init_method"]: "marching_squares" or "skeleton_device") followed by the ASM form at config["tolerance"] (or
     `tolerance`).  Without any kept path: the same empty result as polygonize_acm_pieces."""
     tolerance = config["tolerance"] if tolerance is None else tolerance
     tensorskeleton = polygonize_asm.polygonize_device(seg_batch, crossfield_batch, config)
@@ -140,7 +140,7 @@ def polygonize_acm_polygons(seg_batch, crossfield_batch, config=polygonize_acm.A
 
 
 def polygonize_asm_polygons(seg_batch, crossfield_batch, config, tolerance=None):
-    """PolygonizerASM.__call__ (config["init_method"] must be "marching_squares") on the device: polygonize_asm_pieces followed by polygons_from_pieces."""
+    """PolygonizerASM.__call__ (config["init_method"]: "marching_squares" or "skeleton_device") on the device: polygonize_asm_pieces followed by polygons_from_pieces."""
     _indicator(seg_batch, "polygonize_asm_polygons")
     return polygons_from_pieces(polygonize_asm_pieces(seg_batch, crossfield_batch, config, tolerance), seg_batch, config)
 
