@@ -1087,6 +1087,54 @@ int p3_ffl_polygons(const float* out_pos, int64_t V, const int64_t* piece_slice,
                     int32_t* poly_flags, int32_t* image_status, int32_t* counts, int32_t* status, void* workspace, void* stream);
 int64_t p3_ffl_polygons_workspace_bytes(int64_t V, int B);
 
+/* ------------------------------------------------------------------------------------------
+ * Polygon metrics: the figures of the reference's Evaluator.evaluate that depend only on two polygon sets and the image size - IoU, C-IoU and NR
+ * (eval/cIoU.py compute_IoU_cIoU) and POLIS, chamfer and Hausdorff (eval/polis_chamfer_hausdorff.py PointBasedMetrics, IoU threshold 0.5, sampling distance
+ * 0.1) - on the device (csrc/poly_metrics.hip).  pycocotools and shapely are not linked: the text below and its float64 restatement
+ * tests/poly_metrics_ref.py are the contract, DESIGN.md section 21 says where the text knowingly differs from those libraries.
+ * Input: two ring sets, ground truth (gt) and predictions (dt).  A ring set: pos fp32 [V,2] in (x, y) order, ring_slice int64 [R,2] = [first vertex, one
+ * past the last), ring_image int32 [R], non-decreasing.  Rings are open (n distinct vertices, the closing edge implied) and exterior rings only.  A ring
+ * with fewer than 3 vertices, or with a coordinate that is not finite or lies beyond +-32768, is invalid: it takes part in nothing, is counted in
+ * invalid_rings[image] and sets status bit 0.  A ring with ring_image outside [0, B) or a slice outside [0, V] is left out and sets status bit 1.
+ * All arithmetic is in double on the fp32 coordinates converted once, every product and sum rounded on its own (no fused multiply-add).
+ *   1  mask of an image: pixel (r, c), 0 <= r < H, 0 <= c < W, has centre p = (c + 0.5, r + 0.5) and lies in a ring by the even-odd rule: an edge (a, b),
+ *      the closing one included, is crossed when (a.y <= p.y) != (b.y <= p.y), and the crossing lies to the right of p when the sign of
+ *      (b.x - a.x)(p.y - a.y) - (p.x - a.x)(b.y - a.y) equals the sign of b.y - a.y.  The mask of a set is the union of the parities of its valid rings.
+ *   2  per image: I = |gt and dt|, U = |gt or dt| as integers; iou = 1 when U == 0, else I / (U + 1e-9); N_gt, N_dt the vertex counts of the valid
+ *      rings; nr = 1 - |N_dt - N_gt| / (N_dt + N_gt + 1e-9); ciou = iou nr.  IoU, C-IoU and NR are the means over all B images, summed in image order.
+ *   3  matching per image: the box of a ring is [min x, min y, max x - min x, max y - min y]; box IoU with iw = min(x0 + w0, x1 + w1) - max(x0, x1), ih
+ *      likewise, 0 when iw <= 0 or ih <= 0, else i = iw ih and iou = i / (w0 h0 + w1 h1 - i).  For every valid gt ring in order the matched prediction is
+ *      the first argmax over the image's valid predictions; the pair counts when that box IoU is > 0.5.
+ *   4  POLIS of a pair (A = gt, B = prediction): side(A, B) = (sum over the n vertices a of A of d(a, ring B)) / (2 (n + 1)), d the least point-to-segment
+ *      distance over B's n_B edges, the closing one included (t = clamp(((a - p).(q - p)) / |q - p|^2, 0, 1), d = |a - (p + t (q - p))|; a zero-length
+ *      edge is the point p); polis = side(A, B) + side(B, A).
+ *   5  samples of a ring: for each edge (p, q) in order, the closing edge last, L = sqrt(dx dx + dy dy), m = max(1, ceil(L / 0.1)) and the samples
+ *      p + ((j (L / m)) / L) (q - p), j = 0 .. m-1 (p once when L == 0); behind the last edge the first vertex once more.
+ *   6  chamfer and Hausdorff of a pair: S_A, S_B the samples, d1[i] = min_j |S_A[i] - S_B[j]|, d2 the other way round; chamfer = (mean d1 + mean d2) / 2,
+ *      hausdorff = max(max d1, max d2).
+ *   7  an image without a counted pair is not valid; else its three figures are the means over its counted pairs in gt order.  POLIS, chamfer and
+ *      hausdorff are the means over the valid images in image order, NaN when there is none.
+ * modes: P3_PM_IOU (steps 1-2), P3_PM_POLIS (step 4), P3_PM_SAMPLES (steps 5-6), any non-empty set; what a mode that is off would give is NaN (image_iou, image_nr
+ * and metrics[0..2]; pair_polis, image_polis and metrics[3]; the chamfer and hausdorff outputs; image_counts: 0).  match, image_valid and invalid_rings do not depend on modes.
+ * Outputs: metrics fp64 [6] = (IoU, C-IoU, NR, POLIS, chamfer, hausdorff); image_iou, image_nr, image_polis, image_chamfer, image_hausdorff fp64 [B] (NaN
+ * for the last three where the image is not valid); image_valid int32 [B]; image_counts int32 [B,2] = (I, U); match int32 [R_gt]: the index of the matched
+ * ring in the prediction set, -1 when the gt ring has no counted pair; pair_polis, pair_chamfer, pair_hausdorff fp64 [R_gt], NaN where match is -1;
+ * invalid_rings int32 [B,2] = (gt, dt); status int32 [1].
+ * Errors before any launch, P3_EINVAL with a message: negative counts, B, H or W < 1, H W above 2^18 (both bit-packed masks of an image are held in LDS),
+ * an empty or unknown modes, null pointers, and ring_slice / ring_image in host memory.
+ * Launches depend on the shapes and modes only; no floating-point atomics, no host synchronisation; two runs, an image alone or inside a batch give the
+ * same bits.  workspace: p3_polygon_metrics_workspace_bytes(R_gt, R_dt, B) bytes (0 for B < 1 or a negative count).
+ * ------------------------------------------------------------------------------------------ */
+#define P3_PM_IOU 1
+#define P3_PM_POLIS 2
+#define P3_PM_SAMPLES 4
+int p3_polygon_metrics(const float* gt_pos, int64_t V_gt, const int64_t* gt_slice, const int32_t* gt_image, int R_gt, const float* dt_pos, int64_t V_dt,
+                       const int64_t* dt_slice, const int32_t* dt_image, int R_dt, int B, int H, int W, int modes, double* metrics, double* image_iou,
+                       double* image_nr, double* image_polis, double* image_chamfer, double* image_hausdorff, int32_t* image_valid, int32_t* image_counts,
+                       int32_t* match, double* pair_polis, double* pair_chamfer, double* pair_hausdorff, int32_t* invalid_rings, int32_t* status,
+                       void* workspace, void* stream);
+int64_t p3_polygon_metrics_workspace_bytes(int R_gt, int R_dt, int B);
+
 #ifdef __cplusplus
 }
 #endif

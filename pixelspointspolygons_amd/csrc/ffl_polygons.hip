@@ -661,15 +661,6 @@ extern "C" int64_t p3_ffl_polygons_workspace_bytes(int64_t V, int B) {
     return c.at;
 }
 
-// the array can be read by the host (no device allocation, or no device at all): its values are checked here and the call is refused either way
-static bool ffp_host_array(const void* p) {
-    hipPointerAttribute_t a;
-    memset(&a, 0, sizeof a);
-    const hipError_t e = hipPointerGetAttributes(&a, p);
-    if (e != hipSuccess) { (void)hipGetLastError(); return true; }
-    return a.type != hipMemoryTypeDevice && a.type != hipMemoryTypeManaged && a.type != hipMemoryTypeArray;
-}
-
 extern "C" int p3_ffl_polygons(const float* out_pos, int64_t V, const int64_t* piece_slice, const int32_t* piece_batch, int Q, const float* indicator, int B, int H,
                                int W, double min_area, double seg_threshold, int force_fallback, int max_polygons, int max_rings, int max_vertices,
                                float* ring_pos, int64_t* ring_slice, int64_t* poly_rings, int32_t* poly_batch, float* poly_area, float* poly_prob,
@@ -680,10 +671,11 @@ extern "C" int p3_ffl_polygons(const float* out_pos, int64_t V, const int64_t* p
     P3_CHECK(min_area == min_area && seg_threshold == seg_threshold, P3_EINVAL, "p3_ffl_polygons: a threshold is NaN (min_area, seg_threshold)");
     P3_CHECK(image_status && counts && status, P3_EINVAL, "p3_ffl_polygons: null pointer (image_status, counts, status)");
     P3_CHECK(Q == 0 || (piece_slice && piece_batch && out_pos), P3_EINVAL, "p3_ffl_polygons: null pointer (out_pos, piece_slice, piece_batch)");
-    if (Q > 0 && (ffp_host_array(piece_slice) || ffp_host_array(piece_batch))) {
-        if (ffp_host_array(piece_batch))
+    // host arrays: their values are checked here and the call is refused either way
+    if (Q > 0 && (p3_host_array(piece_slice) || p3_host_array(piece_batch))) {
+        if (p3_host_array(piece_batch))
             for (int q = 0; q < Q; ++q) P3_CHECK(piece_batch[q] >= 0 && piece_batch[q] < B, P3_EINVAL, "p3_ffl_polygons: piece_batch out of [0, B)");
-        if (ffp_host_array(piece_slice))
+        if (p3_host_array(piece_slice))
             for (int q = 0; q < Q; ++q)
                 P3_CHECK(piece_slice[2 * q] >= 0 && piece_slice[2 * q] <= piece_slice[2 * q + 1] && piece_slice[2 * q + 1] <= V, P3_EINVAL,
                          "p3_ffl_polygons: a piece_slice row lies outside out_pos [0, V]");

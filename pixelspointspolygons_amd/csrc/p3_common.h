@@ -237,6 +237,14 @@ static inline int p3_hip_status(hipError_t e) {
     if (e != hipSuccess) p3_set_error(hipGetErrorString(e));
     return (int)e;
 }
+// the array can be read by the host (no device allocation, or no device at all): the polygon stages refuse such index arrays, which their kernels would follow
+static inline bool p3_host_array(const void* p) {
+    hipPointerAttribute_t a;
+    memset(&a, 0, sizeof a);
+    const hipError_t e = hipPointerGetAttributes(&a, p);
+    if (e != hipSuccess) { (void)hipGetLastError(); return true; }
+    return a.type != hipMemoryTypeDevice && a.type != hipMemoryTypeManaged && a.type != hipMemoryTypeArray;
+}
 static inline int p3_memset(void* p, int byte, int64_t bytes, hipStream_t s) { return p3_hip_status(hipMemsetAsync(p, byte, (size_t)bytes, s)); }
 // a step that returns such a status - p3_launch, p3_memset: the first one that fails ends the entry point with its code
 #define P3_TRY(status)                     \

@@ -1,0 +1,117 @@
+"""Polygon metrics on the device: the figures of the reference's `Evaluator.evaluate` that depend only on the predicted and the ground-truth polygons and
+the image size - IoU, C-IoU and NR (eval/cIoU.py) and POLIS, chamfer and Hausdorff (eval/polis_chamfer_hausdorff.py, IoU threshold 0.5, sampling distance
+0.1) - from packed rings to the six means in p3_polygon_metrics (csrc/poly_metrics.hip; the definition is in include/p3hip.h and DESIGN.md section 21).
+
+A ring set is a dict(pos fp32 [V,2] in (x, y) order, ring_slice int64 [R,2], ring_image int32 [R] non-decreasing, batch_size): open exterior rings.
+`pack_rings` builds one from per-image lists; `rings_from_ffl`, `rings_from_hisup` and `rings_from_pix2poly` build one from what the three models return.
+`polygon_metrics(pred, gt, height, width)` scores a batch with one read-back.  There is no CPU path: host tensors raise hip.P3Error.
+
+Host synchronisations: `polygon_metrics` has one, its read-back.  `rings_from_ffl` and `rings_from_hisup` (device dict) each select the kept rings with a
+boolean mask, which makes torch read the number of kept rings back once per indexed tensor (two per call); no coordinate, slice or flag reaches the host.
+`pack_rings` and `rings_from_pix2poly` start from host lists and upload."""
+import numpy as np
+import torch
+
+from . import hip
+
+MODES = {"iou": hip.PM_IOU, "polis": hip.PM_POLIS, "chamfer": hip.PM_SAMPLES, "hausdorff": hip.PM_SAMPLES}
+KEYS = ("IoU", "C-IoU", "NR", "POLIS", "chamfer", "hausdorff")
+
+
+def pack_rings(polygons_batch, device):
+    """per image a list of [n, 2] (x, y) arrays (numpy, torch or nested lists) -> ring set on `device`.  A closing duplicate of the first vertex is dropped;
+    rings keep their order, images too.  One upload per field (polygon_metrics refuses a ring set packed onto the host)."""
+    pos, sl, img, at = [], [], [], 0
+    for b, polygons in enumerate(polygons_batch):
+        for poly in polygons:
+            p = poly.detach().cpu().numpy() if torch.is_tensor(poly) else np.asarray(poly)
+            p = p.astype(np.float32).reshape(-1, 2)
+            if len(p) > 1 and np.array_equal(p[0], p[-1]):
+                p = p[:-1]
+            pos.append(p)
+            sl.append((at, at + len(p)))
+            img.append(b)
+            at += len(p)
+    return {"pos": torch.from_numpy(np.concatenate(pos) if pos else np.zeros((0, 2), np.float32)).to(device),
+            "ring_slice": torch.tensor(sl, dtype=torch.int64).reshape(-1, 2).to(device), "ring_image": torch.tensor(img, dtype=torch.int32).to(device),
+            "batch_size": len(polygons_batch)}
+
+
+def _open_rings(pos, ring_slice):
+    """closed rings (first vertex again at the end) -> the same slices without the closing vertex, on the device"""
+    first, last = ring_slice[:, 0], ring_slice[:, 1] - 1
+    n = ring_slice[:, 1] - ring_slice[:, 0]
+    safe = pos.shape[0] - 1
+    closed = (n > 1) & (pos[first.clamp(0, safe)] == pos[last.clamp(0, safe)]).all(dim=1) if pos.shape[0] else torch.zeros_like(n, dtype=torch.bool)
+    return torch.stack([ring_slice[:, 0], ring_slice[:, 1] - closed.to(ring_slice.dtype)], dim=1)
+
+
+def rings_from_ffl(result):
+    """the dict of polygonize_post.polygons_from_pieces / polygonize_acm_polygons / polygonize_asm_polygons -> ring set: the shells of the polygons no
+    filter flagged (poly_flags == 0), (row, col) flipped to (x, y), the closing vertex dropped.  The coordinates stay on the device; selecting the kept
+    polygons by a boolean mask synchronises with the host twice (poly_rings[keep], poly_batch[keep]: torch reads the number of kept polygons)."""
+    if "ring_pos" not in result:
+        raise hip.P3Error("rings_from_ffl: one polygon dict expected (pick a tolerance of a 'tol_{}' dict first)")
+    hip._dev(result["ring_pos"])
+    keep = result["poly_flags"] == 0
+    shell = result["poly_rings"][keep][:, 0]
+    pos = result["ring_pos"].flip(1).contiguous()
+    return {"pos": pos, "ring_slice": _open_rings(pos, result["ring_slice"][shell]), "ring_image": result["poly_batch"][keep].to(torch.int32),
+            "batch_size": int(result["batch_size"])}
+
+
+def rings_from_hisup(output, device=None):
+    """the output of HiSup `forward_val_device(polygons=True)` (device dict output["polygons"]: pos (x, y), poly_slice [B,R,2], poly_flags [B,R]; regions'
+    n_regions [B]) -> ring set of the outer polygons that exist (poly_flags bit 2 clear), the closing vertex dropped, without a copy of the coordinates.
+    Selecting those polygons by a boolean mask synchronises with the host twice (poly_slice[keep], image[keep]: torch reads their number).
+    The host form of `forward_val(polygons=True)` (`polys_pred`, with `poly_parts` when inner rings were built) is packed onto `device`."""
+    if "polygons" in output:
+        pg, n_regions = output["polygons"], output["regions"]["n_regions"]
+        hip._dev(pg["pos"])
+        B, R = pg["poly_flags"].shape
+        keep = (torch.arange(R, device=n_regions.device)[None, :] < n_regions[:, None]) & ((pg["poly_flags"] & 4) == 0)
+        image = torch.arange(B, device=n_regions.device, dtype=torch.int32)[:, None].expand(B, R)
+        return {"pos": pg["pos"], "ring_slice": _open_rings(pg["pos"], pg["poly_slice"][keep]), "ring_image": image[keep], "batch_size": B}
+    if "polys_pred" not in output:
+        raise hip.P3Error("rings_from_hisup: the output of forward_val_device(polygons=True) or of forward_val(polygons=True) expected")
+    if device is None:
+        raise hip.P3Error("rings_from_hisup: the host lists of forward_val need the device to pack them onto (there is no CPU path)")
+    parts = output.get("poly_parts")
+    outer = [[p[:parts[b][i][0]] if parts is not None else p for i, p in enumerate(polys)] for b, polys in enumerate(output["polys_pred"])]
+    return pack_rings(outer, device)
+
+
+def rings_from_pix2poly(polygons, device):
+    """the per-tile lists of [n, 2] (x, y) tensors `postprocess.batch_to_polygons` returns (host tensors: the permutation decoding ends there) -> ring set"""
+    return pack_rings(polygons, device)
+
+
+def _fields(rings, name):
+    try:
+        return rings["pos"], rings["ring_slice"], rings["ring_image"], int(rings["batch_size"])
+    except (KeyError, TypeError, IndexError):
+        raise hip.P3Error(f"polygon_metrics: {name} is not a ring set (pos, ring_slice, ring_image, batch_size): see pack_rings") from None
+
+
+def polygon_metrics(pred, gt, height, width, modes=("iou", "polis", "chamfer", "hausdorff"), out=None):
+    """pred, gt: ring sets of the same batch.  -> dict with the reference's keys "IoU", "C-IoU", "NR", "POLIS", "chamfer", "hausdorff" as Python floats (NaN
+    for a mode left out, and for the last three when no image has a counted pair), "status" (int; bit 0 an invalid ring, bit 1 a ring left out), and the
+    device tensors "per_image" (iou, nr, polis, chamfer, hausdorff, valid, counts = (I, U), invalid_rings) and "pairs" (match, polis, chamfer, hausdorff
+    per gt ring).  One read-back: the six means and the status."""
+    dp, ds, di, B = _fields(pred, "pred")
+    gp, gs, gi, Bg = _fields(gt, "gt")
+    if B != Bg:
+        raise hip.P3Error(f"polygon_metrics: pred holds {B} images, gt {Bg}")
+    bits = 0
+    for m in modes:
+        if m not in MODES:
+            raise hip.P3Error(f"polygon_metrics: unknown mode {m!r}; the modes are {sorted(MODES)}")
+        bits |= MODES[m]
+    o = hip.polygon_metrics_device(gp, gs, gi, dp, ds, di, B, height, width, bits, out=out)
+    *means, status = torch.cat([o["metrics"], o["status"].to(torch.float64)]).tolist()
+    res = dict(zip(KEYS, means))
+    res["status"] = int(status)
+    res["per_image"] = {"iou": o["image_iou"], "nr": o["image_nr"], "polis": o["image_polis"], "chamfer": o["image_chamfer"],
+                        "hausdorff": o["image_hausdorff"], "valid": o["image_valid"], "counts": o["image_counts"], "invalid_rings": o["invalid_rings"]}
+    res["pairs"] = {"match": o["match"], "polis": o["pair_polis"], "chamfer": o["pair_chamfer"], "hausdorff": o["pair_hausdorff"]}
+    return res

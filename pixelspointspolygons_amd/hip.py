@@ -1504,6 +1504,66 @@ def ffl_polygons(out_pos, piece_slice, piece_batch, indicator, min_area, seg_thr
                       dict(ring_pos=2, ring_slice=1, poly_rings=0, poly_batch=0, poly_area=0, poly_prob=0, poly_flags=0))
 
 
+# ------------------------------------------------------------------------------------------ polygon metrics: IoU / C-IoU / NR, POLIS, chamfer, Hausdorff
+PM_IOU, PM_POLIS, PM_SAMPLES = 1, 2, 4          # include/p3hip.h P3_PM_*
+PM_MAX_HW = 1 << 18        # csrc/poly_metrics.hip: pixels of one image whose two bit-packed masks are held in LDS
+PM_EDGE_CHUNK = 32         # edges of a ring staged through LDS at a time
+PM_TILE = 1024             # samples of a ring in LDS at a time
+
+
+def _ring_set(who, name, pos, ring_slice, ring_image):
+    for t in (pos, ring_slice, ring_image):
+        _dev(t)
+    if pos.dtype != torch.float32 or pos.dim() != 2 or pos.shape[1] != 2:
+        raise P3Error(f"{who}: {name} pos must be float32 [V, 2], got {pos.dtype} {tuple(pos.shape)}")
+    R = ring_slice.shape[0]
+    if ring_slice.dim() != 2 or ring_slice.shape[1] != 2 or ring_image.dim() != 1 or ring_image.shape[0] != R or ring_slice.dtype.is_floating_point \
+            or ring_image.dtype.is_floating_point:
+        raise P3Error(f"{who}: integer {name} ring_slice [R, 2] and ring_image [R] expected, got {ring_slice.dtype} {tuple(ring_slice.shape)}, "
+                      f"{ring_image.dtype} {tuple(ring_image.shape)}")
+    # converted copies stay referenced until the launch is queued
+    return pos.contiguous(), ring_slice.to(torch.int64).contiguous(), ring_image.to(torch.int32).contiguous()
+
+
+def polygon_metrics_workspace_bytes(R_gt, R_dt, B):
+    """bytes of workspace p3_polygon_metrics takes for R_gt ground-truth rings and R_dt predicted rings in B images: 24 bytes of state, vertex count, first vertex
+    and 32 of box per ring, each section rounded up to 256"""
+    return int(lib().p3_polygon_metrics_workspace_bytes(int(R_gt), int(R_dt), int(B)))
+
+
+def polygon_metrics_device(gt_pos, gt_slice, gt_image, dt_pos, dt_slice, dt_image, batch_size, height, width, modes=PM_IOU | PM_POLIS | PM_SAMPLES, out=None):
+    """p3_polygon_metrics (IoU / C-IoU / NR of the rasterised ring sets, POLIS, chamfer and Hausdorff of the matched pairs; include/p3hip.h, DESIGN.md
+    section 21) without any synchronisation.  A ring set: pos fp32 [V,2] (x, y), ring_slice [R,2], ring_image [R] non-decreasing; open exterior rings.
+    gt_*: the ground truth, dt_*: the predictions.  modes: PM_IOU | PM_POLIS | PM_SAMPLES; the figures of a mode that is off are NaN (image_iou and image_nr, the pair_* and image_* of POLIS, of chamfer and
+    Hausdorff; image_counts 0), match, image_valid and invalid_rings are always computed.
+    -> dict(metrics f64 [6] = (IoU, C-IoU, NR, POLIS, chamfer, hausdorff), image_iou, image_nr, image_polis, image_chamfer, image_hausdorff f64 [B],
+    image_valid i32 [B], image_counts i32 [B,2] = (I, U), match i32 [R_gt] (index into the predictions, -1: no counted pair), pair_polis, pair_chamfer,
+    pair_hausdorff f64 [R_gt] (NaN where match is -1), invalid_rings i32 [B,2] = (gt, dt), status i32 [1] (bit 0: an invalid ring - fewer than 3 vertices, a
+    coordinate not finite or beyond +-32768; bit 1: a ring with ring_image outside [0, B) or a slice outside pos was left out)).
+    out: the caller's own tensors for any of the outputs (`_outputs`)."""
+    gp, gs, gi = _ring_set("polygon_metrics", "gt", gt_pos, gt_slice, gt_image)
+    dp, ds, di = _ring_set("polygon_metrics", "dt", dt_pos, dt_slice, dt_image)
+    B, H, W, modes = int(batch_size), int(height), int(width), int(modes)
+    if B < 1 or H < 1 or W < 1 or H * W > PM_MAX_HW:
+        raise P3Error(f"polygon_metrics: batch_size, height, width >= 1 and height * width <= {PM_MAX_HW} expected, got {B}, {H}, {W}")
+    if modes < 1 or modes & ~(PM_IOU | PM_POLIS | PM_SAMPLES):
+        raise P3Error(f"polygon_metrics: modes = {modes} is not a non-empty set of PM_IOU | PM_POLIS | PM_SAMPLES")
+    Rg, Rd = gs.shape[0], ds.shape[0]
+    dev, f64, i32 = gp.device, torch.float64, torch.int32
+    out = _outputs("polygon_metrics", dev, (("metrics", (6,), f64), ("image_iou", (B,), f64), ("image_nr", (B,), f64), ("image_polis", (B,), f64),
+                                            ("image_chamfer", (B,), f64), ("image_hausdorff", (B,), f64), ("image_valid", (B,), i32),
+                                            ("image_counts", (B, 2), i32), ("match", (Rg,), i32), ("pair_polis", (Rg,), f64), ("pair_chamfer", (Rg,), f64),
+                                            ("pair_hausdorff", (Rg,), f64), ("invalid_rings", (B, 2), i32), ("status", (1,), i32)), out)
+    ws = workspace(polygon_metrics_workspace_bytes(Rg, Rd, B), dev, "polygon_metrics")
+    o = lambda k: ptr(out[k] if out[k].numel() else None)
+    check(lib().p3_polygon_metrics(ptr(gp if Rg else None), gp.shape[0], ptr(gs if Rg else None), ptr(gi if Rg else None), Rg,
+                                   ptr(dp if Rd else None), dp.shape[0], ptr(ds if Rd else None), ptr(di if Rd else None), Rd, B, H, W, modes,
+                                   o("metrics"), o("image_iou"), o("image_nr"), o("image_polis"), o("image_chamfer"), o("image_hausdorff"), o("image_valid"),
+                                   o("image_counts"), o("match"), o("pair_polis"), o("pair_chamfer"), o("pair_hausdorff"), o("invalid_rings"), o("status"),
+                                   ptr(ws), stream()), "p3_polygon_metrics")
+    return out
+
+
 # ------------------------------------------------------------------------------------------ FFL active-skeleton optimiser
 ASM_LDS_CAP = 4096         # csrc/asm.hip: nodes of one connected component that fit the one-launch LDS path
 FFL_POLY_LDS_CAP = 1024    # csrc/ffl_polygons.hip: edge slots of one image (its segments + its segment ends on the border + 4) that run in LDS
