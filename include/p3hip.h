@@ -1135,6 +1135,59 @@ int p3_polygon_metrics(const float* gt_pos, int64_t V_gt, const int64_t* gt_slic
                        void* workspace, void* stream);
 int64_t p3_polygon_metrics_workspace_bytes(int R_gt, int R_dt, int B);
 
+/* ------------------------------------------------------------------------------------------
+ * COCO AP / AR of a predicted ring set against a ground-truth ring set, on instance masks (segm) and on their boundaries (boundary): the reference's
+ * Evaluator.compute_coco_metrics (pycocotools COCOeval, iouType 'segm', one category) and compute_boundary_coco_metrics (boundary-iou-api), on the device
+ * (csrc/coco_metrics.hip).  Neither library is linked: the text below and its float64 / integer restatement tests/coco_metrics_ref.py are the contract,
+ * DESIGN.md section 22 says where the text knowingly differs from those libraries.
+ * Input: two ring sets as for p3_polygon_metrics (pos, ring_slice, ring_image non-decreasing; open exterior rings), with one optional fp32 [R] field each:
+ * dt_score, the prediction's score (null: every score is 1.0), and gt_area, the annotation's area that sorts a gt ring into the size buckets (null: the
+ * ring's own pixel count).  Ring validity, status bits 0 and 1 and the bound H W <= 2^18 are those of p3_polygon_metrics; a prediction whose score is NaN
+ * is invalid (bit 0).  Counts are integers, quotients are doubles of those integers, every operation rounded on its own.
+ *   1  instance mask: the pixels (r, c) of the H x W image whose centre (c + 0.5, r + 0.5) lies in the ring by the even-odd crossing rule of
+ *      p3_polygon_metrics step 1, for this ring alone; area_px is its pixel count.  The area of a prediction is area_px, that of a gt ring gt_area or area_px.
+ *   2  boundary mask: d = max(1, (int)rint(0.02 sqrt(H H + W W))), rint rounding half to even; the eroded mask keeps a pixel when every pixel of the
+ *      (2d+1) x (2d+1) square around it is in the mask, pixels outside the image counting as not in it; the boundary is the mask minus the eroded mask.
+ *   3  pair IoU, per image, between every valid gt ring and the image's kept predictions - its valid predictions in stable order of descending score, the
+ *      first 100: I the common pixels, U = a + b - I, iou = 0 when U == 0, else (double)I / (double)U.  For boundary the IoU of a pair is the smaller of
+ *      its mask IoU and the IoU of the two boundary masks.
+ *   4  tables: iouThrs = linspace(0.5, 0.95, 10) and recThrs = linspace(0, 1, 101) as numpy's doubles (p3_coco_thresholds); area ranges [0, 1e10],
+ *      [0, 1024], [1024, 9216], [9216, 1e10]; maxDets 1, 10, 100.
+ *   5  matching (evaluateImg, no crowd) per image, area range a and threshold t: a gt ring is ignored when its area is < lo or > hi; the gt rings are
+ *      visited in stable order of that flag, not-ignored first.  The kept predictions are visited in order; for each the running best starts at
+ *      min(t, 1 - 1e-10) with no match; walking the gt rings, one already matched at this (a, t) is skipped, the walk stops at the first ignored gt ring
+ *      once a not-ignored match is held, a gt ring whose IoU is less than the running best is skipped (equality matches), any other is taken and raises the
+ *      running best to its IoU.  A matched prediction inherits the ignore flag of its gt ring; an unmatched one is ignored when its own area lies outside
+ *      the range.  The matching for maxDets 1 and 10 is the prefix of the one for 100.
+ *   6  accumulation (accumulate) per (a, m): the first m kept predictions of every image, in image order, ordered stably by descending score; npig the
+ *      number of not-ignored gt rings - 0 leaves -1 in the (a, m) entries of precision and recall; tp, fp the integer prefix counts of the not-ignored
+ *      matched and unmatched predictions; per t, with nd predictions: rc = tp / npig, pr = tp / (fp + tp + 2^-52), recall[t, a, m] = rc[nd-1] (0 when
+ *      nd == 0), pr made non-increasing from the right, precision[t, r, a, m] = pr[first i with rc[i] >= recThrs[r]] (0 when there is none).
+ *   7  stats (summarize), 12 per type in pycocotools' order - AP, AP50, AP75, AP small, medium, large (maxDets 100), AR at maxDets 1, 10, 100 (all areas),
+ *      AR small, medium, large (maxDets 100): the mean, summed in index order, over the entries > -1; -1 when there is none.
+ * iou_types: P3_COCO_SEGM | P3_COCO_BOUNDARY, any non-empty set.  A type that is off leaves NaN in its row of stats, precision and recall, -1 in its rows of
+ * dt_match and gt_match and 0 in its rows of dt_ignore; without P3_COCO_BOUNDARY no boundary is built: gt_boundary_px, dt_boundary_px and row 1 of
+ * pair_inter hold 0.  The areas, dt_rank and row 0 of pair_inter do not depend on iou_types.
+ * Outputs: stats fp64 [2,12] (row 0 segm, row 1 boundary); precision fp64 [2,10,101,4,3]; recall fp64 [2,10,4,3]; gt_area_px, gt_boundary_px int32 [R_gt],
+ * dt_area_px, dt_boundary_px int32 [R_dt] (0 for a ring that is not valid); dt_rank int32 [R_dt]: the position among its image's kept predictions, -1 when
+ * not kept; pair_inter int32 [2, 100 R_gt]: I of gt ring g and the prediction of rank k at 100 g + k (0 where no kept prediction has that rank, and where
+ * the masks do not overlap); dt_match int32 [2,4,10,R_dt]: the gt ring index or -1; dt_ignore uint8 of that shape; gt_match int32 [2,4,10,R_gt]: the
+ * prediction's ring index or -1; status int32 [1].
+ * Errors before any launch, P3_EINVAL with a message: those of p3_polygon_metrics, an empty or unknown iou_types, dt_score / gt_area in host memory.
+ * Launches depend on the shapes and iou_types only; no floating-point atomics, no host synchronisation; two runs, an image alone or inside a batch give the
+ * same bits in every per-ring and per-pair output.  workspace: p3_coco_metrics_workspace_bytes(R_gt, R_dt, B, H, W, iou_types) bytes (0 for arguments
+ * the entry refuses).  p3_coco_thresholds (host only) copies the two threshold tables out; either pointer may be null.
+ * ------------------------------------------------------------------------------------------ */
+#define P3_COCO_SEGM 1
+#define P3_COCO_BOUNDARY 2
+int p3_coco_metrics(const float* gt_pos, int64_t V_gt, const int64_t* gt_slice, const int32_t* gt_image, const float* gt_area, int R_gt,
+                    const float* dt_pos, int64_t V_dt, const int64_t* dt_slice, const int32_t* dt_image, const float* dt_score, int R_dt, int B, int H, int W,
+                    int iou_types, double* stats, double* precision, double* recall, int32_t* gt_area_px, int32_t* dt_area_px, int32_t* gt_boundary_px,
+                    int32_t* dt_boundary_px, int32_t* dt_rank, int32_t* pair_inter, int32_t* dt_match, uint8_t* dt_ignore, int32_t* gt_match, int32_t* status,
+                    void* workspace, void* stream);
+int64_t p3_coco_metrics_workspace_bytes(int R_gt, int R_dt, int B, int H, int W, int iou_types);
+void p3_coco_thresholds(double* iou10, double* rec101);
+
 #ifdef __cplusplus
 }
 #endif

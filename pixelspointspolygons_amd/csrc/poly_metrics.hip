@@ -7,32 +7,14 @@
 //   pm_finish_kernel   one workgroup: per-image figures, then the six means in image order
 // Every floating-point value is a double made of the fp32 coordinates; contraction is off for the whole file, so that a product and the sum behind it round as
 // the float64 restatement (tests/poly_metrics_ref.py) rounds them: sample counts, crossings and the argmax are then the restatement's.
-#include "p3_common.h"
+#include "pm_rings.h"          // the ring set, ring validity and the crossing rule, shared with coco_metrics.hip
 
 #pragma clang fp contract(off)
 
-constexpr int PM_THREADS = 256;
-constexpr int PM_EDGE_CHUNK = 32;          // edges of a ring staged through LDS at a time (raster: their end points; pair: their sample counts, prefix-summed)
 constexpr int PM_OWN = 4;                  // samples a thread owns in registers
 constexpr int PM_TILE = PM_THREADS * PM_OWN;          // samples of the other ring in LDS at a time, and the samples the workgroup owns at a time
 constexpr double PM_STEP = 0.1;            // segmentize(0.1)
-constexpr double PM_MAX_COORD = 32768.0;   // a ring with a coordinate beyond it is invalid: per-edge sample counts stay far inside int32
-constexpr int64_t PM_MAX_HW = (int64_t)1 << 18;
 
-struct PmSet {
-    const float2* pos;
-    const int64_t* slice;
-    const int32_t* image;
-    int64_t V;
-    int R;
-};
-// per ring of one set (workspace): state 1 valid, 0 invalid (counted per image), -1 left out; n vertices from `first`; box = (min x, min y, w, h)
-struct PmRings {
-    int32_t* state;
-    int32_t* n;
-    int64_t* first;
-    double* box;          // [R, 4]
-};
 struct PmOut {
     double* metrics;
     double* image_iou;
@@ -50,53 +32,7 @@ struct PmOut {
     int32_t* status;
 };
 
-__device__ __forceinline__ double pm_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-// first index whose image is >= b: ring_image is non-decreasing, so the rings of image b are [pm_lower(b), pm_lower(b + 1))
-__device__ __forceinline__ int pm_lower(const int32_t* image, int R, int b) {
-    int lo = 0, hi = R;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (image[mid] < b) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // ---- rings ----------------------------------------------------------------------------------------------------------------------------------------------
-__device__ void pm_ring(const PmSet& s, const PmRings& w, int r, int B, int32_t* status) {
-    const int64_t a = s.slice[2 * r], e = s.slice[2 * r + 1];
-    const int img = s.image[r];
-    w.first[r] = 0;
-    w.n[r] = 0;
-    for (int k = 0; k < 4; ++k) w.box[4 * (int64_t)r + k] = 0.0;
-    if (img < 0 || img >= B || a < 0 || e < a || e > s.V || e - a >= ((int64_t)1 << 30)) {
-        w.state[r] = -1;
-        atomicOr(status, 2);
-        return;
-    }
-    const int n = (int)(e - a);
-    bool ok = n >= 3;
-    double x0 = 0, x1 = 0, y0 = 0, y1 = 0;
-    for (int i = 0; i < n && ok; ++i) {
-        const float2 p = s.pos[a + i];
-        const double x = (double)p.x, y = (double)p.y;
-        if (!(fabs(x) <= PM_MAX_COORD && fabs(y) <= PM_MAX_COORD)) ok = false;          // NaN and the infinities fail the comparison too
-        if (i == 0) { x0 = x1 = x; y0 = y1 = y; }
-        x0 = x < x0 ? x : x0; x1 = x > x1 ? x : x1;
-        y0 = y < y0 ? y : y0; y1 = y > y1 ? y : y1;
-    }
-    if (!ok) {
-        w.state[r] = 0;
-        atomicOr(status, 1);
-        return;
-    }
-    w.state[r] = 1;
-    w.n[r] = n;
-    w.first[r] = a;
-    double* box = w.box + 4 * (int64_t)r;
-    box[0] = x0; box[1] = y0; box[2] = x1 - x0; box[3] = y1 - y0;
-}
-
 __global__ __launch_bounds__(PM_THREADS) void pm_ring_kernel(PmSet gt, PmSet dt, PmRings wg, PmRings wd, int B, PmOut o) {
     const int r = blockIdx.x * PM_THREADS + threadIdx.x;
     if (r < gt.R) {
@@ -109,8 +45,6 @@ __global__ __launch_bounds__(PM_THREADS) void pm_ring_kernel(PmSet gt, PmSet dt,
 }
 
 // ---- masks, I and U -------------------------------------------------------------------------------------------------------------------------------------
-struct PmEdge { double ax, ay, bx, by; };
-
 // the rings of one set of image b into `mask` (bit r W + c of the packed words): the parity of each valid ring, ORed in
 __device__ void pm_raster_set(const PmSet& s, const PmRings& w, int b, int H, int W, uint32_t* mask, PmEdge* edges) {
     const int tid = threadIdx.x;
@@ -119,11 +53,8 @@ __device__ void pm_raster_set(const PmSet& s, const PmRings& w, int b, int H, in
         if (w.state[r] != 1) continue;          // uniform over the workgroup
         const int n = w.n[r];
         const int64_t first = w.first[r];
-        const double* box = w.box + 4 * (int64_t)r;
-        // rows and columns whose centres can lie inside: clamped in double before the conversion
-        const double fr0 = floor(box[1] - 0.5), fr1 = ceil(box[1] + box[3] - 0.5), fc0 = floor(box[0] - 0.5), fc1 = ceil(box[0] + box[2] - 0.5);
-        if (fr1 < 0.0 || fc1 < 0.0 || fr0 > (double)(H - 1) || fc0 > (double)(W - 1)) continue;
-        const int r0 = (int)fmax(fr0, 0.0), r1 = (int)fmin(fr1, (double)(H - 1)), c0 = (int)fmax(fc0, 0.0), c1 = (int)fmin(fc1, (double)(W - 1));
+        int r0, r1, c0, c1;          // rows and columns whose centres can lie inside
+        if (!pm_pixel_box(w.box + 4 * (int64_t)r, H, W, r0, r1, c0, c1)) continue;
         const int per_row = ((c1 - c0) >> 5) + 2;          // words a row's [c0, c1] can touch
         const int units = (r1 - r0 + 1) * per_row;
         for (int base = 0; base < units; base += PM_THREADS) {
@@ -138,23 +69,17 @@ __device__ void pm_raster_set(const PmSet& s, const PmRings& w, int b, int H, in
             for (int e0 = 0; e0 < n; e0 += PM_EDGE_CHUNK) {
                 const int cnt = n - e0 < PM_EDGE_CHUNK ? n - e0 : PM_EDGE_CHUNK;
                 __syncthreads();          // the last chunk has been read
-                if (tid < cnt) {
-                    const int i = e0 + tid, j = i + 1 == n ? 0 : i + 1;
-                    const float2 pa = s.pos[first + i], pb = s.pos[first + j];
-                    edges[tid] = {(double)pa.x, (double)pa.y, (double)pb.x, (double)pb.y};
-                }
+                pm_stage_edges(s.pos, first, n, e0, cnt, edges);
                 __syncthreads();
                 if (!active) continue;
                 for (int k = 0; k < cnt; ++k) {
                     const PmEdge ed = edges[k];
-                    if ((ed.ay <= py) == (ed.by <= py)) continue;          // not crossed by this row's centres
+                    if (!pm_crossed(ed, py)) continue;          // not crossed by this row's centres
                     const double ex = ed.bx - ed.ax, ey = ed.by - ed.ay, wy = py - ed.ay;
                     const double t1 = ex * wy;
                     for (int bit = lo; bit <= hi; ++bit) {
                         const double px = (double)(bit - row * W) + 0.5;
-                        const double cr = t1 - (px - ed.ax) * ey;
-                        const bool right = ey > 0.0 ? cr > 0.0 : cr < 0.0;
-                        if (right) parity ^= 1u << (bit & 31);
+                        if (pm_right_of(ed, t1, ey, px)) parity ^= 1u << (bit & 31);
                     }
                 }
             }
@@ -456,14 +381,6 @@ __global__ __launch_bounds__(PM_THREADS) void pm_finish_kernel(PmSet gt, int B, 
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------------------------------
 struct PmWs { PmRings gt, dt; };
-static PmRings pm_carve_set(int R, P3Carve& c) {
-    PmRings w;
-    w.state = c.take<int32_t>(R);
-    w.n = c.take<int32_t>(R);
-    w.first = c.take<int64_t>(R);
-    w.box = c.take<double>(4 * (int64_t)R);
-    return w;
-}
 static PmWs pm_carve(int R_gt, int R_dt, P3Carve& c) {
     PmWs l;
     l.gt = pm_carve_set(R_gt, c);

@@ -6,7 +6,12 @@ A ring set is a dict(pos fp32 [V,2] in (x, y) order, ring_slice int64 [R,2], rin
 `pack_rings` builds one from per-image lists; `rings_from_ffl`, `rings_from_hisup` and `rings_from_pix2poly` build one from what the three models return.
 `polygon_metrics(pred, gt, height, width)` scores a batch with one read-back.  There is no CPU path: host tensors raise hip.P3Error.
 
-Host synchronisations: `polygon_metrics` has one, its read-back.  `rings_from_ffl` and `rings_from_hisup` (device dict) each select the kept rings with a
+`coco_metrics(pred, gt, height, width)` gives the reference's COCO columns - AP, AP50, AP75, AP and AR by size, AR at 1, 10 and 100 detections
+(Evaluator.compute_coco_metrics) and the same on the boundaries of the masks (compute_boundary_coco_metrics) - from p3_coco_metrics (csrc/coco_metrics.hip,
+DESIGN.md section 22), with one read-back.  For it a ring set may carry "score" (predictions, fp32 [R]; missing: every score 1.0, which is what the
+reference's annotation writer puts) and "area" (ground truth, fp32 [R]: the annotation's area for the size buckets; missing: the ring's pixel count).
+
+Host synchronisations: `polygon_metrics` and `coco_metrics` have one each, the read-back.  `rings_from_ffl` and `rings_from_hisup` (device dict) each select the kept rings with a
 boolean mask, which makes torch read the number of kept rings back once per indexed tensor (two per call); no coordinate, slice or flag reaches the host.
 `pack_rings` and `rings_from_pix2poly` start from host lists and upload."""
 import numpy as np
@@ -16,11 +21,22 @@ from . import hip
 
 MODES = {"iou": hip.PM_IOU, "polis": hip.PM_POLIS, "chamfer": hip.PM_SAMPLES, "hausdorff": hip.PM_SAMPLES}
 KEYS = ("IoU", "C-IoU", "NR", "POLIS", "chamfer", "hausdorff")
+IOU_TYPES = {"segm": hip.COCO_SEGM, "boundary": hip.COCO_BOUNDARY}
+COCO_KEYS = ("AP", "AP50", "AP75", "AP_small", "AP_medium", "AP_large", "AR1", "AR10", "AR100", "AR_small", "AR_medium", "AR_large")
 
 
-def pack_rings(polygons_batch, device):
+def _per_ring(values, polygons_batch, name):
+    """per image a list of one number per ring -> float32 [R]"""
+    flat = [float(v) for per_image in values for v in per_image]
+    if len(values) != len(polygons_batch) or [len(v) for v in values] != [len(p) for p in polygons_batch]:
+        raise hip.P3Error(f"pack_rings: {name} must hold one number per ring, image by image")
+    return torch.tensor(flat, dtype=torch.float32)
+
+
+def pack_rings(polygons_batch, device, scores=None, areas=None):
     """per image a list of [n, 2] (x, y) arrays (numpy, torch or nested lists) -> ring set on `device`.  A closing duplicate of the first vertex is dropped;
-    rings keep their order, images too.  One upload per field (polygon_metrics refuses a ring set packed onto the host)."""
+    rings keep their order, images too.  One upload per field (polygon_metrics refuses a ring set packed onto the host).  scores / areas: per image a list
+    of one number per ring -> the "score" / "area" field (coco_metrics)."""
     pos, sl, img, at = [], [], [], 0
     for b, polygons in enumerate(polygons_batch):
         for poly in polygons:
@@ -32,9 +48,14 @@ def pack_rings(polygons_batch, device):
             sl.append((at, at + len(p)))
             img.append(b)
             at += len(p)
-    return {"pos": torch.from_numpy(np.concatenate(pos) if pos else np.zeros((0, 2), np.float32)).to(device),
-            "ring_slice": torch.tensor(sl, dtype=torch.int64).reshape(-1, 2).to(device), "ring_image": torch.tensor(img, dtype=torch.int32).to(device),
-            "batch_size": len(polygons_batch)}
+    rings = {"pos": torch.from_numpy(np.concatenate(pos) if pos else np.zeros((0, 2), np.float32)).to(device),
+             "ring_slice": torch.tensor(sl, dtype=torch.int64).reshape(-1, 2).to(device), "ring_image": torch.tensor(img, dtype=torch.int32).to(device),
+             "batch_size": len(polygons_batch)}
+    if scores is not None:
+        rings["score"] = _per_ring(scores, polygons_batch, "scores").to(device)
+    if areas is not None:
+        rings["area"] = _per_ring(areas, polygons_batch, "areas").to(device)
+    return rings
 
 
 def _open_rings(pos, ring_slice):
@@ -46,32 +67,42 @@ def _open_rings(pos, ring_slice):
     return torch.stack([ring_slice[:, 0], ring_slice[:, 1] - closed.to(ring_slice.dtype)], dim=1)
 
 
-def rings_from_ffl(result):
+def rings_from_ffl(result, unit_scores=False):
     """the dict of polygonize_post.polygons_from_pieces / polygonize_acm_polygons / polygonize_asm_polygons -> ring set: the shells of the polygons no
     filter flagged (poly_flags == 0), (row, col) flipped to (x, y), the closing vertex dropped.  The coordinates stay on the device; selecting the kept
-    polygons by a boolean mask synchronises with the host twice (poly_rings[keep], poly_batch[keep]: torch reads the number of kept polygons)."""
+    polygons by a boolean mask synchronises with the host twice (poly_rings[keep], poly_batch[keep]: torch reads the number of kept polygons).  "score" is
+    the kept polygons' poly_prob (torch sizes that selection from the count it already read); unit_scores=True leaves it out, so that every score is 1.0 as
+    in the reference's protocol."""
     if "ring_pos" not in result:
         raise hip.P3Error("rings_from_ffl: one polygon dict expected (pick a tolerance of a 'tol_{}' dict first)")
     hip._dev(result["ring_pos"])
     keep = result["poly_flags"] == 0
     shell = result["poly_rings"][keep][:, 0]
     pos = result["ring_pos"].flip(1).contiguous()
-    return {"pos": pos, "ring_slice": _open_rings(pos, result["ring_slice"][shell]), "ring_image": result["poly_batch"][keep].to(torch.int32),
-            "batch_size": int(result["batch_size"])}
+    rings = {"pos": pos, "ring_slice": _open_rings(pos, result["ring_slice"][shell]), "ring_image": result["poly_batch"][keep].to(torch.int32),
+             "batch_size": int(result["batch_size"])}
+    if not unit_scores and "poly_prob" in result:
+        rings["score"] = result["poly_prob"][keep].to(torch.float32)
+    return rings
 
 
-def rings_from_hisup(output, device=None):
+def rings_from_hisup(output, device=None, unit_scores=False):
     """the output of HiSup `forward_val_device(polygons=True)` (device dict output["polygons"]: pos (x, y), poly_slice [B,R,2], poly_flags [B,R]; regions'
     n_regions [B]) -> ring set of the outer polygons that exist (poly_flags bit 2 clear), the closing vertex dropped, without a copy of the coordinates.
     Selecting those polygons by a boolean mask synchronises with the host twice (poly_slice[keep], image[keep]: torch reads their number).
-    The host form of `forward_val(polygons=True)` (`polys_pred`, with `poly_parts` when inner rings were built) is packed onto `device`."""
+    The host form of `forward_val(polygons=True)` (`polys_pred`, with `poly_parts` when inner rings were built) is packed onto `device`.
+    "score" is the region score of the device dict (regions' score [B,R]) where it is there; unit_scores=True leaves it out, so that every score is 1.0 as in
+    the reference's protocol.  The host lists carry no score per polygon."""
     if "polygons" in output:
         pg, n_regions = output["polygons"], output["regions"]["n_regions"]
         hip._dev(pg["pos"])
         B, R = pg["poly_flags"].shape
         keep = (torch.arange(R, device=n_regions.device)[None, :] < n_regions[:, None]) & ((pg["poly_flags"] & 4) == 0)
         image = torch.arange(B, device=n_regions.device, dtype=torch.int32)[:, None].expand(B, R)
-        return {"pos": pg["pos"], "ring_slice": _open_rings(pg["pos"], pg["poly_slice"][keep]), "ring_image": image[keep], "batch_size": B}
+        rings = {"pos": pg["pos"], "ring_slice": _open_rings(pg["pos"], pg["poly_slice"][keep]), "ring_image": image[keep], "batch_size": B}
+        if not unit_scores and "score" in output["regions"]:
+            rings["score"] = output["regions"]["score"][keep].to(torch.float32)
+        return rings
     if "polys_pred" not in output:
         raise hip.P3Error("rings_from_hisup: the output of forward_val_device(polygons=True) or of forward_val(polygons=True) expected")
     if device is None:
@@ -81,16 +112,17 @@ def rings_from_hisup(output, device=None):
     return pack_rings(outer, device)
 
 
-def rings_from_pix2poly(polygons, device):
-    """the per-tile lists of [n, 2] (x, y) tensors `postprocess.batch_to_polygons` returns (host tensors: the permutation decoding ends there) -> ring set"""
+def rings_from_pix2poly(polygons, device, unit_scores=False):
+    """the per-tile lists of [n, 2] (x, y) tensors `postprocess.batch_to_polygons` returns (host tensors: the permutation decoding ends there) -> ring set.
+    The decoder gives no score per polygon, so the set carries none and every score is 1.0 with or without unit_scores (the keyword of the other two)."""
     return pack_rings(polygons, device)
 
 
-def _fields(rings, name):
+def _fields(rings, name, who="polygon_metrics"):
     try:
         return rings["pos"], rings["ring_slice"], rings["ring_image"], int(rings["batch_size"])
     except (KeyError, TypeError, IndexError):
-        raise hip.P3Error(f"polygon_metrics: {name} is not a ring set (pos, ring_slice, ring_image, batch_size): see pack_rings") from None
+        raise hip.P3Error(f"{who}: {name} is not a ring set (pos, ring_slice, ring_image, batch_size): see pack_rings") from None
 
 
 def polygon_metrics(pred, gt, height, width, modes=("iou", "polis", "chamfer", "hausdorff"), out=None):
@@ -114,4 +146,32 @@ def polygon_metrics(pred, gt, height, width, modes=("iou", "polis", "chamfer", "
     res["per_image"] = {"iou": o["image_iou"], "nr": o["image_nr"], "polis": o["image_polis"], "chamfer": o["image_chamfer"],
                         "hausdorff": o["image_hausdorff"], "valid": o["image_valid"], "counts": o["image_counts"], "invalid_rings": o["invalid_rings"]}
     res["pairs"] = {"match": o["match"], "polis": o["pair_polis"], "chamfer": o["pair_chamfer"], "hausdorff": o["pair_hausdorff"]}
+    return res
+
+
+def coco_metrics(pred, gt, height, width, iou_types=("segm", "boundary"), out=None):
+    """pred, gt: ring sets of the same batch; pred may carry "score", gt "area".  -> dict with the reference's keys "AP", "AP50", "AP75", "AP_small",
+    "AP_medium", "AP_large", "AR1", "AR10", "AR100", "AR_small", "AR_medium", "AR_large" as Python floats for the instance masks, the same keys under
+    "boundary" for boundary IoU (NaN for a type left out, -1 where COCO has no entry to average), "status" (int; bit 0 an invalid ring, bit 1 a ring left
+    out), and the device tensors "tables" (stats, precision, recall) and "pairs" (gt_area_px, dt_area_px, gt_boundary_px, dt_boundary_px, dt_rank,
+    pair_inter, dt_match, dt_ignore, gt_match).  One read-back: the 24 stats and the status."""
+    dp, ds, di, B = _fields(pred, "pred", "coco_metrics")
+    gp, gs, gi, Bg = _fields(gt, "gt", "coco_metrics")
+    if B != Bg:
+        raise hip.P3Error(f"coco_metrics: pred holds {B} images, gt {Bg}")
+    bits = 0
+    for t in iou_types:
+        if t not in IOU_TYPES:
+            raise hip.P3Error(f"coco_metrics: unknown iou type {t!r}; the types are {sorted(IOU_TYPES)}")
+        bits |= IOU_TYPES[t]
+    if not bits:
+        raise hip.P3Error(f"coco_metrics: iou_types is empty; the types are {sorted(IOU_TYPES)}")
+    o = hip.coco_metrics_device(gp, gs, gi, dp, ds, di, B, height, width, bits, dt_score=pred.get("score"), gt_area=gt.get("area"), out=out)
+    *stats, status = torch.cat([o["stats"].reshape(-1), o["status"].to(torch.float64)]).tolist()
+    res = dict(zip(COCO_KEYS, stats[:12]))
+    res["boundary"] = dict(zip(COCO_KEYS, stats[12:]))
+    res["status"] = int(status)
+    res["tables"] = {k: o[k] for k in ("stats", "precision", "recall")}
+    res["pairs"] = {k: o[k] for k in ("gt_area_px", "dt_area_px", "gt_boundary_px", "dt_boundary_px", "dt_rank", "pair_inter", "dt_match", "dt_ignore",
+                                      "gt_match")}
     return res

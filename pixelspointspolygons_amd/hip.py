@@ -1564,6 +1564,64 @@ def polygon_metrics_device(gt_pos, gt_slice, gt_image, dt_pos, dt_slice, dt_imag
     return out
 
 
+# ------------------------------------------------------------------------------------------ COCO AP / AR on instance masks and on their boundaries
+COCO_SEGM, COCO_BOUNDARY = 1, 2          # include/p3hip.h P3_COCO_*
+COCO_KEEP = 100            # csrc/coco_metrics.hip: predictions of an image that take part (maxDets[-1])
+COCO_IOU_LDS = 2048        # pair IoUs of an image, both types, that the match kernel stages in LDS
+
+
+def _ring_field(who, name, t, R, dev):
+    """the optional fp32 [R] field of a ring set (score, area) -> contiguous tensor or None"""
+    if t is None:
+        return None
+    _dev(t)
+    if t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] != R or t.device != dev:
+        raise P3Error(f"{who}: {name} must be float32 [{R}] on {dev}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return t.contiguous()
+
+
+def _coco_sizes(B, H, W, types):
+    if B < 1 or H < 1 or W < 1 or H * W > PM_MAX_HW:
+        raise P3Error(f"coco_metrics: batch_size, height, width >= 1 and height * width <= {PM_MAX_HW} expected, got {B}, {H}, {W}")
+    if types < 1 or types & ~(COCO_SEGM | COCO_BOUNDARY):
+        raise P3Error(f"coco_metrics: iou_types = {types} is not a non-empty set of COCO_SEGM | COCO_BOUNDARY")
+
+
+def coco_metrics_workspace_bytes(R_gt, R_dt, B, height, width, iou_types=COCO_SEGM | COCO_BOUNDARY):
+    """bytes of workspace p3_coco_metrics takes: per ring the 56 bytes of p3_polygon_metrics, 16 of pixel box, 1 of flags and one slab of height *
+    ceil(width / 32) words (three with COCO_BOUNDARY); 400 B of kept lists, 1600 R_gt of pair IoUs, 12 R_dt of ranks and 240 x 13 R_dt of series; each
+    section rounded up to 256"""
+    return int(lib().p3_coco_metrics_workspace_bytes(int(R_gt), int(R_dt), int(B), int(height), int(width), int(iou_types)))
+
+
+def coco_metrics_device(gt_pos, gt_slice, gt_image, dt_pos, dt_slice, dt_image, batch_size, height, width, iou_types=COCO_SEGM | COCO_BOUNDARY, dt_score=None,
+                        gt_area=None, out=None):
+    """p3_coco_metrics (COCO AP / AR on instance masks and on their boundaries; include/p3hip.h) without any synchronisation.  Ring
+    sets as for polygon_metrics_device; dt_score fp32 [R_dt] (None: every score 1.0), gt_area fp32 [R_gt] (None: the ring's own pixel count).
+    -> dict(stats f64 [2,12], precision f64 [2,10,101,4,3], recall f64 [2,10,4,3], gt_area_px, dt_area_px, gt_boundary_px, dt_boundary_px i32 [R],
+    dt_rank i32 [R_dt], pair_inter i32 [2, 100 R_gt], dt_match i32 [2,4,10,R_dt], dt_ignore u8 [2,4,10,R_dt], gt_match i32 [2,4,10,R_gt], status i32 [1]);
+    row 0 is segm, row 1 boundary, a type that is off gives NaN.  out: the caller's own tensors for any of the outputs (`_outputs`)."""
+    gp, gs, gi = _ring_set("coco_metrics", "gt", gt_pos, gt_slice, gt_image)
+    dp, ds, di = _ring_set("coco_metrics", "dt", dt_pos, dt_slice, dt_image)
+    B, H, W, types = int(batch_size), int(height), int(width), int(iou_types)
+    _coco_sizes(B, H, W, types)
+    Rg, Rd = gs.shape[0], ds.shape[0]
+    dev, f64, i32 = gp.device, torch.float64, torch.int32
+    score, area = _ring_field("coco_metrics", "dt_score", dt_score, Rd, dev), _ring_field("coco_metrics", "gt_area", gt_area, Rg, dev)
+    out = _outputs("coco_metrics", dev, (("stats", (2, 12), f64), ("precision", (2, 10, 101, 4, 3), f64), ("recall", (2, 10, 4, 3), f64),
+                                         ("gt_area_px", (Rg,), i32), ("dt_area_px", (Rd,), i32), ("gt_boundary_px", (Rg,), i32), ("dt_boundary_px", (Rd,), i32),
+                                         ("dt_rank", (Rd,), i32), ("pair_inter", (2, COCO_KEEP * Rg), i32), ("dt_match", (2, 4, 10, Rd), i32),
+                                         ("dt_ignore", (2, 4, 10, Rd), torch.uint8), ("gt_match", (2, 4, 10, Rg), i32), ("status", (1,), i32)), out)
+    ws = workspace(coco_metrics_workspace_bytes(Rg, Rd, B, H, W, types), dev, "coco_metrics")
+    o = lambda k: ptr(out[k] if out[k].numel() else None)
+    check(lib().p3_coco_metrics(ptr(gp if Rg else None), gp.shape[0], ptr(gs if Rg else None), ptr(gi if Rg else None), ptr(area if Rg else None), Rg,
+                                ptr(dp if Rd else None), dp.shape[0], ptr(ds if Rd else None), ptr(di if Rd else None), ptr(score if Rd else None), Rd,
+                                B, H, W, types, o("stats"), o("precision"), o("recall"), o("gt_area_px"), o("dt_area_px"), o("gt_boundary_px"),
+                                o("dt_boundary_px"), o("dt_rank"), o("pair_inter"), o("dt_match"), o("dt_ignore"), o("gt_match"), o("status"), ptr(ws),
+                                stream()), "p3_coco_metrics")
+    return out
+
+
 # ------------------------------------------------------------------------------------------ FFL active-skeleton optimiser
 ASM_LDS_CAP = 4096         # csrc/asm.hip: nodes of one connected component that fit the one-launch LDS path
 FFL_POLY_LDS_CAP = 1024    # csrc/ffl_polygons.hip: edge slots of one image (its segments + its segment ends on the border + 4) that run in LDS
