@@ -1188,6 +1188,54 @@ int p3_coco_metrics(const float* gt_pos, int64_t V_gt, const int64_t* gt_slice, 
 int64_t p3_coco_metrics_workspace_bytes(int R_gt, int R_dt, int B, int H, int W, int iou_types);
 void p3_coco_thresholds(double* iou10, double* rec101);
 
+/* ------------------------------------------------------------------------------------------
+ * Max tangent angle error (MTA): the mean over the predicted polygons of the largest angle between a polygon's contour and the ground-truth contour it
+ * projects onto - the reference's eval/angle_eval.py (the Frame Field Learning contour measure), on the device (csrc/mta_metrics.hip).  shapely is not
+ * linked: the text below and its float64 restatement tests/mta_ref.py are the contract, DESIGN.md section 23 says where the text knowingly differs from
+ * angle_eval.py.
+ * Input: two ring sets exactly as for p3_polygon_metrics (pos fp32 [V,2] in (x, y), ring_slice int64 [R,2], ring_image int32 [R] non-decreasing; open
+ * exterior rings).  Ring validity, status bits 0 and 1 and the bound H W <= 2^18 are those of p3_polygon_metrics.  Parameters: sampling_spacing (the
+ * reference: 2.0), min_precision (0.5), max_stretch (2.0).  All arithmetic is in double on the fp32 coordinates converted once, every product and sum
+ * rounded on its own (no fused multiply-add).
+ *   1  masks: the instance mask of a valid prediction ring is p3_coco_metrics step 1 (the even-odd crossing rule at pixel centres, the ring alone), A its
+ *      pixel count; the gt mask of an image is p3_polygon_metrics step 1 (the union of the parities of its valid gt rings); I = the pixels of the
+ *      prediction's mask that are in the gt mask.
+ *   2  precision filter: A == 0: the ring is empty (the reference drops zero-area polygons); else it is kept when (double)I / (double)A > min_precision,
+ *      else it is below precision.
+ *   3  samples of a kept prediction ring: for each edge (p, q) in order, the closing edge last, L = sqrt(dx dx + dy dy) and
+ *      m = max(1, (int)rint(L / sampling_spacing)), rint rounding half to even; the points of the edge are
+ *      p + j ((q - p) / m), j = 0 .. m-1, the step computed per component, and the end point q itself (the last point of a linspace); the first point of
+ *      every edge but the first is skipped, so that the sample line starts at vertex 0 and ends at vertex 0 again: 1 + sum m samples.
+ *   4  projection of a sample s: its nearest point on the edges of all valid gt rings of the same image, closing edges included, rings in set order and
+ *      edges in ring order.  Per edge (p, q): t = ((s - p).(q - p)) / |q - p|^2; the point is p when t <= 0 or the edge has zero length, q when t >= 1,
+ *      else p + t (q - p); the squared distance is e = dx dx + dy dy; the first edge with the strictly smallest e wins.
+ *   5  edges of a ring: for consecutive samples k, k+1: u = s[k+1] - s[k], v = proj[k+1] - proj[k], |u| = sqrt(ux ux + uy uy), |v| likewise; the edge is
+ *      valid when |u| |v| > 0 and 1 / max_stretch < |u| / |v| < max_stretch, both strict; c = fabs((ux vx + uy vy) / (|u| |v|)); ring_cos is the least c
+ *      over the valid edges; a ring without a valid edge has no valid edge (the reference's None).
+ *   6  ring_angle = acos(min(1, ring_cos)) in radians; MTA is the mean of (ring_angle 180) / pi over the counted rings of the whole call, summed in ring
+ *      order, NaN when nothing is counted.
+ *   7  overlap report: per image, image_overlap_px = (sum of A over its valid predictions) - (pixel count of the union of their masks); status bit 2
+ *      (value 4) is set when it is non-zero anywhere: in such an image the reference would have merged the overlapping predictions before measuring.
+ * Outputs: mta fp64 [1] in degrees; counted int32 [1]; ring_angle, ring_cos fp64 [R_dt], NaN unless the ring is counted; ring_state int32 [R_dt]:
+ * P3_MTA_COUNTED, P3_MTA_INVALID (invalid or left out), P3_MTA_EMPTY, P3_MTA_BELOW_PRECISION, P3_MTA_NO_EDGE; ring_px int32 [R_dt,2] = (A, I), both 0 for
+ * P3_MTA_INVALID; image_overlap_px int32 [B]; invalid_rings int32 [B,2] = (gt, dt); status int32 [1].
+ * Errors before any launch, P3_EINVAL with a message: those of p3_polygon_metrics (negative counts, B, H or W < 1, H W above 2^18, null pointers,
+ * ring_slice / ring_image in host memory); sampling_spacing not finite, <= 0 or below 1 / 64 (with coordinates within 2^15 an edge then has fewer than 2^23 samples); min_precision outside [0, 1); max_stretch not finite or <= 1.
+ * Launches depend on the shapes only; no floating-point atomics, no host synchronisation; two runs give the same bits in every per-ring and per-image
+ * output, and so does an image alone or inside a batch.  workspace: p3_max_tangent_angle_workspace_bytes(R_gt, R_dt, B) bytes (0 for B < 1 or a negative
+ * count).
+ * ------------------------------------------------------------------------------------------ */
+#define P3_MTA_COUNTED 0
+#define P3_MTA_INVALID 1
+#define P3_MTA_EMPTY 2
+#define P3_MTA_BELOW_PRECISION 3
+#define P3_MTA_NO_EDGE 4
+int p3_max_tangent_angle(const float* gt_pos, int64_t V_gt, const int64_t* gt_slice, const int32_t* gt_image, int R_gt, const float* dt_pos, int64_t V_dt,
+                         const int64_t* dt_slice, const int32_t* dt_image, int R_dt, int B, int H, int W, double sampling_spacing, double min_precision,
+                         double max_stretch, double* mta, int32_t* counted, double* ring_angle, double* ring_cos, int32_t* ring_state, int32_t* ring_px,
+                         int32_t* image_overlap_px, int32_t* invalid_rings, int32_t* status, void* workspace, void* stream);
+int64_t p3_max_tangent_angle_workspace_bytes(int R_gt, int R_dt, int B);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,4 +1,4 @@
-// p3hip — what the two ring-set scoring stages share (poly_metrics.hip: p3_polygon_metrics; coco_metrics.hip: p3_coco_metrics): the ring set, the ring
+// p3hip — what the ring-set scoring stages share (poly_metrics.hip: p3_polygon_metrics; coco_metrics.hip: p3_coco_metrics; mta_metrics.hip: p3_max_tangent_angle): the ring set, the ring
 // validity routine with its workspace record, the rings of an image by binary search, and the even-odd crossing rule at pixel centres.  DESIGN.md section 21
 // holds the definition.  Every floating-point value is a double made of the fp32 coordinates; contraction is off from here on, so that a product and the sum
 // behind it round as the float64 restatements round them.

@@ -11,7 +11,10 @@ A ring set is a dict(pos fp32 [V,2] in (x, y) order, ring_slice int64 [R,2], rin
 DESIGN.md section 22), with one read-back.  For it a ring set may carry "score" (predictions, fp32 [R]; missing: every score 1.0, which is what the
 reference's annotation writer puts) and "area" (ground truth, fp32 [R]: the annotation's area for the size buckets; missing: the ring's pixel count).
 
-Host synchronisations: `polygon_metrics` and `coco_metrics` have one each, the read-back.  `rings_from_ffl` and `rings_from_hisup` (device dict) each select the kept rings with a
+`max_tangent_angle(pred, gt, height, width)` gives the reference's "MTA" column - the mean max tangent angle error of eval/angle_eval.py, in degrees -
+from p3_max_tangent_angle (csrc/mta_metrics.hip), with one read-back.  A "score" or "area" field of a ring set is ignored.
+
+Host synchronisations: `polygon_metrics`, `coco_metrics` and `max_tangent_angle` have one each, the read-back.  `rings_from_ffl` and `rings_from_hisup` (device dict) each select the kept rings with a
 boolean mask, which makes torch read the number of kept rings back once per indexed tensor (two per call); no coordinate, slice or flag reaches the host.
 `pack_rings` and `rings_from_pix2poly` start from host lists and upload."""
 import numpy as np
@@ -175,3 +178,19 @@ def coco_metrics(pred, gt, height, width, iou_types=("segm", "boundary"), out=No
     res["pairs"] = {k: o[k] for k in ("gt_area_px", "dt_area_px", "gt_boundary_px", "dt_boundary_px", "dt_rank", "pair_inter", "dt_match", "dt_ignore",
                                       "gt_match")}
     return res
+
+
+def max_tangent_angle(pred, gt, height, width, sampling_spacing=2.0, min_precision=0.5, max_stretch=2.0, out=None):
+    """pred, gt: ring sets of the same batch (a "score" or "area" field is ignored).  -> dict with the reference's key "MTA" as a Python float in degrees
+    (NaN when no ring is counted), "counted" (int: the rings the mean runs over), "status" (int; bit 0 an invalid ring, bit 1 a ring left out, bit 2
+    predictions of an image overlap: the reference would have merged them), and the device tensors "per_ring" (angle in radians, cos, state = hip.MTA_*,
+    px = (A, I)) and "per_image" (overlap_px, invalid_rings).  The defaults are the reference's.  One read-back: MTA, counted and status together."""
+    dp, ds, di, B = _fields(pred, "pred", "max_tangent_angle")
+    gp, gs, gi, Bg = _fields(gt, "gt", "max_tangent_angle")
+    if B != Bg:
+        raise hip.P3Error(f"max_tangent_angle: pred holds {B} images, gt {Bg}")
+    o = hip.max_tangent_angle_device(gp, gs, gi, dp, ds, di, B, height, width, sampling_spacing, min_precision, max_stretch, out=out)
+    mta, counted, status = torch.cat([o["mta"], o["counted"].to(torch.float64), o["status"].to(torch.float64)]).tolist()
+    return {"MTA": mta, "counted": int(counted), "status": int(status),
+            "per_ring": {"angle": o["ring_angle"], "cos": o["ring_cos"], "state": o["ring_state"], "px": o["ring_px"]},
+            "per_image": {"overlap_px": o["image_overlap_px"], "invalid_rings": o["invalid_rings"]}}

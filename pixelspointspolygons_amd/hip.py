@@ -1622,6 +1622,48 @@ def coco_metrics_device(gt_pos, gt_slice, gt_image, dt_pos, dt_slice, dt_image, 
     return out
 
 
+# ------------------------------------------------------------------------------------------ max tangent angle error (MTA)
+MTA_COUNTED, MTA_INVALID, MTA_EMPTY, MTA_BELOW_PRECISION, MTA_NO_EDGE = 0, 1, 2, 3, 4          # include/p3hip.h P3_MTA_*: ring_state
+MTA_MIN_SPACING = 1.0 / 64          # csrc/mta_metrics.hip: a smaller sampling_spacing is refused, which bounds the samples of a ring
+
+
+def max_tangent_angle_workspace_bytes(R_gt, R_dt, B):
+    """bytes of workspace p3_max_tangent_angle takes: the ring records of p3_polygon_metrics (24 bytes of state, vertex count, first vertex and 32 of box
+    per ring, each section rounded up to 256) and nothing else: masks, samples and projected points live in LDS"""
+    return int(lib().p3_max_tangent_angle_workspace_bytes(int(R_gt), int(R_dt), int(B)))
+
+
+def max_tangent_angle_device(gt_pos, gt_slice, gt_image, dt_pos, dt_slice, dt_image, batch_size, height, width, sampling_spacing=2.0, min_precision=0.5,
+                             max_stretch=2.0, out=None):
+    """p3_max_tangent_angle (the mean max tangent angle error of eval/angle_eval.py; include/p3hip.h) without any synchronisation.
+    Ring sets as for polygon_metrics_device: gt_* the ground truth, dt_* the predictions.  sampling_spacing >= MTA_MIN_SPACING = 1 / 64.
+    -> dict(mta f64 [1] in degrees (NaN when nothing is counted), counted i32 [1], ring_angle (radians), ring_cos f64 [R_dt] (NaN unless the ring is
+    counted), ring_state i32 [R_dt] (MTA_COUNTED, MTA_INVALID: invalid or left out, MTA_EMPTY: no pixel, MTA_BELOW_PRECISION, MTA_NO_EDGE), ring_px i32
+    [R_dt,2] = (A, I), image_overlap_px i32 [B], invalid_rings i32 [B,2] = (gt, dt), status i32 [1] (bits 0 and 1 as for polygon_metrics_device; bit 2:
+    predictions of an image overlap, which the reference would have merged)).  out: the caller's own tensors for any of the outputs (`_outputs`)."""
+    gp, gs, gi = _ring_set("max_tangent_angle", "gt", gt_pos, gt_slice, gt_image)
+    dp, ds, di = _ring_set("max_tangent_angle", "dt", dt_pos, dt_slice, dt_image)
+    B, H, W = int(batch_size), int(height), int(width)
+    spacing, precision, stretch = float(sampling_spacing), float(min_precision), float(max_stretch)
+    if B < 1 or H < 1 or W < 1 or H * W > PM_MAX_HW:
+        raise P3Error(f"max_tangent_angle: batch_size, height, width >= 1 and height * width <= {PM_MAX_HW} expected, got {B}, {H}, {W}")
+    if not (MTA_MIN_SPACING <= spacing < math.inf and 0.0 <= precision < 1.0 and 1.0 < stretch < math.inf):
+        raise P3Error(f"max_tangent_angle: finite sampling_spacing >= 1 / 64, min_precision in [0, 1) and finite max_stretch > 1 expected, got {spacing}, "
+                      f"{precision}, {stretch}")
+    Rg, Rd = gs.shape[0], ds.shape[0]
+    dev, f64, i32 = gp.device, torch.float64, torch.int32
+    out = _outputs("max_tangent_angle", dev, (("mta", (1,), f64), ("counted", (1,), i32), ("ring_angle", (Rd,), f64), ("ring_cos", (Rd,), f64),
+                                              ("ring_state", (Rd,), i32), ("ring_px", (Rd, 2), i32), ("image_overlap_px", (B,), i32),
+                                              ("invalid_rings", (B, 2), i32), ("status", (1,), i32)), out)
+    ws = workspace(max_tangent_angle_workspace_bytes(Rg, Rd, B), dev, "max_tangent_angle")
+    o = lambda k: ptr(out[k] if out[k].numel() else None)
+    check(lib().p3_max_tangent_angle(ptr(gp if Rg else None), gp.shape[0], ptr(gs if Rg else None), ptr(gi if Rg else None), Rg,
+                                     ptr(dp if Rd else None), dp.shape[0], ptr(ds if Rd else None), ptr(di if Rd else None), Rd, B, H, W, spacing, precision,
+                                     stretch, o("mta"), o("counted"), o("ring_angle"), o("ring_cos"), o("ring_state"), o("ring_px"), o("image_overlap_px"),
+                                     o("invalid_rings"), o("status"), ptr(ws), stream()), "p3_max_tangent_angle")
+    return out
+
+
 # ------------------------------------------------------------------------------------------ FFL active-skeleton optimiser
 ASM_LDS_CAP = 4096         # csrc/asm.hip: nodes of one connected component that fit the one-launch LDS path
 FFL_POLY_LDS_CAP = 1024    # csrc/ffl_polygons.hip: edge slots of one image (its segments + its segment ends on the border + 4) that run in LDS
