@@ -1236,6 +1236,53 @@ int p3_max_tangent_angle(const float* gt_pos, int64_t V_gt, const int64_t* gt_sl
                          int32_t* image_overlap_px, int32_t* invalid_rings, int32_t* status, void* workspace, void* stream);
 int64_t p3_max_tangent_angle_workspace_bytes(int R_gt, int R_dt, int B);
 
+/* ------------------------------------------------------------------------------------------
+ * Mask and topology metrics, subset IoU and annotation counts: the modes `topdig` (eval/topdig_metrics.py compute_mask_metrics: pixel accuracy, F1 and IoU
+ * of the filled union masks and of the "topology" masks, the polygon outlines stroked buffer_thickness pixels thick), `subset_iou`
+ * (compute_IoU_cIoU(subset=True): IoU, C-IoU and NR over the images that have a prediction) and `stats` (compute_coco_stats) of the reference's
+ * Evaluator.evaluate, on the device (csrc/mask_metrics.hip).  Neither OpenCV, pycocotools nor torchmetrics is linked: the text below and its
+ * float64 / Python-integer restatement tests/mask_metrics_ref.py are the contract, DESIGN.md section 24 says where the text knowingly differs from them.
+ * Input: two ring sets exactly as for p3_polygon_metrics (pos fp32 [V,2] in (x, y), ring_slice int64 [R,2], ring_image int32 [R] non-decreasing; open
+ * exterior rings).  Ring validity, status bits 0 and 1 and the bound H W <= 2^18 are those of p3_polygon_metrics.  buffer_thickness = T (the reference: 5).
+ *   1  filled mask of a set in image b: p3_polygon_metrics step 1 (the even-odd rule at the pixel centres (c + 0.5, r + 0.5), the union of the parities of
+ *      the valid rings).
+ *   2  stroked mask of a set in image b: each vertex of a valid ring becomes the integer point q = (rint(x), rint(y)), rint of the double made of the fp32
+ *      coordinate, half to even (with |x| <= 2^15 it fits int32).  Pixel (r, c) is the integer point p = (c, r), not its centre (OpenCV's convention).
+ *      For every edge (a, b) of the ring, the closing one included: d = b - a, u = p - a, L2 = d.d, t = u.d; the pixel is set when the first matching
+ *      condition holds:  L2 == 0 or t <= 0: 4 u.u <= T T;  t >= L2: 4 |p - b|^2 <= T T;  otherwise 4 (u.x d.y - u.y d.x)^2 <= T T L2  - the pixel lies
+ *      within T / 2 of the segment, decided in exact integer arithmetic.  The mask is the union over the edges of all valid rings of the set in image b.
+ *   3  confusion counts per image and mask kind, p the prediction mask and g the gt mask: TP = |p & g|, FP = |p & ~g|, FN = |~p & g|,
+ *      TN = H W - TP - FP - FN, int32.  TP + FP + FN == 0: acc = f1 = iou = 1.0; else acc = (double)(TP + TN) / (double)(H W),
+ *      f1 = (double)(2 TP) / (double)(2 TP + FP + FN), iou = (double)TP / ((double)(TP + FP + FN) + 1e-9): one correctly rounded division each, the
+ *      iou one addition before it.
+ *   4  TopDiG means: IoU_, P-Acc, F1-Score from the filled masks, IoU-Topo, P-Acc-Topo, F1-Score-Topo from the stroked masks, each the sum over the B
+ *      images in image order divided by B.
+ *   5  subset: image b is in the subset when the prediction set has at least one ring with ring_image == b, whatever its state.  Per image iou is step 3
+ *      on the filled masks and nr is p3_polygon_metrics step 2 (the vertex counts of the valid rings).  sIoU, sC-IoU (the products iou nr) and sNR are the
+ *      means over the subset, summed in image order; NaN when the subset is empty.
+ *   6  stats int64 [7] = (B, images with at least one counted gt ring, images with at least one counted prediction ring, gt rings, prediction rings, gt
+ *      vertices, prediction vertices).  A ring is counted unless it is left out (status bit 1); its vertices are its slice length, valid or not.
+ * modes: P3_MM_TOPDIG (steps 1-4), P3_MM_SUBSET (steps 1, 3, 5), P3_MM_STATS (step 6), any non-empty set.  A mode that is off leaves NaN in its
+ * floating-point outputs and 0 in its integer outputs: without P3_MM_TOPDIG metrics[0..5] and image_scores are NaN and the stroked row of image_conf is 0;
+ * without P3_MM_SUBSET metrics[6..8] and image_nr are NaN and image_subset is 0; without both the filled row of image_conf is 0 too; without P3_MM_STATS
+ * stats is 0.  invalid_rings and status do not depend on modes.
+ * Outputs: metrics fp64 [9] = (IoU_, P-Acc, F1-Score, IoU-Topo, P-Acc-Topo, F1-Score-Topo, sIoU, sC-IoU, sNR); stats int64 [7]; image_conf int32 [B,2,4]
+ * = (filled, stroked) x (TP, FP, FN, TN); image_scores fp64 [B,6], per image in the order of metrics[0..5]; image_nr fp64 [B]; image_subset int32 [B];
+ * invalid_rings int32 [B,2] = (gt, dt); status int32 [1].
+ * Errors before any launch, P3_EINVAL with a message: those of p3_polygon_metrics (negative counts, B, H or W < 1, H W above 2^18, null pointers,
+ * ring_slice / ring_image in host memory); buffer_thickness outside [1, 64]; an empty or unknown modes.
+ * Launches depend on the shapes and modes only; no floating-point atomics, no host synchronisation; two runs, an image alone or inside a batch give the
+ * same bits.  workspace: p3_mask_metrics_workspace_bytes(R_gt, R_dt, B) bytes (0 for B < 1 or a negative count).
+ * ------------------------------------------------------------------------------------------ */
+#define P3_MM_TOPDIG 1
+#define P3_MM_SUBSET 2
+#define P3_MM_STATS 4
+int p3_mask_metrics(const float* gt_pos, int64_t V_gt, const int64_t* gt_slice, const int32_t* gt_image, int R_gt, const float* dt_pos, int64_t V_dt,
+                    const int64_t* dt_slice, const int32_t* dt_image, int R_dt, int B, int H, int W, int buffer_thickness, int modes, double* metrics,
+                    int64_t* stats, int32_t* image_conf, double* image_scores, double* image_nr, int32_t* image_subset, int32_t* invalid_rings,
+                    int32_t* status, void* workspace, void* stream);
+int64_t p3_mask_metrics_workspace_bytes(int R_gt, int R_dt, int B);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,5 @@
-// p3hip — what the ring-set scoring stages share (poly_metrics.hip: p3_polygon_metrics; coco_metrics.hip: p3_coco_metrics; mta_metrics.hip: p3_max_tangent_angle): the ring set, the ring
-// validity routine with its workspace record, the rings of an image by binary search, and the even-odd crossing rule at pixel centres.  DESIGN.md section 21
+// p3hip — what the ring-set scoring stages share (poly_metrics.hip: p3_polygon_metrics; coco_metrics.hip: p3_coco_metrics; mta_metrics.hip: p3_max_tangent_angle; mask_metrics.hip: p3_mask_metrics): the ring set, the ring
+// validity routine with its workspace record, the rings of an image by binary search, the even-odd crossing rule at pixel centres and the filled union mask of a set (pm_raster_set).  DESIGN.md section 21
 // holds the definition.  Every floating-point value is a double made of the fp32 coordinates; contraction is off from here on, so that a product and the sum
 // behind it round as the float64 restatements round them.
 #pragma once
@@ -98,6 +98,51 @@ __device__ __forceinline__ void pm_stage_edges(const float2* pos, int64_t first,
         const int i = e0 + tid, j = i + 1 == n ? 0 : i + 1;
         const float2 pa = pos[first + i], pb = pos[first + j];
         edges[tid] = {(double)pa.x, (double)pa.y, (double)pb.x, (double)pb.y};
+    }
+}
+
+// ---- the filled mask of a set ---------------------------------------------------------------------------------------------------------------------------
+// the rings of one set of image b into `mask` (bit r W + c of the packed words): the parity of each valid ring, ORed in.  Every thread of a workgroup of
+// PM_THREADS calls it; `edges`: PM_EDGE_CHUNK of them in LDS; the caller clears the mask before and puts a barrier behind the call
+__device__ inline void pm_raster_set(const PmSet& s, const PmRings& w, int b, int H, int W, uint32_t* mask, PmEdge* edges) {
+    const int tid = threadIdx.x;
+    const int r_lo = pm_lower(s.image, s.R, b), r_hi = pm_lower(s.image, s.R, b + 1);
+    for (int r = r_lo; r < r_hi; ++r) {
+        if (w.state[r] != 1) continue;          // uniform over the workgroup
+        const int n = w.n[r];
+        const int64_t first = w.first[r];
+        int r0, r1, c0, c1;          // rows and columns whose centres can lie inside
+        if (!pm_pixel_box(w.box + 4 * (int64_t)r, H, W, r0, r1, c0, c1)) continue;
+        const int per_row = ((c1 - c0) >> 5) + 2;          // words a row's [c0, c1] can touch
+        const int units = (r1 - r0 + 1) * per_row;
+        for (int base = 0; base < units; base += PM_THREADS) {
+            const int u = base + tid;
+            const int row = r0 + u / per_row;
+            const int bit0 = row * W + c0, bit1 = row * W + c1;          // H W <= 2^18: no overflow
+            const int word = (bit0 >> 5) + u % per_row;
+            const bool active = u < units && word <= (bit1 >> 5);
+            const int lo = bit0 > (word << 5) ? bit0 : (word << 5), hi = bit1 < (word << 5) + 31 ? bit1 : (word << 5) + 31;
+            const double py = (double)row + 0.5;
+            uint32_t parity = 0;
+            for (int e0 = 0; e0 < n; e0 += PM_EDGE_CHUNK) {
+                const int cnt = n - e0 < PM_EDGE_CHUNK ? n - e0 : PM_EDGE_CHUNK;
+                __syncthreads();          // the last chunk has been read
+                pm_stage_edges(s.pos, first, n, e0, cnt, edges);
+                __syncthreads();
+                if (!active) continue;
+                for (int k = 0; k < cnt; ++k) {
+                    const PmEdge ed = edges[k];
+                    if (!pm_crossed(ed, py)) continue;          // not crossed by this row's centres
+                    const double ex = ed.bx - ed.ax, ey = ed.by - ed.ay, wy = py - ed.ay;
+                    const double t1 = ex * wy;
+                    for (int bit = lo; bit <= hi; ++bit) {
+                        const double px = (double)(bit - row * W) + 0.5;
+                        if (pm_right_of(ed, t1, ey, px)) parity ^= 1u << (bit & 31);
+                    }
+                }
+            }
+            if (active && parity) atomicOr(mask + word, parity);
+        }
     }
 }
 

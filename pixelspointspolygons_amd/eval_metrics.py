@@ -14,7 +14,12 @@ reference's annotation writer puts) and "area" (ground truth, fp32 [R]: the anno
 `max_tangent_angle(pred, gt, height, width)` gives the reference's "MTA" column - the mean max tangent angle error of eval/angle_eval.py, in degrees -
 from p3_max_tangent_angle (csrc/mta_metrics.hip), with one read-back.  A "score" or "area" field of a ring set is ignored.
 
-Host synchronisations: `polygon_metrics`, `coco_metrics` and `max_tangent_angle` have one each, the read-back.  `rings_from_ffl` and `rings_from_hisup` (device dict) each select the kept rings with a
+`mask_metrics(pred, gt, height, width)` gives the reference's modes "topdig" (eval/topdig_metrics.py: IoU, pixel accuracy and F1 of the filled masks and
+of the outlines stroked 5 pixels thick), "subset_iou" (compute_IoU_cIoU(subset=True)) and "stats" (compute_coco_stats) from p3_mask_metrics
+(csrc/mask_metrics.hip), with one read-back.  `evaluate(pred, gt, height, width, modes)` takes the reference's
+cfg.evaluation.modes and makes at most four such calls.
+
+Host synchronisations: `polygon_metrics`, `coco_metrics`, `max_tangent_angle` and `mask_metrics` have one each, the read-back; `evaluate` has one per call it makes.  `rings_from_ffl` and `rings_from_hisup` (device dict) each select the kept rings with a
 boolean mask, which makes torch read the number of kept rings back once per indexed tensor (two per call); no coordinate, slice or flag reaches the host.
 `pack_rings` and `rings_from_pix2poly` start from host lists and upload."""
 import numpy as np
@@ -25,6 +30,10 @@ from . import hip
 MODES = {"iou": hip.PM_IOU, "polis": hip.PM_POLIS, "chamfer": hip.PM_SAMPLES, "hausdorff": hip.PM_SAMPLES}
 KEYS = ("IoU", "C-IoU", "NR", "POLIS", "chamfer", "hausdorff")
 IOU_TYPES = {"segm": hip.COCO_SEGM, "boundary": hip.COCO_BOUNDARY}
+MASK_MODES = {"topdig": hip.MM_TOPDIG, "subset_iou": hip.MM_SUBSET, "stats": hip.MM_STATS}
+MASK_KEYS = ("IoU_", "P-Acc", "F1-Score", "IoU-Topo", "P-Acc-Topo", "F1-Score-Topo", "sIoU", "sC-IoU", "sNR")
+STATS_KEYS = ("#images", "GT #images w/ polys", "Pred #images w/ polys", "GT #polygons", "Pred #polygons", "GT #vertices", "Pred #vertices")
+EVALUATE_MODES = ("iou", "polis", "chamfer", "hausdorff", "topdig", "subset_iou", "stats", "mta", "coco", "boundary-coco", "ldof")
 COCO_KEYS = ("AP", "AP50", "AP75", "AP_small", "AP_medium", "AP_large", "AR1", "AR10", "AR100", "AR_small", "AR_medium", "AR_large")
 
 
@@ -194,3 +203,76 @@ def max_tangent_angle(pred, gt, height, width, sampling_spacing=2.0, min_precisi
     return {"MTA": mta, "counted": int(counted), "status": int(status),
             "per_ring": {"angle": o["ring_angle"], "cos": o["ring_cos"], "state": o["ring_state"], "px": o["ring_px"]},
             "per_image": {"overlap_px": o["image_overlap_px"], "invalid_rings": o["invalid_rings"]}}
+
+
+def mask_metrics(pred, gt, height, width, modes=("topdig", "subset_iou", "stats"), buffer_thickness=5, out=None):
+    """pred, gt: ring sets of the same batch (a "score" or "area" field is ignored).  -> dict with the reference's keys "IoU_", "P-Acc", "F1-Score",
+    "IoU-Topo", "P-Acc-Topo", "F1-Score-Topo" (topdig) and "sIoU", "sC-IoU", "sNR" (subset_iou; NaN when no image has a prediction) as Python floats, NaN
+    for a mode left out; "#images", "GT #images w/ polys", "Pred #images w/ polys", "GT #polygons", "Pred #polygons", "GT #vertices", "Pred #vertices"
+    (stats) as ints, 0 when left out; "status" (int; bit 0 an invalid ring, bit 1 a ring left out), and the device tensors "per_image" (conf = (filled,
+    stroked) x (TP, FP, FN, TN), scores in the order of the six topdig keys, nr, subset, invalid_rings).  buffer_thickness: the width of the stroked
+    outlines, the reference's 5.  One read-back: the nine means, the seven counts and the status."""
+    dp, ds, di, B = _fields(pred, "pred", "mask_metrics")
+    gp, gs, gi, Bg = _fields(gt, "gt", "mask_metrics")
+    if B != Bg:
+        raise hip.P3Error(f"mask_metrics: pred holds {B} images, gt {Bg}")
+    bits = 0
+    for m in modes:
+        if m not in MASK_MODES:
+            raise hip.P3Error(f"mask_metrics: unknown mode {m!r}; the modes are {sorted(MASK_MODES)}")
+        bits |= MASK_MODES[m]
+    if not bits:
+        raise hip.P3Error(f"mask_metrics: modes is empty; the modes are {sorted(MASK_MODES)}")
+    o = hip.mask_metrics_device(gp, gs, gi, dp, ds, di, B, height, width, buffer_thickness, bits, out=out)
+    # counts below 2^53 are exact as doubles: that is every ring set whose slices do not overlap
+    flat = torch.cat([o["metrics"], o["stats"].to(torch.float64), o["status"].to(torch.float64)]).tolist()
+    res = dict(zip(MASK_KEYS, flat[:9]))
+    res.update(zip(STATS_KEYS, (int(v) for v in flat[9:16])))
+    res["status"] = int(flat[16])
+    res["per_image"] = {"conf": o["image_conf"], "scores": o["image_scores"], "nr": o["image_nr"], "subset": o["image_subset"],
+                        "invalid_rings": o["invalid_rings"]}
+    return res
+
+
+def evaluate(pred, gt, height, width, modes):
+    """the polygon-only part of the reference's Evaluator.evaluate: modes with the reference's names (cfg.evaluation.modes), grouped into at most four
+    calls - polygon_metrics for "iou", "polis", "chamfer", "hausdorff"; mask_metrics for "topdig", "subset_iou", "stats"; max_tangent_angle for "mta";
+    coco_metrics for "coco", "boundary-coco" - each with its defaults.  -> dict with the reference's keys of the modes asked for merged into one (the
+    boundary table under "boundary", as coco_metrics returns it), "status": the statuses ORed, and "calls": function name -> that call's full result.  One
+    read-back per call made.  "ldof" needs the reference's external executable and raises."""
+    modes = list(modes)
+    for m in modes:
+        if m not in EVALUATE_MODES:
+            raise hip.P3Error(f"evaluate: unknown mode {m!r}; the modes are {list(EVALUATE_MODES)}")
+    if "ldof" in modes:
+        raise hip.P3Error("evaluate: the mode 'ldof' needs the reference's external executable (its ldof binary) and has no device path")
+    if not modes:
+        raise hip.P3Error(f"evaluate: modes is empty; the modes are {list(EVALUATE_MODES)}")
+    res, calls, status = {}, {}, 0
+    pm = [m for m in modes if m in MODES]
+    if pm:
+        c = calls["polygon_metrics"] = polygon_metrics(pred, gt, height, width, modes=pm)
+        if "iou" in pm:
+            res.update({k: c[k] for k in KEYS[:3]})
+        res.update({k: c[k] for k in KEYS[3:] if k.lower() in pm})
+    mm = [m for m in modes if m in MASK_MODES]
+    if mm:
+        c = calls["mask_metrics"] = mask_metrics(pred, gt, height, width, modes=mm)
+        for m, keys in (("topdig", MASK_KEYS[:6]), ("subset_iou", MASK_KEYS[6:]), ("stats", STATS_KEYS)):
+            if m in mm:
+                res.update({k: c[k] for k in keys})
+    if "mta" in modes:
+        c = calls["max_tangent_angle"] = max_tangent_angle(pred, gt, height, width)
+        res["MTA"] = c["MTA"]
+    types = [t for m, t in (("coco", "segm"), ("boundary-coco", "boundary")) if m in modes]
+    if types:
+        c = calls["coco_metrics"] = coco_metrics(pred, gt, height, width, iou_types=types)
+        if "coco" in modes:
+            res.update({k: c[k] for k in COCO_KEYS})
+        if "boundary-coco" in modes:
+            res["boundary"] = c["boundary"]
+    for c in calls.values():
+        status |= c["status"]
+    res["status"] = status
+    res["calls"] = calls
+    return res

@@ -1664,6 +1664,49 @@ def max_tangent_angle_device(gt_pos, gt_slice, gt_image, dt_pos, dt_slice, dt_im
     return out
 
 
+# ------------------------------------------------------------------------------------------ mask / topology metrics, subset IoU, annotation counts
+MM_TOPDIG, MM_SUBSET, MM_STATS = 1, 2, 4          # include/p3hip.h P3_MM_*
+MM_MAX_THICKNESS = 64      # csrc/mask_metrics.hip: the largest buffer_thickness
+
+
+def mask_metrics_workspace_bytes(R_gt, R_dt, B):
+    """bytes of workspace p3_mask_metrics takes: the ring records of p3_polygon_metrics (24 bytes of state, vertex count, first vertex and 32 of box per
+    ring) and 32 bytes of counts per image, each section rounded up to 256; the masks live in LDS"""
+    return int(lib().p3_mask_metrics_workspace_bytes(int(R_gt), int(R_dt), int(B)))
+
+
+def mask_metrics_device(gt_pos, gt_slice, gt_image, dt_pos, dt_slice, dt_image, batch_size, height, width, buffer_thickness=5,
+                        modes=MM_TOPDIG | MM_SUBSET | MM_STATS, out=None):
+    """p3_mask_metrics (the reference's modes topdig, subset_iou and stats; include/p3hip.h) without any synchronisation.  Ring sets
+    as for polygon_metrics_device: gt_* the ground truth, dt_* the predictions.  buffer_thickness in [1, MM_MAX_THICKNESS]: the width of the stroked
+    outlines (the reference: 5).  modes: MM_TOPDIG | MM_SUBSET | MM_STATS; a mode that is off leaves NaN in its floating-point outputs and 0 in its
+    integer ones.
+    -> dict(metrics f64 [9] = (IoU_, P-Acc, F1-Score, IoU-Topo, P-Acc-Topo, F1-Score-Topo, sIoU, sC-IoU, sNR), stats i64 [7] = (images, images with gt
+    rings, images with predictions, gt rings, predictions, gt vertices, prediction vertices), image_conf i32 [B,2,4] = (filled, stroked) x (TP, FP, FN,
+    TN), image_scores f64 [B,6] in the order of metrics[0..5], image_nr f64 [B], image_subset i32 [B], invalid_rings i32 [B,2] = (gt, dt), status i32 [1]
+    (bits 0 and 1 as for polygon_metrics_device)).  out: the caller's own tensors for any of the outputs (`_outputs`)."""
+    gp, gs, gi = _ring_set("mask_metrics", "gt", gt_pos, gt_slice, gt_image)
+    dp, ds, di = _ring_set("mask_metrics", "dt", dt_pos, dt_slice, dt_image)
+    B, H, W, T, modes = int(batch_size), int(height), int(width), int(buffer_thickness), int(modes)
+    if B < 1 or H < 1 or W < 1 or H * W > PM_MAX_HW:
+        raise P3Error(f"mask_metrics: batch_size, height, width >= 1 and height * width <= {PM_MAX_HW} expected, got {B}, {H}, {W}")
+    if not 1 <= T <= MM_MAX_THICKNESS:
+        raise P3Error(f"mask_metrics: buffer_thickness in [1, {MM_MAX_THICKNESS}] expected, got {buffer_thickness}")
+    if modes < 1 or modes & ~(MM_TOPDIG | MM_SUBSET | MM_STATS):
+        raise P3Error(f"mask_metrics: modes = {modes} is not a non-empty set of MM_TOPDIG | MM_SUBSET | MM_STATS")
+    Rg, Rd = gs.shape[0], ds.shape[0]
+    dev, f64, i32 = gp.device, torch.float64, torch.int32
+    out = _outputs("mask_metrics", dev, (("metrics", (9,), f64), ("stats", (7,), torch.int64), ("image_conf", (B, 2, 4), i32), ("image_scores", (B, 6), f64),
+                                         ("image_nr", (B,), f64), ("image_subset", (B,), i32), ("invalid_rings", (B, 2), i32), ("status", (1,), i32)), out)
+    ws = workspace(mask_metrics_workspace_bytes(Rg, Rd, B), dev, "mask_metrics")
+    o = lambda k: ptr(out[k])
+    check(lib().p3_mask_metrics(ptr(gp if Rg else None), gp.shape[0], ptr(gs if Rg else None), ptr(gi if Rg else None), Rg,
+                                ptr(dp if Rd else None), dp.shape[0], ptr(ds if Rd else None), ptr(di if Rd else None), Rd, B, H, W, T, modes,
+                                o("metrics"), o("stats"), o("image_conf"), o("image_scores"), o("image_nr"), o("image_subset"), o("invalid_rings"),
+                                o("status"), ptr(ws), stream()), "p3_mask_metrics")
+    return out
+
+
 # ------------------------------------------------------------------------------------------ FFL active-skeleton optimiser
 ASM_LDS_CAP = 4096         # csrc/asm.hip: nodes of one connected component that fit the one-launch LDS path
 FFL_POLY_LDS_CAP = 1024    # csrc/ffl_polygons.hip: edge slots of one image (its segments + its segment ends on the border + 4) that run in LDS
